@@ -221,16 +221,6 @@ def respawn(a):
     env = dict(os.environ)
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     env.setdefault("OMP_NUM_THREADS", str(max(1, (os.cpu_count() or 8) // a.gpus)))
-    try:
-        import torch
-        if torch.cuda.device_count() < a.gpus:
-            # ranks SHARING a device (functional check, gloo): every process brings its update stream, the second micro-batch's stream and
-            # gloo's private copy streams.  With ROCm's default of 4 hardware queues per process the streams are multiplexed onto the same
-            # queues and the phased side-by-side form crawled (10 s per update, tools/r6/call9.sh / call10.sh; 0.3 s with 8 queues).  The
-            # runtime reads the variable when it is loaded, so it has to be in the children's environment.  Ranks with a GPU each: default.
-            env.setdefault("GPU_MAX_HW_QUEUES", "8")
-    except Exception:
-        pass
     sys.exit(subprocess.call(cmd, env=env))
 
 
@@ -281,6 +271,30 @@ def emit(obj):
         os.write(_RESULT_FD, line)
 
 
+DUMP_SAMPLE = 1 << 22     # elements drawn from each flat optimizer buffer (3 x 16 MB in fp32)
+DUMP_SEED = 20240917
+
+
+def dump_outputs(upd, out_dir):
+    """What the timed update hands its caller after the last timed step: the fp32 master parameters and Adam's two moments (flat
+    buffers, ~154 M elements each for Base) and the squared global gradient norm the clip used.  The flat buffers go out as the
+    same fixed, seeded sample of positions (with replacement, sorted) so that the files stay under 64 MB; the rest in full.
+    The gradient buffers are not dumped: the Adam kernel consumes them (leaves them zeroed)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    opt = upd.opt
+    if opt.pflat.is_cuda:
+        torch.cuda.synchronize(opt.pflat.device)
+    n = opt.pflat.numel()
+    g = torch.Generator().manual_seed(DUMP_SEED)
+    idx = torch.randint(0, n, (min(DUMP_SAMPLE, n),), generator=g).sort().values.to(opt.pflat.device)
+    outs = {"params_sample": opt.pflat, "adam_exp_avg_sample": opt.m, "adam_exp_avg_sq_sample": opt.v}
+    for name, buf in outs.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), buf.index_select(0, idx).float().cpu().numpy())
+    np.save(os.path.join(out_dir, "grad_sumsq.npy"), opt.gnorm_sq.double().cpu().numpy())
+    np.save(os.path.join(out_dir, "adam_step.npy"), np.array([opt.t], dtype=np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -310,7 +324,14 @@ def main():
                     help="BASELINE.json configs[]: 2 = the pre-training update (the headline metric, default); 3 = TTS fine-tuning step "
                          "(32 texts x 100 tokens -> 600 mel frames, guided attention, replayed) + full-size HiFi-GAN on the same "
                          "32 x 600 frames, one GPU")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (parameters and Adam moments: a fixed seeded sample "
+                         "of the flat buffers; the squared gradient norm; the step count) as DIR/<name>.npy, for comparing two builds")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.dump_outputs is not None and a.config != 2:
+        ap.error("--dump-outputs applies to the pre-training update (--config 2)")
     if _AS_SCRIPT and ("WORLD_SIZE" in os.environ or a.gpus == 1):   # (not in the parent that only re-executes itself under torch.distributed.run)
         quiet_stdout()
     if a.config == 3:
@@ -413,6 +434,8 @@ def main():
     dt = time.perf_counter() - t0
     upd.finish()
     hip.profiler.enabled = False
+    if a.dump_outputs is not None and rank == 0:   # (before the untimed updates below move the parameters on)
+        dump_outputs(upd, a.dump_outputs)
     if use_graph:
         # roofline leg of the graph mode: the replayed launches carry no events, so the SAME update is enqueued once more
         # eagerly, outside the timed region, with HIP events around every st5_gemm launch (same kernels, shapes, streams; the

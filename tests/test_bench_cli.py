@@ -42,3 +42,35 @@ def test_flags_of_the_driver_contract_parse(monkeypatch):
     bench.main()
     assert got["config"] == 3 and got["steps"] == 4 and got["warmup"] == 2 and got["gpus"] == 1
     assert got["exchange"] == "phased" and got["micro"] == "side_by_side" and got["layerdrop"] == 0.05
+
+
+def test_dump_outputs_writes_a_fixed_sample_in_float(tmp_path):
+    """--dump-outputs: the flat optimizer buffers as the same seeded sample of positions every time, every file float32 / float64,
+    under 64 MB in all."""
+    import numpy as np
+    import torch
+    import bench
+    n = 3 * bench.DUMP_SAMPLE + 17
+    opt = Namespace(pflat=torch.arange(n, dtype=torch.float32), m=torch.arange(n, dtype=torch.float32) * 2,
+                    v=torch.arange(n, dtype=torch.float32) * 3, gnorm_sq=torch.tensor([4.5]), t=7)
+    for d in ("a", "b"):
+        bench.dump_outputs(Namespace(opt=opt), str(tmp_path / d))
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == sorted(["params_sample.npy", "adam_exp_avg_sample.npy", "adam_exp_avg_sq_sample.npy", "grad_sumsq.npy", "adam_step.npy"])
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in names) <= 64 * 2 ** 20
+    for f in names:
+        a, b = np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)
+        assert a.dtype in (np.float32, np.float64) and np.array_equal(a, b), f
+    p, m = np.load(tmp_path / "a" / "params_sample.npy"), np.load(tmp_path / "a" / "adam_exp_avg_sample.npy")
+    assert p.shape == (bench.DUMP_SAMPLE,) and np.array_equal(m, 2 * p) and len(np.unique(p)) > bench.DUMP_SAMPLE // 2
+    assert float(np.load(tmp_path / "a" / "adam_step.npy")[0]) == 7.0 and float(np.load(tmp_path / "a" / "grad_sumsq.npy")[0]) == 4.5
+
+
+@pytest.mark.parametrize("argv", [["--steps", "0"], ["--config", "3", "--dump-outputs", "x"]])
+def test_flags_that_cannot_be_honoured_are_refused(monkeypatch, argv):
+    import bench
+    monkeypatch.setattr(bench, "config3", lambda a: pytest.fail("reached the benchmark"))
+    monkeypatch.setattr(sys, "argv", ["bench.py"] + argv)
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
