@@ -539,14 +539,15 @@ int st5_vq_bwd(const float* logits, const float* gumbel, const float* dsel, int3
 /* ---- HuBERT NCE head (speech_encoder_postnet.py:56-76), fp32 (csrc/nce.hip) ----
  * st5_norm_rows: y[r] = x[r] / max(|x[r]|, 1e-8) (x in `dtype`, y fp32), inv[r] = 1 / max(|x[r]|, 1e-8); st5_norm_rows_bwd: its
  * gradient dx (`dtype`; accumulate != 0: dx += ...).  st5_canon_rows: canon[c] = smallest c' whose row equals row c exactly.
- * st5_nce_logits: logits[s] = [sim[s, t_s], sim[s, :]] / temp with -inf where canon[c] == canon[t_s]; st5_nce_logits_bwd: dsim. */
+ * st5_nce_logits: logits[s] = [sim[s, t_s], sim[s, :]] / temp with -inf where canon[c] == canon[t_s]; st5_nce_logits_bwd: dsim with row
+ * stride dsim_ld >= V, its columns V..dsim_ld-1 written as zero (a ld that is a multiple of 4 makes dsim a GEMM operand for any V). */
 int st5_norm_rows(const void* x, float* y, float* inv, int64_t rows, int32_t cols, int dtype, void* stream);
 int st5_norm_rows_bwd(const float* y, const float* inv, const float* dy, void* dx, int64_t rows, int32_t cols, int32_t accumulate, int dtype,
                       void* stream);
 int st5_canon_rows(const float* e, int32_t* canon, int32_t V, int32_t D, void* stream);
 int st5_nce_logits(const float* sim, const int32_t* target, const int32_t* canon, float* logits, int64_t S, int32_t V, float temp, void* stream);
-int st5_nce_logits_bwd(const float* dlogits, const int32_t* target, const int32_t* canon, float* dsim, int64_t S, int32_t V, float temp,
-                       void* stream);
+int st5_nce_logits_bwd(const float* dlogits, const int32_t* target, const int32_t* canon, float* dsim, int32_t dsim_ld, int64_t S, int32_t V,
+                       float temp, void* stream);
 /* A/B switch of the LayerNorm backward: upper bound of its block count (default 256). */
 int st5_layernorm_set_max_blocks(int n);
 /* ---- CTC prefix scoring for joint CTC / attention beam search (sequence_generator.py:273-418 calls espnet's

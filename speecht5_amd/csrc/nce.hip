@@ -77,18 +77,21 @@ __global__ __launch_bounds__(256) void nce_logits_kernel(const float* __restrict
   for (int c = threadIdx.x; c < V; c += 256) out[1 + c] = canon[c] == ct ? -INFINITY : row[c] * inv_temp;
 }
 
-// dsim [S, V] from dlogits [S, 1 + V]
+// dsim [S, ld] (columns V..ld-1 zero: the GEMM operand pad) from dlogits [S, 1 + V]
 __global__ __launch_bounds__(256) void nce_logits_bwd_kernel(const float* __restrict__ dlogits, const int* __restrict__ target,
-                                                             const int* __restrict__ canon, float* __restrict__ dsim, long long S, int V,
-                                                             float inv_temp) {
+                                                             const int* __restrict__ canon, float* __restrict__ dsim, int ld, long long S,
+                                                             int V, float inv_temp) {
   const long long s = blockIdx.x;
   const int t = target[s];
   const int ct = canon[t];
   const float* g = dlogits + s * (V + 1);
-  float* out = dsim + s * V;
-  for (int c = threadIdx.x; c < V; c += 256) {
-    float v = canon[c] == ct ? 0.f : g[1 + c] * inv_temp;
-    if (c == t) v += g[0] * inv_temp;
+  float* out = dsim + s * ld;
+  for (int c = threadIdx.x; c < ld; c += 256) {
+    float v = 0.f;
+    if (c < V) {
+      v = canon[c] == ct ? 0.f : g[1 + c] * inv_temp;
+      if (c == t) v += g[0] * inv_temp;
+    }
     out[c] = v;
   }
 }
@@ -134,12 +137,12 @@ extern "C" int st5_nce_logits(const float* sim, const int32_t* target, const int
   return ST5_OK;
 }
 
-extern "C" int st5_nce_logits_bwd(const float* dlogits, const int32_t* target, const int32_t* canon, float* dsim, int64_t S, int32_t V, float temp,
-                                  void* stream) {
-  if (!dlogits || !target || !canon || !dsim || S < 0 || V <= 0 || !(temp > 0.f)) return ST5_ERR_ARG;
+extern "C" int st5_nce_logits_bwd(const float* dlogits, const int32_t* target, const int32_t* canon, float* dsim, int32_t dsim_ld, int64_t S,
+                                  int32_t V, float temp, void* stream) {
+  if (!dlogits || !target || !canon || !dsim || S < 0 || V <= 0 || dsim_ld < V || !(temp > 0.f)) return ST5_ERR_ARG;
   if (S == 0) return ST5_OK;
-  hipLaunchKernelGGL(nce_logits_bwd_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, dlogits, target, canon, dsim, (long long)S, V,
-                     1.f / temp);
+  hipLaunchKernelGGL(nce_logits_bwd_kernel, dim3((unsigned)S), dim3(256), 0, (hipStream_t)stream, dlogits, target, canon, dsim, (int)dsim_ld,
+                     (long long)S, V, 1.f / temp);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }

@@ -2318,16 +2318,19 @@ class NCELogitsFunction(torch.autograd.Function):
         if S == 0:
             return dx, None, None, None, None, None
         dlogits = dlogits.contiguous().float()
-        dsim = torch.empty(S, V, dtype=torch.float32, device=dev)
-        hip.check(L.st5_nce_logits_bwd(dlogits.data_ptr(), tgt.data_ptr(), canon.data_ptr(), dsim.data_ptr(), S, V, temp, st), "st5_nce_logits_bwd")
+        # dsim's row stride padded to a multiple of 4: fp32 GEMM operands need ld % 4 == 0 (a km50 label set has V = 54)
+        ld = (V + 3) // 4 * 4
+        dsim = torch.empty(S, ld, dtype=torch.float32, device=dev)
+        hip.check(L.st5_nce_logits_bwd(dlogits.data_ptr(), tgt.data_ptr(), canon.data_ptr(), dsim.data_ptr(), ld, S, V, temp, st),
+                  "st5_nce_logits_bwd")
         if dx is not None:
             dxn = torch.empty(S, D, dtype=torch.float32, device=dev)
-            hip.gemm(hip.operand(dsim, V), hip.operand(en, D), hip.operand(dxn, D), S, D, V, hip.F32, flags=hip.B_KSTRIDED)
+            hip.gemm(hip.operand(dsim, ld), hip.operand(en, D), hip.operand(dxn, D), S, D, V, hip.F32, flags=hip.B_KSTRIDED)
             hip.check(L.st5_norm_rows_bwd(xn.data_ptr(), inv_x.data_ptr(), dxn.data_ptr(), dx.data_ptr(), S, D, 0, hip.dt(xdtype), st),
                       "st5_norm_rows_bwd")
         if emb_param.requires_grad:
             den = torch.empty(V, D, dtype=torch.float32, device=dev)
-            hip.gemm(hip.operand(dsim, V), hip.operand(xn, D), hip.operand(den, D), V, D, S, hip.F32,
+            hip.gemm(hip.operand(dsim, ld), hip.operand(xn, D), hip.operand(den, D), V, D, S, hip.F32,
                      flags=hip.A_KSTRIDED | hip.B_KSTRIDED | hip.OUT_F32)   # (OUT_F32: the split-K path, few output tiles / long K)
             g = grad_buffer(emb_param)[row0:row0 + V]
             hip.check(L.st5_norm_rows_bwd(en.data_ptr(), inv_e.data_ptr(), den.data_ptr(), g.data_ptr(), V, D, 1, hip.F32, st), "st5_norm_rows_bwd")

@@ -184,7 +184,7 @@ _SIGS = {
     "st5_norm_rows_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int, c_void_p]),
     "st5_canon_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "st5_nce_logits": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
-    "st5_nce_logits_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_float, c_void_p]),
+    "st5_nce_logits_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_float, c_void_p]),
     "st5_gather3": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int64, c_int64, c_int64, c_int64, c_int32, c_int, c_void_p]),
     "st5_zero_time_edges": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int, c_void_p]),
     "st5_layernorm_set_max_blocks": (c_int, [c_int]),
