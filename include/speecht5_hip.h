@@ -505,7 +505,8 @@ int st5_tacotron_loss_bwd(const float* after, const float* before, const float* 
  * fwd: nll [B], loss[0] = sum_b nll_b (an impossible alignment counts 0 with zero_infinity); ws >= st5_ctc_loss_ws_bytes
  * keeps the alpha rows.  bwd: grad [T, B, V] = grad_out[0] * (exp(lprobs) - posterior) for t < input_lengths[b], else 0 --
  * the form torch's ctc_loss backward returns (the gradient w.r.t. the logits in front of the log-softmax; pushing it through
- * the log-softmax backward leaves it unchanged). */
+ * the log-softmax backward leaves it unchanged).  Both refuse (ST5_ERR_ARG, nothing launched) the same pairs: those with
+ * (8 max_target_len + V + 12) * 4 bytes > 60 KiB of LDS, i.e. max_target_len > 1908 at V = 83. */
 int64_t st5_ctc_loss_ws_bytes(int32_t T, int32_t B, int32_t max_target_len);
 int st5_ctc_loss_fwd(const float* lprobs, const int64_t* targets, const int64_t* target_offsets, const int64_t* input_lengths,
                      const int64_t* target_lengths, int32_t T, int32_t B, int32_t V, int32_t max_target_len, int32_t blank,

@@ -37,7 +37,7 @@ struct CtcDims {
   int T, B, V, maxL, blank;
 };
 
-// LDS layout (ints / floats): tg[maxL] | row0[S] | row1[S] | (backward only) ab[S] perm[maxL] start[V + 1] | red[CTC_THREADS]
+// LDS layout (ints / floats): tg[maxL] | row0[S] | row1[S] | (backward only) ab[S] perm[maxL] start[V + 1] red[8]
 __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_kernel(const float* __restrict__ lp, const long long* __restrict__ targets,
                                                                 const long long* __restrict__ offsets,
                                                                 const long long* __restrict__ in_len, const long long* __restrict__ tg_len,
@@ -46,7 +46,12 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_kernel(const float* __r
   const int b = blockIdx.x;
   const int Smax = 2 * d.maxL + 1;
   int* tg = smem;
-  float* row[2] = {reinterpret_cast<float*>(smem + d.maxL), reinterpret_cast<float*>(smem + d.maxL + Smax)};
+  // The state rows are chosen by selecting between two LDS pointers, not by indexing a pointer array.  Through the array the
+  // compiler lost the address space and emitted FLAT accesses.  For prev[s] the base address was the row's start - 4 (the
+  // +4 went into the instruction offset); with max_target_len = 0 the row starts at LDS offset 0, so that base fell below
+  // the LDS aperture and the access faulted.  Selected pointers stay LDS pointers (ds_* accesses).
+  float* const row0 = reinterpret_cast<float*>(smem + d.maxL);
+  float* const row1 = row0 + Smax;
   long long Lq = tg_len[b];
   const int L = (int)(Lq < 0 ? 0 : (Lq > d.maxL ? d.maxL : Lq));
   const int S = 2 * L + 1;
@@ -65,13 +70,13 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_kernel(const float* __r
     float a = -INFINITY;
     if (s == 0) a = lpb[d.blank];
     else if (s == 1) a = lpb[tg[0]];
-    row[0][s] = a;
+    row0[s] = a;
     ab[s] = a;
   }
   __syncthreads();
   for (int t = 1; t < Tb; ++t) {
-    const float* prev = row[(t - 1) & 1];
-    float* cur = row[t & 1];
+    const float* prev = (t & 1) ? row0 : row1;
+    float* cur = (t & 1) ? row1 : row0;
     const float* lpt = lpb + t * tstride;
     for (int s = threadIdx.x; s < S; s += CTC_THREADS) {
       const int c = prime(tg, s, d.blank);
@@ -85,7 +90,7 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_alpha_kernel(const float* __r
     __syncthreads();
   }
   if (threadIdx.x == 0) {
-    const float* last = row[(Tb - 1) & 1];
+    const float* last = ((Tb - 1) & 1) ? row1 : row0;
     const float l1 = last[S - 1], l2 = S > 1 ? last[S - 2] : -INFINITY;
     float m = fmaxf(l1, l2);
     if (m == -INFINITY) m = 0.f;
@@ -114,7 +119,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_grad_kernel(const float* __re
   const int b = blockIdx.x;
   const int Smax = 2 * d.maxL + 1;
   int* tg = smem;
-  float* row[2] = {reinterpret_cast<float*>(smem + d.maxL), reinterpret_cast<float*>(smem + d.maxL + Smax)};
+  float* const row0 = reinterpret_cast<float*>(smem + d.maxL);   // (selected, not indexed: see ctc_alpha_kernel)
+  float* const row1 = row0 + Smax;
   float* abs_ = reinterpret_cast<float*>(smem + d.maxL + 2 * Smax);
   int* perm = smem + d.maxL + 3 * Smax;
   int* start = perm + d.maxL;
@@ -157,8 +163,8 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_grad_kernel(const float* __re
   __syncthreads();
   const float* al = alpha + (long long)b * d.T * Smax;
   for (int t = Tb - 1; t >= 0; --t) {
-    float* cur = row[t & 1];
-    const float* nxt = row[(t + 1) & 1];
+    float* cur = (t & 1) ? row1 : row0;
+    const float* nxt = (t & 1) ? row0 : row1;
     const float* lpt = lpb + t * tstride;
     float mx = -INFINITY;
     for (int s = threadIdx.x; s < S; s += CTC_THREADS) {
@@ -272,6 +278,11 @@ size_t ctc_lds_bytes(int maxL, int V, bool backward) {
   return words * 4;
 }
 
+// Both passes accept exactly the (max_target_len, V) pairs whose BACKWARD layout fits, (8 maxL + V + 12) * 4 <= 60 KiB: up to
+// 1908 labels at V = 83.  The forward alone would fit ~3000, but a step the backward must refuse is refused by its forward.
+constexpr size_t CTC_LDS_CAP = 60 * 1024;
+bool ctc_lds_fits(int maxL, int V) { return ctc_lds_bytes(maxL, V, true) <= CTC_LDS_CAP; }
+
 }  // namespace
 
 extern "C" int64_t st5_ctc_loss_ws_bytes(int32_t T, int32_t B, int32_t max_target_len) {
@@ -285,8 +296,8 @@ extern "C" int st5_ctc_loss_fwd(const float* lprobs, const int64_t* targets, con
   if (!lprobs || !target_offsets || !input_lengths || !target_lengths || !nll || !loss || !ws) return ST5_ERR_ARG;
   if (T <= 0 || B <= 0 || V <= 0 || max_target_len < 0 || blank < 0 || blank >= V) return ST5_ERR_ARG;
   if (max_target_len > 0 && !targets) return ST5_ERR_ARG;
+  if (!ctc_lds_fits(max_target_len, V)) return ST5_ERR_ARG;   // (the backward's bound: up to 1908 labels at V = 83)
   const size_t lds = ctc_lds_bytes(max_target_len, V, false);
-  if (lds > 60 * 1024) return ST5_ERR_ARG;   // (targets of up to ~3000 labels)
   hipStream_t s = (hipStream_t)stream;
   const CtcDims d{T, B, V, max_target_len, blank};
   hipLaunchKernelGGL(ctc_alpha_kernel, dim3((unsigned)B), dim3(CTC_THREADS), lds, s, lprobs, reinterpret_cast<const long long*>(targets),
@@ -304,8 +315,8 @@ extern "C" int st5_ctc_loss_bwd(const float* lprobs, const int64_t* targets, con
   if (!lprobs || !target_offsets || !input_lengths || !target_lengths || !nll || !grad_out || !ws || !grad) return ST5_ERR_ARG;
   if (T <= 0 || B <= 0 || V <= 0 || max_target_len < 0 || blank < 0 || blank >= V) return ST5_ERR_ARG;
   if (max_target_len > 0 && !targets) return ST5_ERR_ARG;
+  if (!ctc_lds_fits(max_target_len, V)) return ST5_ERR_ARG;
   const size_t lds = ctc_lds_bytes(max_target_len, V, true);
-  if (lds > 60 * 1024) return ST5_ERR_ARG;
   const CtcDims d{T, B, V, max_target_len, blank};
   hipLaunchKernelGGL(ctc_grad_kernel, dim3((unsigned)B), dim3(CTC_THREADS), lds, (hipStream_t)stream, lprobs,
                      reinterpret_cast<const long long*>(targets), reinterpret_cast<const long long*>(target_offsets),

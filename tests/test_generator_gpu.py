@@ -5,6 +5,7 @@ import numpy as np
 import pytest
 import torch
 
+from tests.ctc_reference import prefix_initial, prefix_score
 from tests.util import Task, build_tiny, load_golden, to_dev
 
 pytestmark = pytest.mark.gpu
@@ -51,35 +52,13 @@ def test_ctc_prefix_kernel_equals_numpy_restatement(cuda):
     T, V, blank, eos = 37, 19, 18, 2
     x = torch.log_softmax(torch.tensor(rng.randn(T, V), dtype=torch.float32), -1)
     xn = x.numpy()
-    LOGZERO = np.float32(-1e10)
 
     def np_initial():
-        r = np.full((T, 2), LOGZERO, dtype=np.float32)
-        r[0, 1] = xn[0, blank]
-        for t in range(1, T):
-            r[t, 1] = r[t - 1, 1] + xn[t, blank]
-        return r
+        return prefix_initial(xn, blank, np.float32)
 
     def np_score(y, cs, r_prev):
-        out_len = len(y) - 1
-        r = np.full((T, 2, len(cs)), LOGZERO, dtype=np.float32)
-        xs = xn[:, cs]
-        if out_len == 0:
-            r[0, 0] = xs[0]
-        r_sum = np.logaddexp(r_prev[:, 0], r_prev[:, 1])
-        log_phi = np.stack([r_sum if (out_len == 0 or c != y[-1]) else r_prev[:, 1] for c in cs], 1)
-        start = max(out_len, 1)
-        log_psi = r[start - 1, 0].copy()
-        for t in range(start, T):
-            r[t, 0] = np.logaddexp(r[t - 1, 0], log_phi[t - 1]) + xs[t]
-            r[t, 1] = np.logaddexp(r[t - 1, 0], r[t - 1, 1]) + xn[t, blank]
-            log_psi = np.logaddexp(log_psi, log_phi[t - 1] + xs[t])
-        for i, c in enumerate(cs):
-            if c == eos:
-                log_psi[i] = r_sum[-1]
-            if c == blank:
-                log_psi[i] = LOGZERO
-        return log_psi, np.moveaxis(r, 2, 0)
+        psi, r = prefix_score(xn, [y[-1]], len(y) - 1, cs[None], r_prev[None], blank, eos, np.float32)
+        return psi[0], r[0]
 
     sc = CTCPrefixScorer(x.to(cuda), blank, eos)
     r0 = sc.initial_state()

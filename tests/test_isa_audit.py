@@ -41,6 +41,24 @@ def test_the_audit_sees_the_round4_form_of_the_dkv_kernel():
     assert any("bwd_dkv_kernel" in n for n in names), names
 
 
+def test_ctc_loss_kernels_keep_lds_rows_out_of_flat_accesses():
+    """csrc/ctc_loss.hip reaches its LDS state rows with ds_* instructions only.  Picked from a pointer array they became FLAT
+    accesses, and the base address of prev[s] (the row's start - 4, with +4 in the instruction offset) left the LDS aperture
+    when the row started at LDS offset 0 (max_target_len = 0): a memory fault on the GPU, seen by
+    tests/test_ctc_gpu.py::test_ctc_loss_recipe_shapes[T499-b82-empty]."""
+    import re
+    m = _audit_module()
+    f = _compile(m, os.path.join(ROOT, "speecht5_amd", "csrc", "ctc_loss.hip"))
+    flat, name = [], None
+    for line in open(f, errors="replace"):
+        k = re.match(r"^([A-Za-z_][\w$.]*):", line)
+        if k and not k.group(1).startswith(".L"):
+            name = k.group(1)
+        elif name and "ctc_" in name and re.match(r"^\s*flat_", line):
+            flat.append((name, line.strip()))
+    assert not flat, flat
+
+
 def test_gelu_poly_error_bound():
     """common.h gelu_poly (the transcendental-free GELU value of the bf16 epilogues): its fp32 instruction sequence restated in numpy
     with the constants parsed from the source, against the exact erf-GELU: |Phi error| <= 1.6e-5, |gelu error| <= 2.5e-5 on [-4, 4]
