@@ -561,6 +561,27 @@ int st5_layernorm_set_max_blocks(int n);
 int st5_ctc_initial_state(const float* x, int32_t T, int32_t V, int32_t blank, float* r, void* stream);
 int st5_ctc_prefix_score(const float* x, int32_t T, int32_t V, int32_t blank, int32_t eos, const float* r_prev, const int64_t* last,
                          int32_t out_len, const int64_t* cs, int32_t nh, int32_t nc, float* log_psi, float* r_new, void* stream);
+/* ---- shallow-fusion LM decoding (csrc/lm_decode.hip): replaces the full-prefix LM call of ASR beam search,
+ * SpeechT5/speecht5/sequence_generator.py:420-425 (lm_model(tokens[:, :step + 1]) + log_softmax + lprobs[:, :V_lm] += w * probs) ----
+ * Slot cache of one layer: kv [rows_cap][Tmax][2C] (compute dtype, C = H * head_dim): slot (r, j) = [k | v] of hypothesis row r at
+ * position j, written once.  Ancestry: anc [rows][anc_ld] int32, row r reads position j from slot (anc[r][j], j).
+ * st5_lm_decode_attn (multihead_attention.py self-attention with incremental state, one query per row):
+ * ctx[r][h*hd + i] = softmax_j(q[r] . k_j * hd^-0.5) v_j over positions j < t of head h, fp32 accumulation.  head_dim 64 or 80 and
+ * H <= 64, else ST5_ERR_ARG.  q / kv 16-byte aligned, q_ld a multiple of 4 (fp32) / 8 (bf16), else ST5_ERR_ALIGN.  ws: fp32
+ * workspace of st5_lm_decode_attn_ws_bytes(rows, t, H, head_dim) bytes (16-byte aligned; NULL when that is 0).  An anc entry
+ * outside [0, rows_cap) gives NaN in that row's output. */
+int64_t st5_lm_decode_attn_ws_bytes(int32_t rows, int32_t t, int32_t H, int32_t head_dim);
+int st5_lm_decode_attn(const void* q, int64_t q_ld, const void* kv, int32_t rows_cap, int32_t Tmax, const int32_t* anc, int64_t anc_ld,
+                       int32_t rows, int32_t t, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld, float* ws, int dtype, void* stream);
+/* st5_lm_reorder (the LM's share of reorder_incremental_state, sequence_generator.py:218-224): anc_new[r][j] = anc[order[r]][j] for
+ * j < t and = r for t <= j < Tmax, r < rows_new; order int64 indexes the rows_old rows of anc (an entry outside gives -1 below t).
+ * anc_new must not alias anc. */
+int st5_lm_reorder(const int32_t* anc, int64_t anc_ld, const int64_t* order, int32_t rows_old, int32_t rows_new, int32_t t, int32_t Tmax,
+                   int32_t* anc_new, int64_t new_ld, void* stream);
+/* st5_lm_fuse_logprobs (sequence_generator.py:421-425): lprobs[r][c] += lm_weight * log_softmax(logits[r][:V_lm])[c] for c < V_lm;
+ * lprobs fp32 [rows][lp_ld], logits in `dtype` [rows][lg_ld]; the log-softmax in fp32.  Columns >= V_lm are not touched. */
+int st5_lm_fuse_logprobs(float* lprobs, int64_t lp_ld, const void* logits, int64_t lg_ld, int32_t rows, int32_t V_lm, float lm_weight,
+                         int dtype, void* stream);
 /* ... over TWO gradient buffers: the step uses g + g2 (g2 may be NULL); zero_grads != 0 leaves both buffers zeroed.  With
  * st5_sumsq_pair (sum of squares of x + y) for the clipping norm this replaces "g += g2", two fills and the plain step. */
 int st5_adam_step_pair(float* p, float* g, float* g2, int32_t zero_grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

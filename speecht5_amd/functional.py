@@ -2970,3 +2970,57 @@ def postnet(before, blocks, training, dropout_p):
         bufs.append((bn.running_mean, bn.running_var, bn.num_batches_tracked))
         cfg.append((float(bn.eps), bn.momentum))
     return PostnetFunction.apply(before, (bool(training), float(dropout_p), cfg), bufs, *params)
+
+
+# -------------------------------------------------------------------------------------------------
+# Shallow-fusion LM decoding (csrc/lm_decode.hip): slot-cache attention over an ancestry table, the table's beam reorder, and the
+# fused LM score of beam search (sequence_generator.py:420-425).  Inference only, no autograd.
+# -------------------------------------------------------------------------------------------------
+def linear_into(x, weights, biases, out, N):
+    """out (a hip.operand) = x . stack(weights)^T + stack(biases), N output columns, in the compute dtype of x: a projection whose
+    rows land at a caller-chosen stride (the LM's K / V projection writes each row straight into its slot of the cache)."""
+    x = x.contiguous()
+    M, K = x.shape
+    hip.gemm(hip.operand(x, K), hip.operand(fused_weight(weights, x.dtype), K), out, M, N, K, _dt(x.dtype), bias=fused_bias(biases))
+
+
+def lm_decode_attn_ws(rows, t, H, hd, device):
+    """fp32 workspace of st5_lm_decode_attn for `rows` rows and up to t positions (None when that launch needs none)."""
+    n = int(hip.lib().st5_lm_decode_attn_ws_bytes(rows, t, H, hd))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device) if n else None
+
+
+def lm_decode_attn(q, kv, anc, t, H, hd, ws=None):
+    """q [rows, >= C] (compute dtype, row stride q.stride(0)); kv [rows_cap, Tmax, 2C] slot cache; anc [rows, Tmax'] int32 (Tmax' >= t).
+    Returns ctx [rows, C] = attention of each row's query over positions 0..t-1 of its ancestry."""
+    rows = q.shape[0]
+    rows_cap, Tmax = kv.shape[0], kv.shape[1]
+    C = H * hd
+    assert kv.shape[2] == 2 * C and kv.is_contiguous() and anc.dtype == torch.int32 and anc.stride(1) == 1 and q.stride(1) == 1
+    assert kv.dtype == q.dtype
+    if ws is None or ws.numel() * 4 < hip.lib().st5_lm_decode_attn_ws_bytes(rows, t, H, hd):
+        ws = lm_decode_attn_ws(rows, t, H, hd, q.device)
+    ctx = torch.empty(rows, C, dtype=q.dtype, device=q.device)
+    hip.check(hip.lib().st5_lm_decode_attn(q.data_ptr(), q.stride(0), kv.data_ptr(), rows_cap, Tmax, anc.data_ptr(), anc.stride(0), rows,
+                                           int(t), H, hd, ctx.data_ptr(), C, hip.ptr(ws), _dt(q), hip.stream()), "st5_lm_decode_attn")
+    return ctx
+
+
+def lm_reorder(anc, order, t, out):
+    """out[r, :t] = anc[order[r], :t], out[r, t:] = r for r < len(order) (out must not alias anc); returns out[:len(order)]."""
+    order = order.to(torch.int64).contiguous()
+    n = order.numel()
+    assert out.shape[0] >= n and out.shape[1] == anc.shape[1] and anc.stride(1) == 1 and out.stride(1) == 1
+    hip.check(hip.lib().st5_lm_reorder(anc.data_ptr(), anc.stride(0), order.data_ptr(), anc.shape[0], n, int(t), anc.shape[1],
+                                       out.data_ptr(), out.stride(0), hip.stream()), "st5_lm_reorder")
+    return out[:n]
+
+
+def lm_fuse_logprobs(lprobs, logits, lm_weight):
+    """In place: lprobs[:, :V_lm] += lm_weight * log_softmax(logits) (fp32 lprobs [rows, >= V_lm], logits [rows, V_lm] in the compute
+    dtype or fp32).  -inf entries of lprobs stay -inf; lm_weight 0 leaves lprobs unchanged."""
+    assert lprobs.dtype == torch.float32 and lprobs.stride(1) == 1 and logits.stride(1) == 1 and lprobs.shape[0] == logits.shape[0]
+    rows, V = logits.shape
+    hip.check(hip.lib().st5_lm_fuse_logprobs(lprobs.data_ptr(), lprobs.stride(0), logits.data_ptr(), logits.stride(0), rows, V,
+                                             float(lm_weight), _dt(logits), hip.stream()), "st5_lm_fuse_logprobs")
+    return lprobs

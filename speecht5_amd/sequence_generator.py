@@ -104,6 +104,17 @@ class CTCPrefixScorer:
         return log_psi, r_new
 
 
+def _is_hip_lm(lm):
+    from .transformer_lm import TransformerLanguageModel
+    return isinstance(lm, TransformerLanguageModel)
+
+
+def hip_fuse_lm(lprobs, logits, lm_weight):
+    """lprobs[:, :V_lm] += lm_weight * log_softmax(logits) in place (sequence_generator.py:420-425, csrc/lm_decode.hip)."""
+    from .functional import lm_fuse_logprobs
+    return lm_fuse_logprobs(lprobs, logits, lm_weight)
+
+
 class SequenceGenerator(nn.Module):
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
@@ -186,6 +197,10 @@ class SequenceGenerator(nn.Module):
         assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
 
         encoder_outs = self.model.forward_encoder(net_input)
+        # a HIP transformer_lm decodes incrementally over a slot cache (transformer_lm.py); any other LM runs the full prefix
+        lm_state = None
+        if self.lm_model is not None and _is_hip_lm(self.lm_model):
+            lm_state = self.lm_model.init_decode(bsz * beam, max_len + 2)
 
         # joint CTC scoring state (:273-284): posterior of sentence 0; one prefix state + prefix score per live hypothesis row
         ctc = None
@@ -221,6 +236,8 @@ class SequenceGenerator(nn.Module):
                     reorder_state.view(-1, beam).add_(corr.unsqueeze(-1) * beam)
                     original_batch_idxs = original_batch_idxs[batch_idxs]
                 self.model.reorder_incremental_state(incremental_states, reorder_state)
+                if lm_state is not None:
+                    self.lm_model.reorder(lm_state, reorder_state)
                 encoder_outs = self.model.reorder_encoder_out(encoder_outs, reorder_state)
 
             lprobs, avg_attn_scores = self.model.forward_decoder(tokens[:, : step + 1], encoder_outs, incremental_states,
@@ -239,7 +256,9 @@ class SequenceGenerator(nn.Module):
                 slot_of = torch.full_like(lprobs, -1, dtype=torch.long).scatter_(
                     1, cs, torch.arange(ctc_beam, device=dev).expand_as(cs))
 
-            if self.lm_model is not None:
+            if lm_state is not None:
+                hip_fuse_lm(lprobs, self.lm_model.decode_step(tokens[:, step], lm_state), self.lm_weight)
+            elif self.lm_model is not None:
                 lm_out = self.lm_model(tokens[:, : step + 1])
                 probs = self.lm_model.get_normalized_probs(lm_out, log_probs=True, sample=None)[:, -1, :] * self.lm_weight
                 lprobs[:, : probs.size(1)] += probs

@@ -246,6 +246,14 @@ class SpeechT5Task(LegacyFairseqTask):
         from .sequence_generator import SequenceGenerator
         kw = dict(ctc_weight=getattr(self.args, "ctc_weight", 0.0))
         kw.update(extra_gen_cls_kwargs or {})
+        lm = kw.get("lm_model")
+        if lm is not None:
+            # --lm-path hands over a fairseq transformer_lm: run it as the HIP model (transformer_lm.py), on the model's device
+            from .transformer_lm import convert_fairseq_lm, is_fairseq_lm
+            if is_fairseq_lm(lm):
+                ref = next(iter(models[0].parameters()), None)
+                conv = convert_fairseq_lm(lm, pad=self.target_dictionary.pad())
+                kw["lm_model"] = conv.to(device=ref.device, dtype=ref.dtype) if ref is not None else conv
         cls_ = seq_gen_cls or SequenceGenerator
         return cls_(models, self.target_dictionary, beam_size=getattr(args, "beam", 5), max_len_a=getattr(args, "max_len_a", 0),
                     max_len_b=getattr(args, "max_len_b", 200), min_len=getattr(args, "min_len", 1),
