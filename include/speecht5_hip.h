@@ -582,6 +582,27 @@ int st5_lm_reorder(const int32_t* anc, int64_t anc_ld, const int64_t* order, int
  * lprobs fp32 [rows][lp_ld], logits in `dtype` [rows][lg_ld]; the log-softmax in fp32.  Columns >= V_lm are not touched. */
 int st5_lm_fuse_logprobs(float* lprobs, int64_t lp_ld, const void* logits, int64_t lg_ld, int32_t rows, int32_t V_lm, float lm_weight,
                          int dtype, void* stream);
+/* ---- Speaker-identification head (s2c, speaker_decoder_postnet.py; csrc/speaker_head.hip) ----
+ * st5_angular_margin_fwd: out[b][v] = s * m(cos[b][v]) for v < V on fp32 cosine logits, with the margin only on column target[b]
+ * (int32; -1 = no margin in that row, which is then only scaled).  mode ST5_MARGIN_AM (AngularMargin): s * (cos - m) on the target.
+ * ST5_MARGIN_AAM / ST5_MARGIN_AAM_EASY (AdditiveAngularMargin): phi = cos*cos_m - sqrt(clamp(1 - cos^2, 0, 1))*sin_m on the target,
+ * used where cos > th (else cos - mm), or with easy margin where cos > 0 (else cos); th = cos(pi - m), mm = sin(pi - m) * m.
+ * out may be cos (in place).  st5_angular_margin_bwd: dcos = dy * d out / d cos, exactly; columns V..dcos_ld-1 of dcos are written
+ * as zero.  Where the clamp is active (|cos| >= 1, the sine term is 0) its derivative is taken as 0: the target column's gradient
+ * there is s * cos_m on the phi branch -- finite, where the reference's autograd gives inf or NaN.  B <= 65535. */
+#define ST5_MARGIN_AM 0
+#define ST5_MARGIN_AAM 1
+#define ST5_MARGIN_AAM_EASY 2
+int st5_angular_margin_fwd(const float* cos, int64_t ld, const int32_t* target, float* out, int64_t out_ld, int32_t B, int32_t V,
+                           int32_t mode, float margin, float scale, void* stream);
+int st5_angular_margin_bwd(const float* cos, int64_t ld, const int32_t* target, const float* dy, int64_t dy_ld, float* dcos,
+                           int64_t dcos_ld, int32_t B, int32_t V, int32_t mode, float margin, float scale, void* stream);
+/* st5_time_mean_fwd: y[b][c] = (1/T) sum_t x[t*t_stride + b*b_stride + c] over ALL T frames, padded ones included
+ * (encoder_out.mean(1), speecht5.py:837-838); x in `dtype`, y fp32 [B, C]; compensated fp32 sums.  st5_time_mean_bwd: dx[t][b][c] =
+ * dy[b][c] / T for every frame, dx time-major [T, B, C] contiguous in `dtype` (accumulate != 0: added to dx).  B <= 65535. */
+int st5_time_mean_fwd(const void* x, int64_t t_stride, int64_t b_stride, int32_t T, int32_t B, int32_t C, float* y, int dtype,
+                      void* stream);
+int st5_time_mean_bwd(const float* dy, int32_t T, int32_t B, int32_t C, int32_t accumulate, void* dx, int dtype, void* stream);
 /* ... over TWO gradient buffers: the step uses g + g2 (g2 may be NULL); zero_grads != 0 leaves both buffers zeroed.  With
  * st5_sumsq_pair (sum of squares of x + y) for the clipping norm this replaces "g += g2", two fills and the plain step. */
 int st5_adam_step_pair(float* p, float* g, float* g2, int32_t zero_grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

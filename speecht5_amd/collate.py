@@ -225,6 +225,39 @@ class SpeechToTextCollater:
     __call__ = collater
 
 
+class SpeechToClassCollater:
+    """SpeechToClassDataset.collater (data/speech_to_class_dataset.py:138-198) + collater_audio (:200-214) + collater_label (:222-231).
+    samples: [{"id", "source": fp32 [S] (device), "label": int64 [n] (device, the encoded speaker; n = 1) or None}].  The random crop of
+    the reference happens in the dataset's __getitem__ (host numpy), before this.  prev_output_tokens = [[</s>]] per item (the
+    move_eos_to_beginning collate of [-1]); target [B, max n] right-padded, ntokens = B."""
+
+    def __init__(self, device, *, pad_idx=1, eos_idx=2):
+        self.device, self.pad_idx, self.eos_idx = device, pad_idx, eos_idx
+
+    def collater(self, samples):
+        samples = [s for s in samples if s["source"] is not None]
+        if not samples:
+            return {}
+        dev, B = self.device, len(samples)
+        audios = [s["source"].contiguous() for s in samples]
+        sizes = [int(a.shape[0]) for a in audios]
+        S = max(sizes)
+        source = _ragged(audios, [0] * B, sizes, B, S, 1, 1, 0, torch.float32, 0.0, dev)
+        padding_mask = _tail(sizes, B, S, False, dev)
+        target = target_lengths = None
+        if samples[0]["label"] is not None:
+            labs = [s["label"].reshape(-1).long().contiguous() for s in samples]
+            n = [int(t.shape[0]) for t in labs]
+            target = _pad_tokens(labs, n, B, max(n), self.pad_idx, dev)
+            target_lengths = _lengths(n, dev)
+        prev = torch.full((B, 1), self.eos_idx, dtype=torch.long).to(dev, non_blocking=True)
+        net_input = {"source": source, "padding_mask": padding_mask, "prev_output_tokens": prev, "task_name": "s2c"}
+        return {"id": torch.LongTensor([s["id"] for s in samples]), "net_input": net_input, "target": target,
+                "target_lengths": target_lengths, "task_name": "s2c", "ntokens": B}
+
+    __call__ = collater
+
+
 class TextPretrainCollater:
     """collate() of data/text_dataset.py:18-99 (TextPretrainDataset.collater :435-444): source / target right-padded, the batch sorted by
     descending SOURCE length (the reference's own torch sort on the host lengths: the tie order is part of the batch), the decoder

@@ -312,6 +312,7 @@ class SpeechtoTextLoss(nn.Module):
         self.sentence_avg = sentence_avg
         self.eps = label_smoothing
         self.zero_infinity = getattr(cfg, "zero_infinity", True)
+        self.report_accuracy = report_accuracy
         self.sync_logging = sync_logging
 
     def forward(self, model, sample, reduce=True):
@@ -341,7 +342,23 @@ class SpeechtoTextLoss(nn.Module):
         log = {"loss": _item(loss, s), "ce_loss": _item(loss_ce, s) if loss_ce is not None else 0,
                "ctc_loss": _item(loss_ctc, s) if loss_ctc is not None else 0, "nll_loss": _item(nll, s) if nll is not None else 0,
                "ntokens": ntokens, "nsentences": sample["target"].size(0), "sample_size": sample_size}
+        if self.ce_weight > 0 and self.report_accuracy:
+            n_correct, total = self.compute_accuracy(model, net_output_decoder, sample)
+            log["n_correct"] = _item(n_correct, s)
+            log["total"] = _item(total, s)
         return loss, sample_size, log
+
+    def compute_accuracy(self, model, net_output, sample):
+        """speech_to_text_loss.py:363-370: argmax over the classes of every non-pad target position, counted on the device (int64
+        scalars).  The argmax of the logits is the argmax of their log-softmax."""
+        logits = net_output[0]
+        with torch.no_grad():
+            target = sample["target"].reshape(-1)
+            pred = logits.reshape(-1, logits.size(-1)).argmax(-1)
+            mask = target.ne(self.padding_idx)
+            n_correct = (pred.eq(target) & mask).sum()
+            total = mask.sum()
+        return n_correct, total
 
     def compute_loss_ctc(self, model, net_output, sample):
         lprobs = model.get_normalized_probs_for_ctc(net_output, log_probs=True).contiguous()

@@ -1611,6 +1611,9 @@ def layer_norm(x, weight, bias, eps=1e-5, gate=None, q8=False, relay=None):
 # -------------------------------------------------------------------------------------------------
 # Attention core (scores, rel-pos bias, masks, softmax, dropout, P.V) on projected q / k / v buffers
 # -------------------------------------------------------------------------------------------------
+UNFUSED_MAX_KEYS = 4096   # csrc/softmax.hip: MAXCH * 512
+
+
 def _attn_fwd(q, k, v, B, H, T, S, hd, pe, maxrel, kpm, causal, p_drop, seed):
     """q/k/v: (tensor, ld, col_off) of projected activations, rows batch-major.  Returns ctx [B*T, H*hd],
     probs [B*H, T, lds], probs_drop (or None)."""
@@ -1621,6 +1624,9 @@ def _attn_fwd(q, k, v, B, H, T, S, hd, pe, maxrel, kpm, causal, p_drop, seed):
     dev = qt.device
     d = H * hd
     lds = _ceil8(S)
+    if lds > UNFUSED_MAX_KEYS:
+        raise ValueError(f"the unfused attention path (fp32, or attention probabilities requested) takes at most {UNFUSED_MAX_KEYS} keys "
+                         f"(st5_softmax_fwd), got {S}: run inputs this long in bf16, where the flash-attention kernels take them")
     alpha = hd ** -0.5
     BH = B * H
     scores = torch.empty(BH, T, lds, dtype=dtype, device=dev)
@@ -3024,3 +3030,171 @@ def lm_fuse_logprobs(lprobs, logits, lm_weight):
     hip.check(hip.lib().st5_lm_fuse_logprobs(lprobs.data_ptr(), lprobs.stride(0), logits.data_ptr(), logits.stride(0), rows, V,
                                              float(lm_weight), _dt(logits), hip.stream()), "st5_lm_fuse_logprobs")
     return lprobs
+
+
+# -------------------------------------------------------------------------------------------------
+# Speaker-identification head (s2c, speaker_decoder_postnet.py): BatchNorm1d over [B, C] rows (st5_batchnorm_act_*), cosine logits
+# F.linear(F.normalize(x), F.normalize(W)) (st5_norm_rows + st5_gemm) with the AM / AAM margin (csrc/speaker_head.hip), and the time
+# mean of --sid-pooling-layer encoder.  The head runs in fp32 whatever the compute dtype: it is B rows wide.
+# -------------------------------------------------------------------------------------------------
+MARGIN_AM, MARGIN_AAM, MARGIN_AAM_EASY = 0, 1, 2
+
+
+class RowBatchNormFunction(torch.autograd.Function):
+    """torch.nn.BatchNorm1d on x fp32 [B, C] (C % 4 == 0): batch statistics and the running-statistics update (momentum blend,
+    unbiased variance) when training, running statistics otherwise.  y fp32 [B, C]."""
+
+    @staticmethod
+    def forward(ctx, x, gamma, beta, bufs, training, momentum, eps):
+        rm, rv, nbt = bufs
+        L = hip.lib()
+        x = x.contiguous()
+        B, C = x.shape
+        assert x.dtype == torch.float32 and C % 4 == 0, (x.dtype, C)
+        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        stats = torch.empty(2 * C, dtype=torch.float32, device=x.device)
+        ws = hip.workspace(L.st5_batchnorm_ws_bytes(C), x.device)
+        hip.check(L.st5_batchnorm_act_fwd(x.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hip.ptr(rm), hip.ptr(rv), hip.ptr(nbt),
+                                          momentum, eps, 1 if training else 0, ACT_NONE, 0.0, 0, 0, y.data_ptr(), 1, stats.data_ptr(),
+                                          ws.data_ptr(), B, C, 0, 0, 0, 0, hip.F32, hip.stream()), "st5_batchnorm_act_fwd")
+        ctx.save_for_backward(x, stats)
+        ctx.meta = (gamma, beta, training)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        x, stats = ctx.saved_tensors
+        gamma, beta, training = ctx.meta
+        L = hip.lib()
+        B, C = x.shape
+        dy = dy.contiguous().float()
+        dx = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        ws = hip.workspace(L.st5_batchnorm_ws_bytes(C), x.device)
+        gg = grad_buffer(gamma) if gamma.requires_grad else None
+        gb = grad_buffer(beta) if beta.requires_grad else None
+        hip.check(L.st5_batchnorm_act_bwd(x.data_ptr(), dy.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hip.ptr(gg),
+                                          hip.ptr(gb), 1 if training else 0, ACT_NONE, 0.0, 0, dx.data_ptr(), ws.data_ptr(), B, C, 0, 0, 0, 0,
+                                          hip.F32, hip.stream()), "st5_batchnorm_act_bwd")
+        for q in (gamma, beta):
+            if q.requires_grad:
+                _grad_done(q)
+        return dx, None, None, None, None, None, None
+
+
+def row_batch_norm(x, bn):
+    """bn: a torch.nn.BatchNorm1d (affine, running statistics tracked) applied to x [B, C] the way its forward would be."""
+    training = bn.training
+    if training and x.shape[0] == 1:   # the check of torch.nn.functional.batch_norm (_verify_batch_size)
+        raise ValueError(f"Expected more than 1 value per channel when training, got input size {torch.Size(x.shape)}")
+    if training and bn.momentum is None:
+        raise NotImplementedError("BatchNorm1d with momentum=None (cumulative average) is not used by the speaker head")
+    return RowBatchNormFunction.apply(as_float(x), bn.weight, bn.bias, (bn.running_mean, bn.running_var, bn.num_batches_tracked),
+                                      bool(training), float(bn.momentum if bn.momentum is not None else 0.0), float(bn.eps))
+
+
+class CosineLogitsFunction(torch.autograd.Function):
+    """logits fp32 [B, V] (row stride padded to a multiple of 4) = normalize(x) . normalize(W)^T, then -- when `margin` is given --
+    the AM / AAM margin and scale on each row's target column (target int32 [B], -1 = none).  x fp32 [B, D], W fp32 parameter [V, D].
+    normalize is st5_norm_rows: x / max(|x|, 1e-8) where F.normalize clamps the norm at 1e-12 -- equal unless a row's norm is
+    below 1e-8, and a zero row gives a zero cosine row either way."""
+
+    @staticmethod
+    def forward(ctx, x, weight, target, margin):
+        L = hip.lib()
+        st = hip.stream()
+        dev = x.device
+        x = x.contiguous()
+        B, D = x.shape
+        V = weight.shape[0]
+        w = weight.detach()
+        assert x.dtype == torch.float32 and w.dtype == torch.float32 and w.is_contiguous() and D % 4 == 0
+        ld = (V + 3) // 4 * 4     # fp32 GEMM operands need ld % 4 == 0 (class_num is odd in the recipe)
+        xn = torch.empty(B, D, dtype=torch.float32, device=dev)
+        inv_x = torch.empty(B, dtype=torch.float32, device=dev)
+        wn = torch.empty(V, D, dtype=torch.float32, device=dev)
+        inv_w = torch.empty(V, dtype=torch.float32, device=dev)
+        hip.check(L.st5_norm_rows(w.data_ptr(), wn.data_ptr(), inv_w.data_ptr(), V, D, hip.F32, st), "st5_norm_rows")
+        hip.check(L.st5_norm_rows(x.data_ptr(), xn.data_ptr(), inv_x.data_ptr(), B, D, hip.F32, st), "st5_norm_rows")
+        cos = torch.empty(B, ld, dtype=torch.float32, device=dev)
+        hip.gemm(hip.operand(xn, D), hip.operand(wn, D), hip.operand(cos, ld), B, V, D, hip.F32)
+        out = cos
+        if margin is not None:
+            mode, m, s = margin
+            out = torch.empty(B, ld, dtype=torch.float32, device=dev)
+            hip.check(L.st5_angular_margin_fwd(cos.data_ptr(), ld, target.data_ptr(), out.data_ptr(), ld, B, V, mode, m, s, st),
+                      "st5_angular_margin_fwd")
+        if target is None:
+            target = torch.full((B,), -1, dtype=torch.int32, device=dev)
+        ctx.save_for_backward(xn, inv_x, wn, inv_w, cos, target)
+        ctx.meta = (weight, margin if margin is not None else (MARGIN_AM, 0.0, 1.0), ld)   # (no margin: dcos = dlogits)
+        return out[:, :V]
+
+    @staticmethod
+    def backward(ctx, dlogits):
+        xn, inv_x, wn, inv_w, cos, target = ctx.saved_tensors
+        weight, margin, ld = ctx.meta
+        L = hip.lib()
+        st = hip.stream()
+        B, D = xn.shape
+        V = wn.shape[0]
+        dev = xn.device
+        dlogits = dlogits.float()
+        if dlogits.stride(1) != 1:
+            dlogits = dlogits.contiguous()
+        dcos = torch.empty(B, ld, dtype=torch.float32, device=dev)
+        mode, m, s = margin
+        hip.check(L.st5_angular_margin_bwd(cos.data_ptr(), ld, target.data_ptr(), dlogits.data_ptr(), dlogits.stride(0), dcos.data_ptr(),
+                                           ld, B, V, mode, m, s, st), "st5_angular_margin_bwd")
+        dx = None
+        if ctx.needs_input_grad[0]:
+            dxn = torch.empty(B, D, dtype=torch.float32, device=dev)
+            hip.gemm(hip.operand(dcos, ld), hip.operand(wn, D), hip.operand(dxn, D), B, D, V, hip.F32, flags=hip.B_KSTRIDED)
+            dx = torch.empty(B, D, dtype=torch.float32, device=dev)
+            hip.check(L.st5_norm_rows_bwd(xn.data_ptr(), inv_x.data_ptr(), dxn.data_ptr(), dx.data_ptr(), B, D, 0, hip.F32, st),
+                      "st5_norm_rows_bwd")
+        if weight.requires_grad:
+            dwn = torch.empty(V, D, dtype=torch.float32, device=dev)
+            hip.gemm(hip.operand(dcos, ld), hip.operand(xn, D), hip.operand(dwn, D), V, D, B, hip.F32,
+                     flags=hip.A_KSTRIDED | hip.B_KSTRIDED | hip.OUT_F32)
+            hip.check(L.st5_norm_rows_bwd(wn.data_ptr(), inv_w.data_ptr(), dwn.data_ptr(), grad_buffer(weight).data_ptr(), V, D, 1, hip.F32,
+                                          st), "st5_norm_rows_bwd")
+            _grad_done(weight)
+        return dx, None, None, None
+
+
+def cosine_logits(x, weight, target=None, margin=None):
+    """margin = (MARGIN_AM | MARGIN_AAM | MARGIN_AAM_EASY, m, s) applies that margin (target int64 [B], -1 = no margin in that row);
+    None gives the plain cosines."""
+    t32 = None
+    if margin is not None:
+        assert target is not None
+        t32 = target.to(torch.int32).contiguous()
+        margin = (int(margin[0]), float(margin[1]), float(margin[2]))
+    return CosineLogitsFunction.apply(as_float(x), weight, t32, margin)
+
+
+class TimeMeanFunction(torch.autograd.Function):
+    """x [T, B, C] (time-major, channels contiguous, compute dtype) -> fp32 [B, C] mean over all T frames (csrc/speaker_head.hip)."""
+
+    @staticmethod
+    def forward(ctx, x):
+        T, B, C = x.shape
+        if x.stride(2) != 1:
+            x = x.contiguous()
+        y = torch.empty(B, C, dtype=torch.float32, device=x.device)
+        hip.check(hip.lib().st5_time_mean_fwd(x.data_ptr(), x.stride(0), x.stride(1), T, B, C, y.data_ptr(), _dt(x), hip.stream()),
+                  "st5_time_mean_fwd")
+        ctx.meta = (T, B, C, x.dtype)
+        return y
+
+    @staticmethod
+    def backward(ctx, dy):
+        T, B, C, dtype = ctx.meta
+        dy = dy.contiguous().float()
+        dx = torch.empty(T, B, C, dtype=dtype, device=dy.device)
+        hip.check(hip.lib().st5_time_mean_bwd(dy.data_ptr(), T, B, C, 0, dx.data_ptr(), _dt(dtype), hip.stream()), "st5_time_mean_bwd")
+        return dx
+
+
+def time_mean(x):
+    return TimeMeanFunction.apply(x)

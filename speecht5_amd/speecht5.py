@@ -1,6 +1,7 @@
 """T5TransformerModel mirror of SpeechT5/speecht5/models/speecht5.py:47-1447: same registration names
 (`t5_transformer` + archs), constructor/builders, forward routing, inference entry points and state-dict
 keys, with every module running on the gfx950 HIP kernels (speecht5_amd/csrc)."""
+import contextlib
 import logging
 from typing import Dict, List, Optional, Tuple
 
@@ -14,6 +15,7 @@ from .fairseq_compat import FairseqEncoderDecoderModel, register_model, register
 from .modules import (GumbelVectorQuantizer, SpeechDecoderPostnet, SpeechDecoderPrenet, SpeechEncoderPostnet,
                       SpeechEncoderPrenet, TextDecoderPostnet, TextDecoderPrenet, TextEncoderPrenet, TransformerDecoder,
                       TransformerEncoder)
+from .modules.speaker_decoder_postnet import SpeakerDecoderPostnet
 
 logger = logging.getLogger(__name__)
 
@@ -126,6 +128,25 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         return SpeechEncoderPostnet(dictionaries, args)
 
     @classmethod
+    def build_speaker_decoder_postnet(cls, embed_dim, class_num, args):
+        return SpeakerDecoderPostnet(embed_dim, class_num, args)
+
+    @staticmethod
+    def check_s2c_options(args):
+        """The speaker-identification options this project does not implement are refused by name (speecht5.py:674-713,
+        :818-842, :912-932 of the reference); the recipe uses none of them."""
+        pooling = getattr(args, "sid_pooling_layer", "decoder")
+        if pooling in ("decoder-las", "encoder-speaker"):
+            raise NotImplementedError(f"--sid-pooling-layer {pooling} is not implemented (decoder, encoder and encoder-cls are)")
+        for flag in ("sid_decoder_speaker", "sid_t5_postnet", "sid_shuffle_encoder_input", "sid_pad_prenet"):
+            if getattr(args, flag, False):
+                raise NotImplementedError(f"--{flag.replace('_', '-')} is not implemented for s2c")
+        if getattr(args, "sid_encoder_cls", None) is not None:
+            raise NotImplementedError("--sid-encoder-cls is not implemented for s2c")
+        if pooling not in ("decoder", "encoder", "encoder-cls"):
+            raise ValueError(f"unknown --sid-pooling-layer {pooling!r}")
+
+    @classmethod
     def build_model(cls, args, task):
         base_architecture(args)
 
@@ -149,11 +170,13 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         speech_decoder_prenet = cls.build_speech_decoder_prenet(speech_odim, args)
         text_decoder_postnet = cls.build_text_decoder_postnet(text_decoder_embed_tokens, task.dicts["text"], args)
         speech_decoder_postnet = cls.build_speech_decoder_postnet(speech_odim, args)
+        speaker_decoder_postnet = None
         if getattr(task, "t5_task", None) == "s2c":
-            raise NotImplementedError("speaker identification (s2c) is outside the SpeechT5 hot-path scope (SURVEY.md 2.2)")
+            cls.check_s2c_options(args)
+            speaker_decoder_postnet = cls.build_speaker_decoder_postnet(args.sid_embed_dim, len(task.dicts["text"]), args)
         speech_encoder_postnet = cls.build_speech_encoder_postnet(task.dicts["hubert"], args) if "hubert" in task.dicts else None
         return cls(args, encoder, decoder, text_encoder_prenet, speech_encoder_prenet, text_decoder_prenet,
-                   speech_decoder_prenet, text_decoder_postnet, speech_decoder_postnet, None, speech_encoder_postnet)
+                   speech_decoder_prenet, text_decoder_postnet, speech_decoder_postnet, speaker_decoder_postnet, speech_encoder_postnet)
 
     # ---- criterion-facing helpers (speecht5.py:731-784) ----
     def get_normalized_probs(self, net_output, log_probs, sample=None):
@@ -216,8 +239,13 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
             codebook_out = {}
         else:
             output_type = "speech"
+        sid_target = None
         if task_name is not None and task_name == "s2c":
-            raise NotImplementedError("s2c")
+            # (:805-810) the reference's one-hot sid_target, kept as the class index; the collater never passes target_list, so in
+            # the recipe the margin is never applied
+            if target_list is not None and target_list.size(1) == 1:
+                sid_target = target_list.squeeze(1)
+            target_list = None
 
         # Encoder pre-net
         if input_type == "text":
@@ -233,6 +261,13 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
 
         if task_name is not None and task_name == "speech_pretrain" and feature_only:
             return encoder_output["encoder_out"][0].transpose(0, 1)
+
+        if task_name is not None and task_name == "s2c":   # (:836-842) encoder pooling, before the codebook mix
+            pooling = self.args.sid_pooling_layer
+            if pooling == "encoder":   # mean over ALL frames, padded ones included
+                return self.speaker_decoder_postnet(Fn.time_mean(encoder_output["encoder_out"][0]), sid_target), None
+            if pooling == "encoder-cls":
+                return self.speaker_decoder_postnet(encoder_output["encoder_out"][0][0], sid_target), None
 
         if target_list is not None:
             hubert_results = self.hubert_layer(encoder_output["encoder_out"][0].transpose(0, 1), encoder_padding_mask,
@@ -269,18 +304,27 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
             return encoder_output
 
         # Decoder pre-net
-        if output_type == "text":
+        if task_name is not None and task_name == "s2c":
+            # (:893-896) the pre-net's output is replaced by zeros: nothing of it (nor a gradient) reaches the decoder
+            prev_output_tokens, tgt_mask = self._zero_decoder_input(prev_output_tokens)
+        elif output_type == "text":
             prev_output_tokens, tgt_mask, _ = self.text_decoder_prenet(prev_output_tokens)
         else:
             prev_output_tokens, tgt_mask = self.speech_decoder_prenet(prev_output_tokens, tgt_lengths, spkembs)
         if task_name is not None and task_name == "s2s" and getattr(self.args, "se_decoder_input", "previous_target") == "source":
             prev_output_tokens, tgt_mask = self.speech_decoder_prenet(src_tokens, src_lengths)
 
-        decoder_output, extra = self.decoder(
-            prev_output_tokens, tgt_mask, encoder_output,
-            full_context_alignment=getattr(self.args, "decoder_full_context_alignment", False),
-            alignment_layer=(-1 if target_list is None and output_type == "speech" else None))
+        if task_name is not None and task_name == "s2c":
+            alignment_layer = self.decoder.num_layers    # (no layer: s2c reads no attention weights)
+        else:
+            alignment_layer = -1 if target_list is None and output_type == "speech" else None
+        with self._no_attention_weights(task_name == "s2c"):
+            decoder_output, extra = self.decoder(
+                prev_output_tokens, tgt_mask, encoder_output,
+                full_context_alignment=getattr(self.args, "decoder_full_context_alignment", False), alignment_layer=alignment_layer)
 
+        if task_name is not None and task_name == "s2c":   # (:925-928) decoder pooling
+            return self.speaker_decoder_postnet(self._time_mean_btc(decoder_output), sid_target), None
         if task_name is not None and task_name == "s2t":
             return (self.text_decoder_postnet(decoder_output), None), encoder_output
         if output_type == "text":
@@ -312,6 +356,45 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         if incremental_state is not None:
             out = out[:, -1:]
         return out, extra
+
+    def _zero_decoder_input(self, prev_output_tokens):
+        """Zero decoder input [B, T, C] in the compute dtype (s2c uses a zero vector as [CLS]) and the pre-net's padding mask."""
+        B, T = prev_output_tokens.shape
+        x = torch.zeros(B, T, self.args.decoder_embed_dim, dtype=Fn.compute_dtype(), device=prev_output_tokens.device)
+        return x, prev_output_tokens.eq(self.text_decoder_prenet.padding_idx)
+
+    @contextlib.contextmanager
+    def _no_attention_weights(self, on=True):
+        """s2c reads no attention weights.  In eval every decoder layer would otherwise materialise its cross-attention
+        probabilities (`need_attn`), the unfused path, whose softmax takes at most 4096 keys: a 160 s utterance has 7999.  With the
+        alignment layer past the last one and need_attn off, the one query stays on the flash kernels in bf16."""
+        layers = list(getattr(self.decoder, "layers", None) or []) if on else []
+        old = [layer.need_attn for layer in layers]
+        for layer in layers:
+            layer.need_attn = False
+        try:
+            yield
+        finally:
+            for layer, v in zip(layers, old):
+                layer.need_attn = v
+
+    @staticmethod
+    def _time_mean_btc(x):
+        """x.mean(1) of [B, T, C] as fp32 [B, C]: a view for the one-position decoder input of s2c, else st5_time_mean."""
+        if x.size(1) == 1:
+            return Fn.as_float(x[:, 0])
+        return Fn.time_mean(x.transpose(0, 1))
+
+    @torch.no_grad()
+    def generate_class(self, source, prev_output_tokens, **kwargs):
+        """speecht5.py:1171-1186: encoder, the zeroed decoder input, decoder, speaker head on the decoder output's time mean; int64
+        classes [B].  Decoder pooling whatever --sid-pooling-layer says (as the reference)."""
+        encoder_out = self.forward_encoder(source, padding_mask=kwargs["padding_mask"])
+        x, tgt_mask = self._zero_decoder_input(prev_output_tokens)
+        with self._no_attention_weights():
+            decoder_output, _ = self.decoder(x, tgt_mask, encoder_out=encoder_out, alignment_layer=self.decoder.num_layers)
+        decoder_out, _ = self.speaker_decoder_postnet(self._time_mean_btc(decoder_output))
+        return decoder_out.argmax(1)
 
     def set_num_updates(self, num_updates):
         for m in self.modules():
@@ -511,6 +594,11 @@ def base_architecture(args):
     d("freeze_encoder_updates", 0)
     d("freeze_decoder_updates", 0)
     d("no_freeze_encoder_layer", None)
+    d("sid_embed_dim", 128)
+    d("sid_pooling_layer", "decoder")
+    d("softmax_scale", 1)
+    d("softmax_margin", 0)
+    d("softmax_easy_margin", False)
     d("modules_filter", None)
     d("conv_pos", 128)
     d("conv_pos_groups", 16)

@@ -261,6 +261,14 @@ class SpeechT5Task(LegacyFairseqTask):
                     unk_penalty=getattr(args, "unkpen", 0), temperature=getattr(args, "temperature", 1.0),
                     no_repeat_ngram_size=getattr(args, "no_repeat_ngram_size", 0), **kw)
 
+    def generate_class(self, models, net_input, prefix_tokens, **kwargs):
+        """tasks/speecht5.py:631-638: speaker identification with the first model; int64 classes [B]."""
+        with torch.no_grad():
+            encoder_input = {k: v for k, v in net_input.items() if k != "prev_output_tokens" and k != "task_name"}
+            encoder_input.update(kwargs)
+            encoder_input.update({"prev_output_tokens": prefix_tokens})
+            return models[0].generate_class(**encoder_input)
+
     @property
     def source_dictionary(self):
         return None
