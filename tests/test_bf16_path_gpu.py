@@ -337,8 +337,8 @@ def test_tn_phased_256_tile(cuda, mode):
 
 
 # ----------------------------------------------------------------------------------------------------------------------
-# fused attention backward vs torch autograd (no dropout: torch cannot reproduce the counter RNG; the dropout masks of the
-# fused kernels are pinned against the unfused path, which test_ops_gpu.py pins against torch, in test_flash_gpu.py)
+# fused attention backward vs torch autograd (no dropout here; with dropout, test_attention_fp64_gpu.py holds the fused kernels to
+# an fp64 reference whose masks come from a numpy restatement of the counter RNG, tests/attention_reference.py)
 # ----------------------------------------------------------------------------------------------------------------------
 def _torch_attention(q, k, v, pe, kpm, causal, maxrel):
     """fp32 reference on [B,H,T,hd] leaf tensors (multihead_attention.py:340-389 incl. the Shaw bias of encoder.py:52-59)."""
