@@ -582,6 +582,26 @@ int st5_lm_reorder(const int32_t* anc, int64_t anc_ld, const int64_t* order, int
  * lprobs fp32 [rows][lp_ld], logits in `dtype` [rows][lg_ld]; the log-softmax in fp32.  Columns >= V_lm are not touched. */
 int st5_lm_fuse_logprobs(float* lprobs, int64_t lp_ld, const void* logits, int64_t lg_ld, int32_t rows, int32_t V_lm, float lm_weight,
                          int dtype, void* stream);
+/* ---- Batched speech synthesis (T5TransformerModel.generate_speech_batch; csrc/tts_decode.hip) ----
+ * st5_decode_cross_attn (multihead_attention.py:340-389 with one query per row b): ctx[b][h*64 + i] = softmax_j(q[b] . k_j * 64^-0.5) v_j
+ * over the S encoder positions of row b, k_j = kv[(b*S + j)*kv_ld + k_off + h*64 ...], v_j at + H*64; a set byte kpm[b*S + j]
+ * (uint8 [B][S], or NULL) excludes key j.  Scores, softmax and accumulation fp32; ctx [B][ctx_ld] and q [B][q_ld] in `dtype`.
+ * probs (fp32, or NULL): probs[b*p_row + h*p_head + j] = the probability of key j (0 at an excluded key); nothing else of the
+ * record is written.  head_dim 64 only and H <= 64, else ST5_ERR_ARG.  q / kv 16-byte aligned and q_ld, kv_ld, k_off multiples of
+ * 4 (fp32) / 8 (bf16), else ST5_ERR_ALIGN.  ws: fp32 workspace of st5_decode_cross_attn_ws_bytes(B, S, H, head_dim) bytes (16-byte
+ * aligned; NULL when that is 0). */
+int64_t st5_decode_cross_attn_ws_bytes(int32_t B, int32_t S, int32_t H, int32_t head_dim);
+int st5_decode_cross_attn(const void* q, int64_t q_ld, const void* kv, int64_t kv_ld, int64_t k_off, const uint8_t* kpm, int32_t B,
+                          int32_t S, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld, float* probs, int64_t p_row, int64_t p_head,
+                          float* ws, int dtype, void* stream);
+/* st5_tts_step_tail (speecht5.py:1233-1246 for B rows at decode step idx, 1 <= idx <= cap): y fp32 [B][y_ld] = r*odim features then r
+ * stop logits.  For every row with done[b] == 0: probs[b][(idx-1)*r + k] = sigmoid(logit k), mel[b][(idx-1)*r + k][:] = feature frame
+ * k, next[b][:] = frame r-1 (in `dtype`); the row stops (done[b] = 1, steps[b] = idx) when idx >= minlen[b] and (some probability
+ * >= threshold or idx >= maxlen[b]).  Rows with done[b] != 0 are not written.  *active = rows with done == 0 afterwards.
+ * mel [B][cap*r][odim], probs [B][cap*r] fp32; B <= 4096. */
+int st5_tts_step_tail(const float* y, int64_t y_ld, int32_t B, int32_t r, int32_t odim, const int32_t* minlen, const int32_t* maxlen,
+                      int32_t* done, int32_t* steps, int32_t idx, int32_t cap, float threshold, float* mel, float* probs, void* next,
+                      int64_t next_ld, int32_t* active, int dtype, void* stream);
 /* ---- Speaker-identification head (s2c, speaker_decoder_postnet.py; csrc/speaker_head.hip) ----
  * st5_angular_margin_fwd: out[b][v] = s * m(cos[b][v]) for v < V on fp32 cosine logits, with the margin only on column target[b]
  * (int32; -1 = no margin in that row, which is then only scaled).  mode ST5_MARGIN_AM (AngularMargin): s * (cos - m) on the target.

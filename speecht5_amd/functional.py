@@ -3033,6 +3033,49 @@ def lm_fuse_logprobs(lprobs, logits, lm_weight):
 
 
 # -------------------------------------------------------------------------------------------------
+# Batched speech synthesis (csrc/tts_decode.hip): one-query cross-attention that records its probabilities, and the decode step's
+# tail (stop rule, frame record, next input).  Inference only, no autograd.
+# -------------------------------------------------------------------------------------------------
+def decode_cross_attn_ws(B, S, H, hd, device):
+    """fp32 workspace of st5_decode_cross_attn for B rows over S keys (None when that launch needs none)."""
+    n = int(hip.lib().st5_decode_cross_attn_ws_bytes(B, S, H, hd))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device) if n else None
+
+
+def decode_cross_attn(q, kv, k_off, S, H, hd, kpm=None, probs=None, ws=None):
+    """q [B, >= C] (compute dtype, row stride q.stride(0)); kv [B*S, kv_ld] rows holding this layer's K at column k_off and V at
+    k_off + C; kpm uint8 [B, S] (1 = padded key) or None.  probs: None, or (fp32 tensor whose first element is row 0 / head 0 /
+    key 0 of the record, row stride, head stride).  Returns ctx [B, C]."""
+    B = q.shape[0]
+    C = H * hd
+    assert kv.stride(1) == 1 and q.stride(1) == 1 and kv.dtype == q.dtype and kv.shape[0] == B * S
+    assert kpm is None or (kpm.dtype == torch.uint8 and kpm.is_contiguous() and kpm.shape == (B, S))
+    if ws is None or ws.numel() * 4 < hip.lib().st5_decode_cross_attn_ws_bytes(B, S, H, hd):
+        ws = decode_cross_attn_ws(B, S, H, hd, q.device)
+    p, p_row, p_head = probs if probs is not None else (None, 0, 0)
+    assert p is None or p.dtype == torch.float32
+    ctx = torch.empty(B, C, dtype=q.dtype, device=q.device)
+    hip.check(hip.lib().st5_decode_cross_attn(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), int(k_off), hip.ptr(kpm), B, S, H,
+                                              hd, ctx.data_ptr(), C, hip.ptr(p), p_row, p_head, hip.ptr(ws), _dt(q), hip.stream()),
+              "st5_decode_cross_attn")
+    return ctx
+
+
+def tts_step_tail(y, r, odim, minlen, maxlen, done, steps, idx, threshold, mel, probs, nxt, active):
+    """Step idx (1-based) of B rows: y fp32 [B, >= r*odim + r]; int32 [B] minlen / maxlen / done / steps; records mel [B, cap*r, odim]
+    and probs [B, cap*r] fp32; nxt [B, odim] (compute dtype) the next decoder input; active int32 [1] (rows still running)."""
+    B = y.shape[0]
+    cap = probs.shape[1] // r
+    assert y.dtype == torch.float32 and y.stride(1) == 1 and nxt.stride(1) == 1
+    assert mel.is_contiguous() and probs.is_contiguous() and mel.shape == (B, cap * r, odim) and probs.shape == (B, cap * r)
+    for t in (minlen, maxlen, done, steps, active):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    hip.check(hip.lib().st5_tts_step_tail(y.data_ptr(), y.stride(0), B, r, odim, minlen.data_ptr(), maxlen.data_ptr(), done.data_ptr(),
+                                          steps.data_ptr(), int(idx), cap, float(threshold), mel.data_ptr(), probs.data_ptr(),
+                                          nxt.data_ptr(), nxt.stride(0), active.data_ptr(), _dt(nxt), hip.stream()), "st5_tts_step_tail")
+
+
+# -------------------------------------------------------------------------------------------------
 # Speaker-identification head (s2c, speaker_decoder_postnet.py): BatchNorm1d over [B, C] rows (st5_batchnorm_act_*), cosine logits
 # F.linear(F.normalize(x), F.normalize(W)) (st5_norm_rows + st5_gemm) with the AM / AAM margin (csrc/speaker_head.hip), and the time
 # mean of --sid-pooling-layer encoder.  The head runs in fp32 whatever the compute dtype: it is B rows wide.

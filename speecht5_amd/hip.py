@@ -199,6 +199,11 @@ _SIGS = {
                                    c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "st5_lm_reorder": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int64, c_void_p]),
     "st5_lm_fuse_logprobs": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_float, c_int, c_void_p]),
+    "st5_decode_cross_attn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
+    "st5_decode_cross_attn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                      c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "st5_tts_step_tail": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                  c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
     "st5_angular_margin_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
     "st5_angular_margin_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float,
                                        c_float, c_void_p]),

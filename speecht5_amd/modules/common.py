@@ -91,16 +91,16 @@ class ScaledPositionalEncoding(nn.Module):
 
 
 class ScaledPEAdd(torch.autograd.Function):
-    """y = x + alpha * pe[:T] (pe constant fp32 table, alpha fp32 scalar parameter)."""
+    """y = x + alpha * pe[offset:offset + T] (pe constant fp32 table, alpha fp32 scalar parameter)."""
 
     @staticmethod
-    def forward(ctx, x, alpha, pe):
+    def forward(ctx, x, alpha, pe, offset=0):
         B, T, d = x.shape
-        idx = torch.arange(T, device=x.device, dtype=torch.int32).repeat(B)
+        idx = torch.arange(offset, offset + T, device=x.device, dtype=torch.int32).repeat(B)
         y = Fn.add_table_rows_dev(x, pe, idx, alpha.detach())  # alpha stays on the device (no host sync)
         ctx.save_for_backward(pe)
         ctx.alpha = alpha
-        ctx.T = T
+        ctx.T, ctx.offset = T, offset
         return y
 
     @staticmethod
@@ -109,5 +109,5 @@ class ScaledPEAdd(torch.autograd.Function):
         dalpha = None
         if ctx.alpha.requires_grad:
             # d alpha = sum(dy * pe): tiny reduction (glue)
-            dalpha = (dy.float().sum(0) * pe[:ctx.T]).sum()
-        return dy, dalpha, None
+            dalpha = (dy.float().sum(0) * pe[ctx.offset:ctx.offset + ctx.T]).sum()
+        return dy, dalpha, None, None

@@ -9,6 +9,7 @@ import torch
 import torch.nn as nn
 
 from .. import functional as Fn
+from .. import hip
 from ..fairseq_compat import IncrementalState
 
 
@@ -130,6 +131,34 @@ class MultiheadAttention(nn.Module, IncrementalState):
             ctx, probs = Fn.CrossAttentionFunction.apply(q, cache["kvp"], kpm, (B, H, 1, S, hd, 0.0, need_weights))
         out = Fn.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual)
         return out, probs
+
+    # ---- batched speech synthesis (generate_speech_batch): preallocated slot cache, one query per row ----
+    @torch.no_grad()
+    def forward_rows_slots(self, x, B, cache, residual):
+        """Self-attention of the newest position: x [B, C] rows.  K|V go straight into slot cache["t"] of cache["slots"]
+        ([B, cap, 2C]); the query attends over slots 0..t of its own row (identity ancestry cache["anc"])."""
+        H, hd, C = self.num_heads, self.head_dim, self.embed_dim
+        kv, t = cache["slots"], cache["t"]
+        q = Fn.linear(x, self.q_proj.weight, self.q_proj.bias)
+        Fn.linear_into(x, [self.k_proj.weight, self.v_proj.weight], [self.k_proj.bias, self.v_proj.bias],
+                       hip.operand(kv, kv.shape[1] * 2 * C, off=t * 2 * C), 2 * C)
+        ctx = Fn.lm_decode_attn(q, kv, cache["anc"], t + 1, H, hd, cache.get("ws"))
+        cache["t"] = t + 1
+        return Fn.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual)
+
+    @torch.no_grad()
+    def forward_rows_one_query(self, x, B, cache, kv, S, key_padding_mask, residual, rec=None):
+        """Cross-attention of one query per row over the encoder rows kv [B*S, C] (projected once into cache["kvp"]).
+        rec: None, or (fp32 tensor at this step's column of row 0 / head 0, row stride, head stride) that receives the
+        probabilities [B, H, S] (st5_decode_cross_attn)."""
+        H, hd, C = self.num_heads, self.head_dim, self.embed_dim
+        if "kvp" not in cache:
+            cache["kvp"] = Fn.linear(kv, [self.k_proj.weight, self.v_proj.weight], [self.k_proj.bias, self.v_proj.bias])
+            cache["kpm"] = _mask_bytes(key_padding_mask) if key_padding_mask is not None else None
+            cache["ws"] = Fn.decode_cross_attn_ws(B, S, H, hd, x.device)
+        q = Fn.linear(x, self.q_proj.weight, self.q_proj.bias)
+        ctx = Fn.decode_cross_attn(q, cache["kvp"], 0, S, H, hd, kpm=cache["kpm"], probs=rec, ws=cache["ws"])
+        return Fn.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual)
 
     # ---- reference-compatible Time x Batch x Channel interface ----
     def forward(self, query, key, value, key_padding_mask=None, incremental_state=None, need_weights=True,

@@ -44,14 +44,16 @@ class SpeechDecoderPrenet(nn.Module):
         self.num_updates = 0
         self.freeze_decoder_updates = args.freeze_decoder_updates
 
-    def forward(self, prev_output_tokens, tgt_lengths_in=None, spkembs=None):
+    def forward(self, prev_output_tokens, tgt_lengths_in=None, spkembs=None, pos_offset=0):
+        """pos_offset: position of the first frame of `prev_output_tokens` (the batched decode loop feeds only the newest frame; the
+        pre-net is position-wise, so this equals the last position of the whole prefix)."""
         ft = self.freeze_decoder_updates <= self.num_updates
         with torch.no_grad() if not ft else contextlib.ExitStack():
             inl, spe = self.decoder_prenet[0], self.decoder_prenet[1]
             x = Fn.as_compute(prev_output_tokens.contiguous())
             x = inl[0](x)
             x = Fn.linear(x, inl[1].weight, inl[1].bias)
-            x = ScaledPEAdd.apply(x, spe.alpha, spe.pe(x.shape[1], x.device))
+            x = ScaledPEAdd.apply(x, spe.alpha, spe.pe(pos_offset + x.shape[1], x.device), pos_offset)
             x = Fn.dropout(x, spe.dropout_rate, self.training)
             if spkembs is not None:
                 # [x ; normalize(spk)] -> Linear -> ReLU (:81-83); the concat is assembled by torch (glue)

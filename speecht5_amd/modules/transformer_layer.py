@@ -150,7 +150,10 @@ class TransformerDecoderLayer(nn.Module):
     @torch.no_grad()
     def forward_rows_cached(self, x, B, cache, enc_rows, S, enc_padding_mask, self_padding_mask, need_attn):
         """Incremental step (transformer_layer.py:262-404 with incremental_state): x [B, C] = the newest position only;
-        `cache` = {"self": {...}, "cross": {...}} of this layer.  Returns (rows [B, C], cross-attn probs [B,H,1,S] or None)."""
+        `cache` = {"self": {...}, "cross": {...}} of this layer.  Returns (rows [B, C], cross-attn probs [B,H,1,S] or None).
+        A cache that carries a preallocated slot cache (`cache["slots"]`, generate_speech_batch) takes the slot path instead."""
+        if "slots" in cache:
+            return self._forward_rows_slots(x, B, cache, enc_rows, S, enc_padding_mask)
         nb = self.normalize_before
         h = self.self_attn_layer_norm(x) if nb else x
         x, _ = self.self_attn.forward_rows_cached(h, B, cache.setdefault("self", {}), key_padding_mask=self_padding_mask, residual=x)
@@ -169,6 +172,29 @@ class TransformerDecoderLayer(nn.Module):
         if not nb:
             x = self.final_layer_norm(x)
         return x, attn
+
+    def _forward_rows_slots(self, x, B, cache, enc_rows, S, enc_padding_mask):
+        """Decode step of generate_speech_batch: self-attention K|V written into slot cache["t"] of cache["slots"], the
+        cross-attention's probabilities written into cache["rec"] (or nowhere when it is None).  Returns (rows [B, C], None)."""
+        nb = self.normalize_before
+        h = self.self_attn_layer_norm(x) if nb else x
+        x = self.self_attn.forward_rows_slots(h, B, cache, residual=x)
+        if not nb:
+            x = self.self_attn_layer_norm(x)
+        if self.encoder_attn is not None and enc_rows is not None:
+            h = self.encoder_attn_layer_norm(x) if nb else x
+            rec = cache.get("rec")
+            if rec is not None:   # (record [B, H, cap, S] of this layer: this step's column is slot t - 1)
+                rec = (rec[:, :, cache["t"] - 1], rec.stride(0), rec.stride(1))
+            x = self.encoder_attn.forward_rows_one_query(h, B, cache.setdefault("cross", {}), enc_rows, S, enc_padding_mask,
+                                                         residual=x, rec=rec)
+            if not nb:
+                x = self.encoder_attn_layer_norm(x)
+        h = self.final_layer_norm(x) if nb else x
+        x = Fn.ffn(h, x, self.fc1, self.fc2, self.act, 0.0, 0.0)
+        if not nb:
+            x = self.final_layer_norm(x)
+        return x, None
 
     def forward(self, x, encoder_out=None, encoder_padding_mask=None, incremental_state=None, prev_self_attn_state=None,
                 prev_attn_state=None, self_attn_mask=None, self_attn_padding_mask=None, need_attn=False,

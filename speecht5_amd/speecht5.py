@@ -51,6 +51,19 @@ def init_bert_params(module):
         normal_(module.v_proj.weight.data)
 
 
+def tts_row_limits(T_in, reduction_factor, text, **kwargs):
+    """Stop threshold, per-row minlen_b / maxlen_b and the step cap of generate_speech_batch for encoder lengths T_in, with the
+    keywords read exactly as generate_speech reads them: `threshold` also stands for both length ratios when it is passed
+    (speecht5.py:1191-1201); otherwise 0.5, 0.0 and 20.0 (text) / 10.0 (speech)."""
+    threshold = kwargs.get("threshold", 0.5)
+    minlenratio = kwargs.get("threshold", 0.0)
+    maxlenratio = kwargs.get("threshold", 20.0 if text else 10.0)
+    minlen = [int(t * minlenratio / reduction_factor) for t in T_in]
+    maxlen = [int(t * maxlenratio / reduction_factor) for t in T_in]
+    cap = max(1, max(max(a, b) for a, b in zip(minlen, maxlen)))
+    return threshold, minlen, maxlen, cap
+
+
 @register_model("t5_transformer")
 class T5TransformerModel(FairseqEncoderDecoderModel):
     def __init__(self, args, encoder, decoder, text_encoder_prenet, speech_encoder_prenet, text_decoder_prenet,
@@ -449,6 +462,93 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         if mel.size(0) == maxlen:
             logging.warning("output length reaches maximum length")
         return mel, probs, attn
+
+    # ---- batched speech synthesis: generate_speech for B utterances at once, each row with its own stopping step ----
+    TTS_POLL_STEPS = 8   # decode steps between two reads of the active-row count (at most this many - 1 idle steps per call)
+
+    def _encode_rows(self, source, src_tokens, padding_mask):
+        """Encoder output of B utterances as one padded batch: (encoder_out dict with [S_max, B, C] and a [B, S_max] key-padding
+        mask, per-row encoder lengths T_b as a host list).  Text rows run as one padded batch (position-wise or key-masked); speech
+        rows one by one on the unpadded clip, since conv layer 0's GroupNorm and the convolutional positional embedding see the
+        padding of a padded batch."""
+        if source is None:
+            enc = self.forward_text_encoder(src_tokens)
+            pad = src_tokens.eq(self.text_encoder_prenet.padding_idx)
+            return enc, (~pad).sum(1).tolist()
+        B = source.size(0)
+        n = [source.size(1)] * B if padding_mask is None else (~padding_mask.bool()).sum(1).tolist()
+        outs = []
+        for b in range(B):
+            pm = padding_mask[b:b + 1, :n[b]] if padding_mask is not None else source.new_zeros(1, n[b], dtype=torch.bool)
+            outs.append(self.forward_encoder(source[b:b + 1, :n[b]], padding_mask=pm)["encoder_out"][0])   # [T_b, 1, C]
+        T = [int(o.size(0)) for o in outs]
+        S = max(T)
+        x = outs[0].new_zeros(S, B, outs[0].size(2))
+        for b, o in enumerate(outs):
+            x[:T[b], b] = o[:, 0]
+        mask = torch.arange(S, device=x.device)[None, :] >= torch.tensor(T, device=x.device)[:, None]
+        return {"encoder_out": [x], "encoder_padding_mask": [mask]}, T
+
+    @torch.no_grad()
+    def generate_speech_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, need_attn=True, **kwargs):
+        """generate_speech for B utterances in one decode loop.  Returns B tuples (mel [L_b, odim], probs [L_b], attn
+        [decoder_layers, H, L_b / r, S_b] or None) in row order, each as generate_speech returns it for that row alone.  Text rows
+        are right-padded (TextToSpeechCollater); speech rows come with `padding_mask`.  Row b stops at the first step idx >= minlen_b
+        at which one of its r stop probabilities reaches `threshold` or idx >= maxlen_b; rows that stopped keep computing (their
+        records are final) until the host sees no active row, every TTS_POLL_STEPS steps."""
+        assert source is not None or src_tokens is not None
+        encoder_out, T_in = self._encode_rows(source, src_tokens, padding_mask)
+        r = self.reduction_factor
+        threshold, minlen, maxlen, cap = tts_row_limits(T_in, r, source is None, **kwargs)
+        enc = encoder_out["encoder_out"][0]
+        S, B = enc.size(0), enc.size(1)
+        dev, dtype = enc.device, Fn.compute_dtype()
+        post, pre, dec = self.speech_decoder_postnet, self.speech_decoder_prenet, self.decoder
+        odim = post.odim
+        C = self.args.decoder_embed_dim
+        layers = list(dec.layers)
+        H = layers[0].self_attn.num_heads
+        hd = C // H
+        # decode state: per layer a slot cache [B, cap, 2C] (identity ancestry) and this layer's view of the attention record
+        anc = torch.arange(B, dtype=torch.int32, device=dev).unsqueeze(1).expand(B, cap).contiguous()
+        ws = Fn.lm_decode_attn_ws(B, cap, H, hd, dev)
+        rec = torch.empty(B, len(layers), H, cap, S, dtype=torch.float32, device=dev) if need_attn else None
+        state = {"layers": [{"slots": torch.empty(B, cap, 2 * C, dtype=dtype, device=dev), "anc": anc, "t": 0, "ws": ws,
+                             "rec": rec[:, l] if rec is not None else None} for l in range(len(layers))]}
+        incremental_states = {dec._CACHE_KEY: state}
+        i32 = dict(dtype=torch.int32, device=dev)
+        minlen_d, maxlen_d = torch.tensor(minlen, **i32), torch.tensor(maxlen, **i32)
+        done, steps, active = torch.zeros(B, **i32), torch.zeros(B, **i32), torch.zeros(1, **i32)
+        mel_rec = torch.empty(B, cap * r, odim, dtype=torch.float32, device=dev)
+        prob_rec = torch.empty(B, cap * r, dtype=torch.float32, device=dev)
+        nxt = torch.zeros(B, odim, dtype=dtype, device=dev)
+        host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        ev = torch.cuda.Event()
+        pre.decoder_prenet[1].pe(cap, dev)   # (the PE table once, for every position of the loop)
+        wf = [post.feat_out.weight, post.prob_out.weight]
+        bf = [post.feat_out.bias, post.prob_out.bias]
+        self.tts_polls = 0
+        for idx in range(1, cap + 1):
+            decoder_in, _ = pre(nxt.view(B, 1, odim), spkembs=spkembs, pos_offset=idx - 1)
+            z, _ = dec(decoder_in, None, encoder_out, incremental_states, alignment_layer=-1)
+            y = Fn.as_float(Fn.linear(Fn.as_compute(z.reshape(B, C)), wf, bf))
+            Fn.tts_step_tail(y, r, odim, minlen_d, maxlen_d, done, steps, idx, threshold, mel_rec, prob_rec, nxt, active)
+            if idx % self.TTS_POLL_STEPS == 0 and idx < cap:
+                host.copy_(active, non_blocking=True)
+                ev.record()
+                ev.synchronize()
+                self.tts_polls += 1
+                if int(host[0]) == 0:
+                    break
+        L = steps.tolist()
+        out = []
+        for b in range(B):
+            mel = mel_rec[b, :L[b] * r].unsqueeze(0)
+            if post.postnet is not None:
+                mel = post.postnet(Fn.as_compute(mel.contiguous()))
+            attn = rec[b, :, :, :L[b], :T_in[b]].contiguous() if rec is not None else None
+            out.append((mel.squeeze(0), prob_rec[b, :L[b] * r].clone(), attn))
+        return out
 
     # ---- checkpoint compatibility (speecht5.py:1022-1058): non-strict per-submodule load ----
     def load_state_dict(self, state_dict, strict=True, model_cfg=None, args=None):

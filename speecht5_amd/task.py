@@ -269,6 +269,20 @@ class SpeechT5Task(LegacyFairseqTask):
             encoder_input.update({"prev_output_tokens": prefix_tokens})
             return models[0].generate_class(**encoder_input)
 
+    def generate_speech(self, models, net_input, **kwargs):
+        """tasks/speecht5.py:640-646: speech synthesis of one utterance with the first model; (mel, probs, attn)."""
+        with torch.no_grad():
+            encoder_input = {k: v for k, v in net_input.items() if k != "prev_output_tokens" and k != "task_name"}
+            encoder_input.update(kwargs)
+            return models[0].generate_speech(**encoder_input)
+
+    def generate_speech_batch(self, models, net_input, **kwargs):
+        """generate_speech for a whole collated batch (T5TransformerModel.generate_speech_batch): one (mel, probs, attn) per row."""
+        with torch.no_grad():
+            encoder_input = {k: v for k, v in net_input.items() if k != "prev_output_tokens" and k != "task_name"}
+            encoder_input.update(kwargs)
+            return models[0].generate_speech_batch(**encoder_input)
+
     @property
     def source_dictionary(self):
         return None
