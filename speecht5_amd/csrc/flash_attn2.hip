@@ -838,41 +838,116 @@ struct KWinStager {
   }
 };
 
-// One 32-query sub-tile: in s = raw S[q][key], dp = dO.V; out pd = dropped P, s = dS.  Element r <-> query q0 + (r&3) + 8(r>>2)
-// (q0 includes 4*hi).  Unclipped bucket gradients dQP[q][q - key + maxrel] are stored here (consecutive lanes = consecutive
-// keys = consecutive buckets, descending: coalesced).
-template <int BMODE /*0 none, 1 window (stores the unclipped bucket gradients), 2 clipped: per-query end value, no stores*/, bool SLOW, bool DROP>
-__device__ __forceinline__ void dkv_sub(f32x16& s, const f32x16& dp, f32x16& pd, const BwdArgs& a, const float* stv, const unsigned int* keyv,
-                                        const unsigned int (&braw)[16], bf16_t* dqpb, int qbase, int q0, int ki, bool kvalid,
-                                        bool kmasked, float sc2, unsigned int pcl, unsigned int kshift, unsigned int thresh, float inv_keep) {
+// lse2 / D of the lane's queries q0 + 8g .. + 3, g = 0..3.  PRE: read in front of the S / dP products (32 registers, which the bias kernel
+// does not have: it reads them group by group inside dkv_sub).
+template <bool PRE>
+struct DkvSide {
+  const f32x4* sv;
+  f32x4 lse[PRE ? 4 : 1], d[PRE ? 4 : 1];
+  __device__ __forceinline__ void load(const float* stq) {   // stq = side array + qbase (a multiple of 4: 16-byte reads)
+    sv = reinterpret_cast<const f32x4*>(stq);
+    if (PRE) {
 #pragma unroll
-  for (int r = 0; r < 16; ++r) {
-    const int c = (r & 3) + 8 * (r >> 2);
-    const int qq = q0 + c;
-    const int bk = qq - ki + a.maxrel;     // unclamped bucket
-    const float bv = BMODE == 0 ? 0.f : __uint_as_float(braw[r]);
-    const float x = fmaf(s[r], sc2, bv);
-    float p = fast_exp2(x - stv[qbase + c]);
-    if (SLOW) { if (kmasked || (a.causal && ki > qq + (a.S - a.T))) p = 0.f; }
-    float dpv = dp[r], pv = p;
-    if (DROP) {
-      const unsigned int bits = drop_pair_bits_pc(keyv[qbase + c], pcl);
-      const bool keep = ((bits >> kshift) & 0xffffu) >= thresh;
-      pv = keep ? p * inv_keep : 0.f;
-      dpv = keep ? dpv * inv_keep : 0.f;
+      for (int g = 0; g < 4; ++g) { lse[g] = sv[2 * g]; d[g] = sv[16 + 2 * g]; }
     }
-    pd[r] = pv;
-    const float ds = p * (dpv - stv[64 + qbase + c]);
-    s[r] = ds;
-    if (BMODE == 1) {
-      bool st_ok = kvalid && bk > 0 && bk < a.nb - 1;
-      if (SLOW) st_ok = st_ok && qq < a.T;
-#if FA2_ABL != 3
-      if (st_ok) dqpb[(unsigned int)(qq * a.nb + bk)] = (bf16_t)ds;
-#else
-      asm volatile("" :: "v"(st_ok));
-#endif
+  }
+  __device__ __forceinline__ f32x4 lse4(int g) const { return PRE ? lse[PRE ? g : 0] : sv[2 * g]; }
+  __device__ __forceinline__ f32x4 d4(int g) const { return PRE ? d[PRE ? g : 0] : sv[16 + 2 * g]; }
+};
+
+// One 32-query sub-tile: in s = raw S[q][key], dp = dO.V; out pd = dropped P, s = dS.  Element r <-> query q0 + (r&3) + 8(r>>2)
+// (q0 includes 4*hi).  Straight-line: no branch and no exec-mask region per score (the round-6 form had one around every bucket-gradient
+// store and two around every SLOW mask test, and hipcc then read lse / D / the dropout key from LDS score by score behind a full
+// lgkmcnt(0) each).
+//   * side values: lse and D of the lane's 16 queries are four 16-byte LDS reads each (DkvSide), none of them per score.
+//   * SLOW (masked keys, the causal edge): "dead" <=> c < cdead with one per-lane bound for the sub-tile (dkv_cdead), a select.
+//   * dropout: hw[] holds ONE pair hash per two scores.  A pair hash yields 2 x 16 bits for keys (2m, 2m+1) of one query row, and
+//     lane parity is key parity here (kw0 is a multiple of 32), so lanes 2m and 2m+1 would compute identical words for every row (the
+//     round-6 form did, and used half of each).  Lane parity par instead hashes only the rows c with (c & 1) == par (the key's LDS
+//     address is lane-dependent by one dword, dkv_hashes) and compares BOTH halves of each word with the threshold: A = lanes whose low
+//     half keeps, B = lanes whose high half keeps.  For an even row the word sits in the even lane: key 2m keeps on A's bit 2m, key
+//     2m+1 on B's bit 2m; for an odd row the word sits in the odd lane.  The two 64-bit lane masks are recombined on the scalar unit
+//     and feed the selects directly: the exchange between the lanes of a pair costs no vector instruction.  Same hash, same half, same
+//     comparison as drop_pair_bits_pc + ">= thresh" per score: identical keep decisions element for element.
+constexpr unsigned long long EVEN_LANES = 0x5555555555555555ull, ODD_LANES = 0xAAAAAAAAAAAAAAAAull;
+template <bool BIASV, bool SLOW, bool DROP>
+__device__ __forceinline__ void dkv_sub(const f32x16& s, const f32x16& dp, bf16x8 (&pf)[2], bf16x8 (&df)[2], const DkvSide<!BIASV>& sd, const unsigned int (&hw)[8],
+                                        const unsigned int (&braw)[16], int cdead, float sc2, unsigned int thresh, float inv_keep) {
+#pragma unroll
+  for (int g = 0; g < 4; ++g) {
+    const f32x4 lse4 = sd.lse4(g), d4 = sd.d4(g);
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const int pr = 2 * g + j;
+      bool keep2[2] = {true, true};
+      if (DROP) {
+        const unsigned long long ka = __ballot((hw[pr] & 0xffffu) >= thresh), kb = __ballot((hw[pr] >> 16) >= thresh);
+        keep2[0] = __builtin_amdgcn_inverse_ballot_w64((ka & EVEN_LANES) | ((kb & EVEN_LANES) << 1));
+        keep2[1] = __builtin_amdgcn_inverse_ballot_w64((kb & ODD_LANES) | ((ka & ODD_LANES) >> 1));
+      }
+      f32x2_t pv2, ds2;
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int r = 2 * pr + e;
+        const int c = (r & 3) + 8 * g;
+        const float bv = BIASV ? __uint_as_float(braw[r]) : 0.f;
+        const float x = fmaf(s[r], sc2, bv);
+        float p = fast_exp2(x - lse4[r & 3]);
+        if (SLOW) p = c < cdead ? 0.f : p;
+        float dpv = dp[r], pv = p;
+        if (DROP) {
+          pv = keep2[e] ? p * inv_keep : 0.f;
+          dpv = keep2[e] ? dpv * inv_keep : 0.f;
+        }
+        pv2[e] = pv;
+        ds2[e] = p * (dpv - d4[r & 3]);
+      }
+      // (bf16 at once, as pack8 does: the fp32 values die here.  Element r of the sub-tile is half r & 1 of dword (r & 7) >> 1 of [r >> 3].)
+      const bf16x2_t pq = __builtin_convertvector(pv2, bf16x2_t), dq_ = __builtin_convertvector(ds2, bf16x2_t);
+      pf[pr >> 2][2 * (pr & 3)] = pq[0]; pf[pr >> 2][2 * (pr & 3) + 1] = pq[1];
+      df[pr >> 2][2 * (pr & 3)] = dq_[0]; df[pr >> 2][2 * (pr & 3) + 1] = dq_[1];
     }
+  }
+}
+// SLOW's per-lane bound: element c of the sub-tile is dead (p = 0) <=> the key is masked, or causal and key > query + (S - T)
+// <=> c < cdead.  (c <= 27.)
+__device__ __forceinline__ int dkv_cdead(bool kmasked, int causal, int ki, int q0, int st) {
+  return kmasked ? 32 : (causal ? ki - st - q0 : 0);
+}
+// the sub-tile's eight pair hashes of this lane: rows c = 8g + 2j + par, par = key parity = lane parity
+__device__ __forceinline__ void dkv_hashes(unsigned int (&hw)[8], const unsigned int* keyv_par, int qbase, unsigned int pcl) {
+#pragma unroll
+  for (int pr = 0; pr < 8; ++pr) hw[pr] = drop_pair_bits_pc(keyv_par[qbase + 8 * (pr >> 1) + 2 * (pr & 1)], pcl);
+}
+
+// The sub-tile's unclipped bucket gradients dQP[q][q - key + maxrel] (consecutive lanes = consecutive keys = consecutive buckets,
+// descending: coalesced), from the bf16 halves the dK MFMA consumes (one conversion per dS value).  Buffer stores through a descriptor
+// over this (batch, head)'s [T][nb] block: element r sits c * (nb + 1) elements behind the lane's first one, so an address is one
+// per-lane byte offset per sub-tile plus a wave-uniform one per element.
+//   INTERIOR (every store of the sub-tile is wanted: band fully inside (0, nb - 1), 32 valid keys, 32 queries < T; wave-uniform test
+//   at the caller): the uniform part rides in the scalar offset, a store costs no vector instruction beside the half-word shift.
+//   otherwise: the stores that are not wanted (bucket clipped, key >= S, query >= T) get an offset past the descriptor's size, which
+//   the hardware drops; nothing is written that the predicated form did not write.  (The scalar offset is not part of the hardware's
+//   range check, so this form keeps the whole offset in the vector register.)
+template <bool INTERIOR>
+__device__ __forceinline__ void dkv_store_dqp(const bf16x8 (&df)[2], __amdgpu_buffer_rsrc_t rsrc, int voff, int cmin, int cmax, int estride2) {
+#pragma unroll
+  for (int u = 0; u < 2; ++u) {
+    const u32x4 w = __builtin_bit_cast(u32x4, df[u]);
+#pragma unroll
+    for (int j = 0; j < 4; ++j)
+#pragma unroll
+      for (int e = 0; e < 2; ++e) {
+        const int r = 8 * u + 2 * j + e;
+        const int c = (r & 3) + 8 * (r >> 2);
+        const unsigned short h = (unsigned short)(e ? w[j] >> 16 : w[j]);
+        if (INTERIOR) {
+          __builtin_amdgcn_raw_buffer_store_b16(h, rsrc, voff, c * estride2, 0);
+        } else {
+          const bool ok = cmin < c && cmax > c;
+          __builtin_amdgcn_raw_buffer_store_b16(h, rsrc, ok ? voff + c * estride2 : (int)0x80000000, 0, 0);
+        }
+      }
   }
 }
 
@@ -921,11 +996,12 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const BwdArgs a) {
   const float inv_keep = drop ? 1.f / (1.f - a.dropout_p) : 1.f;
   const float sc2 = a.scale * LOG2E;
   const unsigned int pcl = ((unsigned int)(ki & 63) >> 1) * PAIR_MUL;
-  const unsigned int kshift = (ki & 1) ? 16u : 0u;
   const long long bhT = (long long)bh * a.T;
   const int nbp = a.nb + 2 * QP_PAD;
   const bf16_t* qpb = BIAS ? a.qp + bhT * nbp : nullptr;
-  bf16_t* dqpb = BIAS ? a.dqp + bhT * a.nb : nullptr;
+  // this (batch, head)'s [T][nb] block of dQP behind a buffer descriptor (wave-uniform inputs only): dkv_store_dqp
+  __amdgpu_buffer_rsrc_t dqp_rsrc = __builtin_amdgcn_make_buffer_rsrc(BIAS ? a.dqp + bhT * a.nb : a.dqp, 0, BIAS ? a.T * a.nb * 2 : 0, 0x00020000);
+  const int dqp_estride2 = (a.nb + 1) * 2;
   const bf16_t* qbase_g = a.q + (long long)b * a.T * a.q_ld + h * HD;
   const bf16_t* dobase_g = a.dout + (long long)b * a.T * a.do_ld + h * HD;
 
@@ -1046,6 +1122,14 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const BwdArgs a) {
 #pragma unroll
         for (int r = 0; r < 16; ++r) braw[r] = pe_[(r & 3) + 8 * (r >> 2)];
       }
+      const int qs0 = qt * 64 + sub * 32;
+      const int qbase = sub * 32 + 4 * hi, q0 = qs0 + 4 * hi;
+      // the sub-tile's pair hashes and side values: issued in front of the S / dP products, whose matrix time covers the LDS round trips
+      // and the hash arithmetic (they depend on the tile's side array only)
+      unsigned int hw[8];
+      if (DROP) dkv_hashes(hw, keyv + (lane & 1), qbase, pcl);
+      DkvSide<!BIAS> sd;
+      sd.load(stv + qbase);
       f32x16 s, dp;
 #pragma unroll
       for (int r = 0; r < 16; ++r) { s[r] = 0.f; dp[r] = 0.f; }
@@ -1056,8 +1140,6 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const BwdArgs a) {
         s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(qa, kf[ks], s, 0, 0, 0);    // S[q][key]
         dp = __builtin_amdgcn_mfma_f32_32x32x16_bf16(oa, vf[ks], dp, 0, 0, 0);  // dP[q][key]
       }
-      const int qs0 = qt * 64 + sub * 32;
-      const int qbase = sub * 32 + 4 * hi, q0 = qs0 + 4 * hi;
       // window of the NEXT sub-tile: issued once this sub-tile's values are in registers
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       __builtin_amdgcn_sched_barrier(0);
@@ -1068,28 +1150,39 @@ __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const BwdArgs a) {
           if (gmode == 0) kws.issue(qpb, 32 * nn, a.T, nbp, gwbc, a.nb >> 3, scratch);
         }
       }
-      f32x16 pd;
-#define DKV_SUB(BM_, SLOW_, DROP_) \
-  dkv_sub<BM_, SLOW_, DROP_>(s, dp, pd, a, stv, keyv, braw, dqpb, qbase, q0, ki, kvalid, kmasked, sc2, pcl, kshift, thresh, inv_keep)
-#define DKV_DISPATCH(SLOW_, DROP_)                            \
-  do {                                                        \
-    if (bmode == 3) DKV_SUB(0, SLOW_, DROP_);                 \
-    else if (bmode == 0) DKV_SUB(1, SLOW_, DROP_);            \
-    else DKV_SUB(2, SLOW_, DROP_);                            \
-  } while (0)
-      if (slow) DKV_DISPATCH(true, DROP); else DKV_DISPATCH(false, DROP);
-#undef DKV_DISPATCH
-#undef DKV_SUB
+      bf16x8 pf[2], df[2];
+      if (slow) {
+        const int cdead = dkv_cdead(kmasked, a.causal, ki, q0, a.S - a.T);
+        dkv_sub<BIAS, true, DROP>(s, dp, pf, df, sd, hw, braw, cdead, sc2, thresh, inv_keep);
+      } else {
+        dkv_sub<BIAS, false, DROP>(s, dp, pf, df, sd, hw, braw, 0, sc2, thresh, inv_keep);
+      }
       // dV^T[d][key] += dO^T[d][q] . Pd[q][key] ;  dK^T[d][key] += Q^T[d][q] . dS[q][key]
 #pragma unroll
       for (int u = 0; u < 2; ++u) {
         const int s4 = 2 * sub + u;
-        const bf16x8 pf = pack8(pd, 8 * u);
-        const bf16x8 df = pack8(s, 8 * u);
-        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(otl + s4 * 2048, toff[0][0], toff[0][1]), pf, dv0, 0, 0, 0);
-        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(otl + s4 * 2048, toff[1][0], toff[1][1]), pf, dv1, 0, 0, 0);
-        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(qtl + s4 * 2048, toff[0][0], toff[0][1]), df, dk0, 0, 0, 0);
-        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(qtl + s4 * 2048, toff[1][0], toff[1][1]), df, dk1, 0, 0, 0);
+        dv0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(otl + s4 * 2048, toff[0][0], toff[0][1]), pf[u], dv0, 0, 0, 0);
+        dv1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(otl + s4 * 2048, toff[1][0], toff[1][1]), pf[u], dv1, 0, 0, 0);
+        dk0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(qtl + s4 * 2048, toff[0][0], toff[0][1]), df[u], dk0, 0, 0, 0);
+        dk1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(tr_frag(qtl + s4 * 2048, toff[1][0], toff[1][1]), df[u], dk1, 0, 0, 0);
+        // The bucket-gradient stores go BEHIND the first half's transposed reads: hipcc puts an s_waitcnt vmcnt(0) in front of the first
+        // ds_read of this block (it cannot tell the tiles from the LDS-DMA targets in flight), and stores issued in front of it were waited
+        // out there, a full write round trip per window sub-tile; here the second half's reads and eight MFMAs cover them.
+        if (u == 0 && BIAS && bmode == 0 && FA2_ABL != 3) {   // the window sub-tiles own the unclipped bucket gradients (the clipped ends are the dq kernel's)
+          const int bk0 = q0 - ki + a.maxrel;                   // unclamped bucket of element c = 0
+          int voff = (q0 * a.nb + bk0) * 2;
+          int estride2 = dqp_estride2;
+          // opaque: hipcc otherwise re-associates the lane's offset with the element offsets into 16 loop-invariant VGPRs, and keeps the 16
+          // element offsets in SGPRs for the whole kernel (both spilled); one scalar multiply per store instead
+          asm volatile("" : "+v"(voff), "+s"(estride2));
+          const int bmin = qs0 - (kw0 + 31) + a.maxrel, bmax = qs0 + 31 - kw0 + a.maxrel;
+          if (bmin > 0 && bmax < a.nb - 1 && kw0 + 31 < a.S && qs0 + 31 < a.T) {
+            dkv_store_dqp<true>(df, dqp_rsrc, voff, 0, 0, estride2);
+          } else {   // wanted: key < S, 0 < bk0 + c < nb - 1, q0 + c < T
+            const int cmax = a.nb - 1 - bk0 < a.T - q0 ? a.nb - 1 - bk0 : a.T - q0;
+            dkv_store_dqp<false>(df, dqp_rsrc, voff, kvalid ? -bk0 : 32, cmax, estride2);
+          }
+        }
       }
     }
     if (qt + 1 < nqt) side_store(smem + ((qt + 1) & 1) * QBUF_B);
