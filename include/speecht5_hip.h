@@ -391,6 +391,22 @@ int st5_pad_time_act(const void* src, void* dst, int32_t B, int32_t T, int32_t C
 /* Zero the halo rows [0, pad_l) and [pad_l + T, pad_l + T + pad_r) of every batch element of dst [B, pad_l + T + pad_r, C]: a
  * convolution whose st5_gemm output operand addresses the interior of the padded buffer the NEXT convolution reads. */
 int st5_zero_halo(void* dst, int32_t B, int32_t T, int32_t C, int32_t pad_l, int32_t pad_r, int dtype, void* stream);
+/* ---- ragged (packed) batches of the text-to-waveform path (csrc/ragged.hip; speecht5_amd/ragged.py builds the tables once per
+ *      call): B utterances lie one after another along time, each followed by a gap of G mel frames; at a stage of cumulative
+ *      upsampling rate s mel frame f covers rows [s*f, s*(f+1)).  valid: one byte per mel frame (1 inside an utterance, 0 in a gap).
+ *      st5_ragged_pad_act: st5_pad_time_act for one packed sequence, dst [pad_l + frames*s + pad_r, C] row t' =
+ *      act(src[t' - pad_l]) where valid[(t' - pad_l) / s], else 0 -- a select, so whatever lies in a gap row of src never reaches
+ *      dst.  st5_ragged_zero_gaps: rows [s*f, s*(f+1)) of buf [frames*s, C] := 0 for the n_gap frames listed in gap_frames (work
+ *      proportional to the gaps; a listed frame that is out of range or marked valid is skipped, so a valid row is never written):
+ *      for buffers a convolution's or the BatchNorm kernel's epilogue wrote.  st5_ragged_gather_rows: dst[u, 0:w] =
+ *      src[idx[u], 0:w], or 0 when idx[u] is outside [0, src_rows); fp32 -> `dtype` (to_f32 = 0: packing fp32 records, gap rows
+ *      zero) or `dtype` -> fp32 (to_f32 = 1: unpacking the packed waveform / mel into per-row results). */
+int st5_ragged_pad_act(const void* src, void* dst, const uint8_t* valid, int64_t frames, int32_t s, int32_t C, int32_t pad_l,
+                       int32_t pad_r, int32_t act, int dtype, void* stream);
+int st5_ragged_zero_gaps(void* buf, const uint8_t* valid, const int32_t* gap_frames, int64_t n_gap, int64_t frames, int32_t s,
+                         int32_t C, int dtype, void* stream);
+int st5_ragged_gather_rows(const void* src, const int32_t* idx, void* dst, int64_t n_rows, int64_t src_rows, int32_t w,
+                           int32_t to_f32, int dtype, void* stream);
 /* Channels-last Conv1d with 32 or 64 OUTPUT channels, bf16, as an MFMA implicit GEMM whose 32 MFMA rows are the output channels and
  * whose columns are time steps (csrc/conv1d_narrow.hip) -- the 64- and 32-channel stages of the HiFi-GAN generator (HF
  * modeling_speecht5.py:2920-2960 residual blocks, :3010-3030 upsampler), where the 128-wide tiles of st5_gemm waste 1/2 .. 3/4 of

@@ -2978,6 +2978,51 @@ def postnet(before, blocks, training, dropout_p):
     return PostnetFunction.apply(before, (bool(training), float(dropout_p), cfg), bufs, *params)
 
 
+@torch.no_grad()
+def postnet_ragged(before, blocks, lay):
+    """The post-net over ONE packed sequence (speecht5_amd/ragged.py), inference only.  before [lay.T, odim] in the compute dtype
+    with zero gap rows; blocks as in `postnet`; lay.gap >= (k - 1) // 2.  Returns after fp32 [lay.T, odim] = before +
+    postnet(before) in the valid rows (the gap rows hold BatchNorm's shift and are never read).  Running statistics only: no
+    buffer is updated and no dropout drawn; a BatchNorm in training mode raises, since batch statistics would couple the rows.
+    Each layer is PostnetFunction.forward's convolution GEMM and BatchNorm + tanh kernel with B = 1; BatchNorm's shift makes the
+    gap rows non-zero, so they are zeroed again (st5_ragged_zero_gaps, work proportional to the gaps) before the next convolution
+    reads them."""
+    if any(blk[1].training for blk in blocks):
+        raise RuntimeError("postnet_ragged runs on running statistics: put the post-net's BatchNorm layers in eval mode")
+    dtype, dev = before.dtype, before.device
+    T, odim = before.shape
+    assert T == lay.T and before.is_contiguous()
+    L = hip.lib()
+    n = len(blocks)
+    pad = (blocks[0][0].weight.shape[2] - 1) // 2
+    assert lay.gap >= pad, (lay.gap, pad)
+    xp = torch.empty(1, T + 2 * pad, odim, dtype=dtype, device=dev)
+    hip.check(L.st5_pad_time(before.data_ptr(), xp.data_ptr(), 1, T, odim, pad, pad, _dt(dtype), hip.stream()), "st5_pad_time")
+    after = None
+    for i, blk in enumerate(blocks):
+        conv, bn = blk[0], blk[1]
+        w = conv.weight
+        Cout, Cin, k = w.shape
+        assert (k - 1) // 2 == pad and Cout % 4 == 0
+        x32 = torch.empty(T, Cout, dtype=torch.float32, device=dev)
+        hip.gemm(hip.operand(xp, Cin, rpb=T, bstride=(T + 2 * pad) * Cin), hip.operand(_conv_w_fwd(w, dtype), k * Cin), hip.operand(x32, Cout),
+                 T, Cout, k * Cin, _dt(dtype), flags=hip.OUT_F32)
+        stats = torch.empty(2 * Cout, dtype=torch.float32, device=dev)
+        ws = hip.workspace(L.st5_batchnorm_ws_bytes(Cout), dev)
+        args = (x32.data_ptr(), bn.weight.data_ptr(), bn.bias.data_ptr(), hip.ptr(bn.running_mean), hip.ptr(bn.running_var), 0, 0.0,
+                float(bn.eps), 0)
+        if i == n - 1:
+            after = torch.empty(T, Cout, dtype=torch.float32, device=dev)
+            hip.check(L.st5_batchnorm_act_fwd(*args, ACT_NONE, 0.0, 0, before.data_ptr(), after.data_ptr(), 1, stats.data_ptr(), ws.data_ptr(),
+                                              T, Cout, 0, 0, 0, 0, _dt(dtype), hip.stream()), "st5_batchnorm_act_fwd")
+        else:
+            nxt = torch.empty(1, T + 2 * pad, Cout, dtype=dtype, device=dev)
+            hip.check(L.st5_batchnorm_act_fwd(*args, ACT_TANH, 0.0, 0, 0, nxt.data_ptr(), 0, stats.data_ptr(), ws.data_ptr(), T, Cout, T,
+                                              (T + 2 * pad) * Cout, pad * Cout, pad, _dt(dtype), hip.stream()), "st5_batchnorm_act_fwd")
+            xp = lay.zero_gaps(nxt, 1, Cout, row0=pad)
+    return after
+
+
 # -------------------------------------------------------------------------------------------------
 # Shallow-fusion LM decoding (csrc/lm_decode.hip): slot-cache attention over an ancestry table, the table's beam reorder, and the
 # fused LM score of beam search (sequence_generator.py:420-425).  Inference only, no autograd.

@@ -18,6 +18,7 @@ import torch.nn as nn
 
 from . import functional as Fn
 from . import hip
+from . import ragged
 
 
 class HifiGanResidualBlock(nn.Module):
@@ -32,9 +33,12 @@ class HifiGanResidualBlock(nn.Module):
                                      for _ in dilation])
 
 
-def _pad_act(x, pl, pr, act=hip.ACT_NONE):
+def _pad_act(x, pl, pr, act=hip.ACT_NONE, lay=None, rate=1):
     """[B, L, C] -> zero-padded act(x) [B, pl + L + pr, C] in one pass (every convolution of the generator reads LeakyReLU of
-    its input, zero "same"-padded: the activation and the halo are made together)."""
+    its input, zero "same"-padded: the activation and the halo are made together).  lay (a ragged.PackedLayout, B = 1): the gap
+    rows of the packed sequence at upsampling rate `rate` come out zero too, in the same pass."""
+    if lay is not None:
+        return lay.pad_act(x, rate, pl, pr, act)
     B, L, C = x.shape
     out = torch.empty(B, L + pl + pr, C, dtype=x.dtype, device=x.device)
     hip.check(hip.lib().st5_pad_time_act(x.data_ptr(), out.data_ptr(), B, L, C, pl, pr, act, hip.dt(x), hip.stream()), "st5_pad_time_act")
@@ -51,11 +55,19 @@ def conv_pad(conv):
     return (k * d - d) // 2
 
 
-def conv1d(xp, L, conv, *, alpha=1.0, act=hip.ACT_NONE, residual=None, out=None, beta=0.0, out_pad=0):
+def conv1d(xp, L, conv, *, alpha=1.0, act=hip.ACT_NONE, residual=None, out=None, beta=0.0, out_pad=0, lay=None, rate=1):
     """Channels-last dilated 'same' Conv1d as an implicit GEMM (K segmented per tap: seg = Cin, seg_stride = dilation * Cin) over
     the PADDED input xp [B, L + 2 * conv_pad(conv), Cin]:  y = act(alpha * conv(x) + bias) + residual + beta * out.
     out_pad > 0: y is written into the interior of a fresh [B, L + 2 * out_pad, Cout] buffer with zeroed halo rows -- the layout
-    the next convolution reads, no copy in between -- and that buffer is returned."""
+    the next convolution reads, no copy in between -- and that buffer is returned.  lay (a ragged.PackedLayout) with out_pad: the
+    gap rows of that buffer are zeroed after the convolution wrote them (bias and activation make them non-zero)."""
+    y = _conv1d(xp, L, conv, alpha, act, residual, out, beta, out_pad)
+    if lay is not None and out_pad:
+        lay.zero_gaps(y, rate, conv.weight.shape[0], row0=out_pad)
+    return y
+
+
+def _conv1d(xp, L, conv, alpha, act, residual, out, beta, out_pad):
     B, Lp, Cin = xp.shape
     Cout, _, k = conv.weight.shape
     d = conv.dilation[0]
@@ -152,6 +164,13 @@ class SpeechT5HifiGan(nn.Module):
         is_batched = spectrogram.dim() == 3
         x = spectrogram if is_batched else spectrogram.unsqueeze(0)
         x = Fn.to_compute(x.float().contiguous())
+        wav = Fn.to_float(self._generate(x)).view(x.shape[0], -1)
+        return wav if is_batched else wav.view(-1)
+
+    def _generate(self, x, lay=None):
+        """The layer walk: x [B, L, model_in_dim] (compute dtype) -> [B, prod(rates) * L, 1].  lay = None: B independent rows of
+        equal length.  lay = a ragged.PackedLayout (B = 1, L = lay.T): one packed sequence; the same launches, with the pad +
+        activation pass selecting the gap rows to zero and the out_pad hand-over followed by a gap-zeroing pass."""
         B, L, C = x.shape
         if self.normalize_before:
             a = (1.0 / self.scale).float().contiguous()
@@ -160,12 +179,14 @@ class SpeechT5HifiGan(nn.Module):
             hip.check(hip.lib().st5_channel_affine(x.data_ptr(), a.data_ptr(), b.data_ptr(), y.data_ptr(), B * L, C, hip.ACT_NONE,
                                                    hip.dt(x), hip.stream()), "st5_channel_affine")
             x = y
-        h = conv1d(_pad_act(x, 3, 3), L, self.conv_pre)
+        rate = 1
+        h = conv1d(_pad_act(x, 3, 3, lay=lay, rate=rate), L, self.conv_pre)
         alpha = 1.0
         LR = hip.ACT_LRELU_01
         for i in range(self.num_upsamples):
-            h = conv_transpose1d(_pad_act(h, 1, 1, LR), L, self.upsampler[i], alpha=alpha)
+            h = conv_transpose1d(_pad_act(h, 1, 1, LR, lay=lay, rate=rate), L, self.upsampler[i], alpha=alpha)
             L = h.shape[1]
+            rate *= self.upsampler[i].stride[0]
             acc = None
             for j in range(self.num_kernels):
                 blk = self.resblocks[i * self.num_kernels + j]
@@ -174,7 +195,8 @@ class SpeechT5HifiGan(nn.Module):
                 for q, (c1, c2) in enumerate(zip(blk.convs1, blk.convs2)):
                     # r -> [LeakyReLU + halo, one pass] -> c1 (+ LeakyReLU in its epilogue, written straight into c2's padded
                     # input) -> c2 (+ r in its epilogue): 7 passes over the activation per pair (round 2: 11)
-                    t = conv1d(_pad_act(r, conv_pad(c1), conv_pad(c1), LR), L, c1, act=LR, out_pad=conv_pad(c2))
+                    t = conv1d(_pad_act(r, conv_pad(c1), conv_pad(c1), LR, lay=lay, rate=rate), L, c1, act=LR, out_pad=conv_pad(c2),
+                               lay=lay, rate=rate)
                     if q == n - 1:   # last pair: accumulate the block output into the running sum of the resblocks
                         if acc is None:
                             acc = conv1d(t, L, c2, residual=r)
@@ -184,6 +206,80 @@ class SpeechT5HifiGan(nn.Module):
                         r = conv1d(t, L, c2, residual=r)
             h = acc
             alpha = 1.0 / self.num_kernels  # mean over resblocks, applied by the next convolution
-        w = conv1d(_pad_act(h, 3, 3, hip.ACT_LRELU_001), L, self.conv_post, alpha=alpha, act=hip.ACT_TANH)  # [B, L_out, 1]
-        wav = Fn.to_float(w).view(B, -1)
-        return wav if is_batched else wav.view(-1)
+        return conv1d(_pad_act(h, 3, 3, hip.ACT_LRELU_001, lay=lay, rate=rate), L, self.conv_post, alpha=alpha, act=hip.ACT_TANH)  # [B, L_out, 1]
+
+    # ---- ragged batches: B rows of different lengths in one packed sequence (speecht5_amd/ragged.py) ----
+    # Default chunk cap.  The largest stage holds E = max over the stages of (rate * channels) elements per mel frame (the last
+    # one at full size: 256 * 32 = 8192).  Inside a resblock pair six buffers of that stage are alive at once: the upsampler output
+    # h (the first pair's residual), the running sum acc, the residual r, its padded LeakyReLU, the hand-over buffer t and the
+    # pair's output.  RAGGED_BYTE_BUDGET bounds those six:  max_frames = budget / (6 * E * element size), 5461 mel frames in
+    # fp32 and 10922 in bf16 at full size (63 s / 127 s of audio at 16 kHz, hop 256).
+    RAGGED_BYTE_BUDGET = 1 << 30
+    RAGGED_LIVE_BUFFERS = 6
+
+    def _ragged_meta(self):
+        """(gap, elements per mel frame of the widest stage, prod(rates)), read from the module once: kernel sizes, dilations,
+        strides and channel counts are fixed at construction."""
+        meta = self.__dict__.get("_ragged_meta_cache")
+        if meta is None:
+            rate, elems = 1, self.conv_pre.weight.shape[0]
+            for up in self.upsampler:
+                rate *= up.stride[0]
+                elems = max(elems, rate * up.weight.shape[1])
+            meta = self.__dict__["_ragged_meta_cache"] = (ragged.hifigan_gap(self), elems, rate)
+        return meta
+
+    def frame_elems(self):
+        """Elements per mel frame of the widest stage."""
+        return self._ragged_meta()[1]
+
+    def default_max_frames(self, dtype=None):
+        esz = 2 if (dtype or Fn.compute_dtype()) == torch.bfloat16 else 4
+        return max(1, self.RAGGED_BYTE_BUDGET // (self.RAGGED_LIVE_BUFFERS * self.frame_elems() * esz))
+
+    def frame_limit(self):
+        """Hard limit of one packed sequence: every buffer of it stays below 2^31 BYTES in fp32 (halo rows included), so the 32-bit
+        row and element counts of the kernels on the path (st5_gemm with rpb, st5_conv1d_narrow, st5_conv1d_cout1,
+        st5_batchnorm_act_fwd) hold whatever their offset types are."""
+        return ((1 << 31) - 1) // (4 * self.frame_elems()) - 64
+
+    def ragged_gap(self):
+        """G of the gap rule (speecht5_amd/ragged.py) for this generator: 7 at full size."""
+        return self._ragged_meta()[0]
+
+    def _packed_rate(self):
+        return self._ragged_meta()[2]
+
+    def forward_packed(self, x, lay):
+        """x [lay.T, model_in_dim] in the compute dtype (gap rows may hold anything) -> packed waveform [lay.T * prod(rates)] in the
+        compute dtype (gap rows hold anything).  lay.gap must be at least ragged_gap()."""
+        assert lay.gap >= self.ragged_gap(), (lay.gap, self.ragged_gap())
+        if lay.T > self.frame_limit():
+            raise ValueError(f"a packed sequence of {lay.T} mel frames exceeds the limit of {self.frame_limit()}")
+        return self._generate(x.view(1, lay.T, -1), lay).view(-1)
+
+    @torch.no_grad()
+    def forward_ragged(self, mels, max_frames=None, lengths=None):
+        """B log-mel rows of different lengths -> B one-dimensional fp32 waveforms of prod(rates) * L_b samples, each equal to
+        forward(mel_b) of that row alone.  `mels`: a list of [L_b, 80] tensors, or a padded [B, L_max, 80] tensor with `lengths`;
+        L_b >= 1.  Rows are packed in order into chunks of at most `max_frames` mel frames, gaps included (default: see
+        RAGGED_BYTE_BUDGET); a longer row gets a chunk of its own, and a chunk of one row is the single-row call."""
+        rows_in = ragged.Rows(mels, lengths)
+        lengths = rows_in.lengths
+        gap = self.ragged_gap()
+        if max_frames is None:
+            max_frames = self.default_max_frames()
+        max_frames = min(int(max_frames), self.frame_limit())
+        S = self._packed_rate()
+        out = [None] * len(lengths)
+        for rows in ragged.plan_chunks(lengths, gap, max_frames):
+            if len(rows) == 1:       # a row alone in its chunk has no neighbour to be kept apart from: the single-row call itself
+                out[rows[0]] = self.forward(rows_in.row(rows[0]))
+                continue
+            src, Lmax = rows_in.source()
+            lay = ragged.PackedLayout([lengths[b] for b in rows], gap, [b * Lmax for b in rows], src.device)
+            w = self.forward_packed(lay.pack_rows(src, Fn.compute_dtype()), lay)
+            _, per_row = lay.unpack_rows(w, S)
+            for b, wav in zip(rows, per_row):
+                out[b] = wav.reshape(-1)
+        return out

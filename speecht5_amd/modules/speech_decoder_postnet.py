@@ -32,6 +32,31 @@ class Postnet(nn.Module):
         training = self.postnet[0][1].training
         return Fn.postnet(x, self.postnet, training, self.dropout_rate if self.training else 0.0)
 
+    @torch.no_grad()
+    def forward_ragged(self, mels, max_frames=None, lengths=None):
+        """B `before` rows of different lengths (a list of [L_b, odim] tensors, or a padded [B, L_max, odim] tensor with `lengths`)
+        -> B `after` rows, fp32 [L_b, odim], each what forward gives for that row alone in eval mode.  One packed sequence per
+        chunk of at most `max_frames` mel frames (speecht5_amd/ragged.py), a chunk of one row being the single-row call; inference
+        only (Fn.postnet_ragged)."""
+        from .. import ragged
+        rows_in = ragged.Rows(mels, lengths)
+        lengths = rows_in.lengths
+        gap = ragged.postnet_gap(self)
+        out = [None] * len(lengths)
+        for rows in ragged.plan_chunks(lengths, gap, max_frames):
+            if len(rows) == 1:       # a row alone in its chunk: the single-row call itself (on running statistics, like the packed path)
+                if any(blk[1].training for blk in self.postnet):
+                    raise RuntimeError("forward_ragged runs on running statistics: put the post-net's BatchNorm layers in eval mode")
+                out[rows[0]] = Fn.postnet(Fn.to_compute(rows_in.row(rows[0]).float().unsqueeze(0)), self.postnet, False, 0.0).squeeze(0)
+                continue
+            src, Lmax = rows_in.source()
+            lay = ragged.PackedLayout([lengths[b] for b in rows], gap, [b * Lmax for b in rows], src.device)
+            after = Fn.postnet_ragged(lay.pack_rows(src, Fn.compute_dtype()), self.postnet, lay)
+            _, per_row = lay.unpack_rows(after, after.shape[1])
+            for b, m in zip(rows, per_row):
+                out[b] = m
+        return out
+
 
 class SpeechDecoderPostnet(nn.Module):
     def __init__(self, odim, args):

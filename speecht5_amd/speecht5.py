@@ -489,13 +489,9 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         mask = torch.arange(S, device=x.device)[None, :] >= torch.tensor(T, device=x.device)[:, None]
         return {"encoder_out": [x], "encoder_padding_mask": [mask]}, T
 
-    @torch.no_grad()
-    def generate_speech_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, need_attn=True, **kwargs):
-        """generate_speech for B utterances in one decode loop.  Returns B tuples (mel [L_b, odim], probs [L_b], attn
-        [decoder_layers, H, L_b / r, S_b] or None) in row order, each as generate_speech returns it for that row alone.  Text rows
-        are right-padded (TextToSpeechCollater); speech rows come with `padding_mask`.  Row b stops at the first step idx >= minlen_b
-        at which one of its r stop probabilities reaches `threshold` or idx >= maxlen_b; rows that stopped keep computing (their
-        records are final) until the host sees no active row, every TTS_POLL_STEPS steps."""
+    def _decode_rows(self, source, src_tokens, spkembs, padding_mask, need_attn, **kwargs):
+        """The decode loop of generate_speech_batch / synthesize_batch: (mel_rec fp32 [B, cap * r, odim], prob_rec fp32 [B, cap * r],
+        rec = the attention record [B, layers, H, cap, S] or None, steps per row as a host list, encoder lengths T_b)."""
         assert source is not None or src_tokens is not None
         encoder_out, T_in = self._encode_rows(source, src_tokens, padding_mask)
         r = self.reduction_factor
@@ -540,14 +536,63 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
                 self.tts_polls += 1
                 if int(host[0]) == 0:
                     break
-        L = steps.tolist()
+        return mel_rec, prob_rec, rec, steps.tolist(), T_in
+
+    @torch.no_grad()
+    def generate_speech_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, need_attn=True, **kwargs):
+        """generate_speech for B utterances in one decode loop.  Returns B tuples (mel [L_b, odim], probs [L_b], attn
+        [decoder_layers, H, L_b / r, S_b] or None) in row order, each as generate_speech returns it for that row alone.  Text rows
+        are right-padded (TextToSpeechCollater); speech rows come with `padding_mask`.  Row b stops at the first step idx >= minlen_b
+        at which one of its r stop probabilities reaches `threshold` or idx >= maxlen_b; rows that stopped keep computing (their
+        records are final) until the host sees no active row, every TTS_POLL_STEPS steps."""
+        mel_rec, prob_rec, rec, L, T_in = self._decode_rows(source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
+        post, r = self.speech_decoder_postnet, self.reduction_factor
         out = []
-        for b in range(B):
+        for b in range(len(L)):
             mel = mel_rec[b, :L[b] * r].unsqueeze(0)
             if post.postnet is not None:
                 mel = post.postnet(Fn.as_compute(mel.contiguous()))
             attn = rec[b, :, :, :L[b], :T_in[b]].contiguous() if rec is not None else None
             out.append((mel.squeeze(0), prob_rec[b, :L[b] * r].clone(), attn))
+        return out
+
+    @torch.no_grad()
+    def synthesize_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, vocoder=None, need_attn=False,
+                         max_frames=None, **kwargs):
+        """B texts (or B source clips) in, B waveforms out: the decode loop of generate_speech_batch, then the mel post-net and the
+        HiFi-GAN `vocoder` over packed sequences (speecht5_amd/ragged.py) instead of once per row.  Returns B tuples (wav fp32
+        [hop * L_b] or None without a vocoder, mel [L_b, odim], probs [L_b], attn or None), each row what generate_speech, the
+        post-net and vocoder.forward give for that row alone.  The mel records are packed on the device straight from the decode
+        loop's record; one layout (the vocoder's gap when there is one) serves the post-net and the vocoder.  Rows go in order into
+        chunks of at most `max_frames` mel frames (default: the vocoder's byte budget)."""
+        from . import ragged
+        mel_rec, prob_rec, rec, steps, T_in = self._decode_rows(source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
+        post, r = self.speech_decoder_postnet, self.reduction_factor
+        B, rows_per, odim = mel_rec.shape
+        lengths = [n * r for n in steps]
+        gap = max(ragged.postnet_gap(post.postnet) if post.postnet is not None else 0, vocoder.ragged_gap() if vocoder is not None else 0)
+        if vocoder is not None:
+            max_frames = min(vocoder.default_max_frames() if max_frames is None else int(max_frames), vocoder.frame_limit())
+            hop = vocoder._packed_rate()
+        src = mel_rec.view(B * rows_per, odim)
+        wavs, mels = [None] * B, [None] * B
+        for rows in ragged.plan_chunks(lengths, gap, max_frames):
+            lay = ragged.PackedLayout([lengths[b] for b in rows], gap, [b * rows_per for b in rows], src.device)
+            if post.postnet is not None:
+                after = Fn.postnet_ragged(lay.pack_rows(src, Fn.compute_dtype()), post.postnet.postnet, lay)   # fp32 [T, odim]
+            else:
+                after = lay.pack_rows(src, torch.float32)
+            _, per_row = lay.unpack_rows(after, odim)
+            for b, m in zip(rows, per_row):
+                mels[b] = m
+            if vocoder is not None:
+                _, per_row = lay.unpack_rows(vocoder.forward_packed(Fn.to_compute(after), lay), hop)
+                for b, w in zip(rows, per_row):
+                    wavs[b] = w.reshape(-1)
+        out = []
+        for b in range(B):
+            attn = rec[b, :, :, :steps[b], :T_in[b]].contiguous() if rec is not None else None
+            out.append((wavs[b], mels[b], prob_rec[b, :lengths[b]].clone(), attn))
         return out
 
     # ---- checkpoint compatibility (speecht5.py:1022-1058): non-strict per-submodule load ----

@@ -283,6 +283,14 @@ class SpeechT5Task(LegacyFairseqTask):
             encoder_input.update(kwargs)
             return models[0].generate_speech_batch(**encoder_input)
 
+    def synthesize_batch(self, models, net_input, vocoder=None, **kwargs):
+        """Text (or speech) to waveform for a whole collated batch (T5TransformerModel.synthesize_batch): one (wav, mel, probs, attn)
+        per row; wav is None without a vocoder."""
+        with torch.no_grad():
+            encoder_input = {k: v for k, v in net_input.items() if k != "prev_output_tokens" and k != "task_name"}
+            encoder_input.update(kwargs)
+            return models[0].synthesize_batch(vocoder=vocoder, **encoder_input)
+
     @property
     def source_dictionary(self):
         return None
