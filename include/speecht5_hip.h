@@ -300,6 +300,16 @@ int st5_conv0_gn_gelu_fwd_m(const float* wav, const float* w, const float* gamma
 int st5_conv0_gn_gelu_bwd_m(const float* wav, const float* w, const float* gamma, const float* beta, const float* stats, const double* mom,
                             const void* dY, float* dw, float* dgamma, float* dbeta, void* ws, int32_t B, int32_t S, int32_t C, int32_t k,
                             int32_t stride, float gscale, int dtype, void* stream);
+/* The forward with PER-ROW LENGTHS (inference: no moments published, no backward).  `lens` int32 [B] on the device, in samples, of a
+ * right-padded batch wav [B,S].  Row b's GroupNorm statistics are taken over its own L_b = (lens[b] - k) / stride + 1 frames; output
+ * frames t >= L_b are stored as zeros.  `stats` [b] and the output frames t < L_b are the bits st5_conv0_gn_gelu_fwd gives for the
+ * single-row call on wav[b, :lens[b]], in every fold / mfma setting (the fold groups the chunk partials by chunk parity and adds each
+ * group in index order, whatever the launch-wide chunk count; the chunks past a row's end contribute + 0.0).  Lengths outside
+ * [k, S] are clamped into the launch's frame range (a row shorter than k gets L_b = 0: all-zero output, undefined statistics); the
+ * caller validates them. */
+int st5_conv0_gn_gelu_fwd_rows(const float* wav, const int32_t* lens, const float* w, const float* gamma, const float* beta, void* out,
+                               float* stats, void* ws, int32_t B, int32_t S, int32_t C, int32_t k, int32_t stride, float eps, int dtype,
+                               void* stream);
 /* A/B switch of the bf16 forward apply pass: 1 (default) = convolution on the matrix cores with split-bf16 operands (x = xh + xl,
  * w = wh + wl; wh.xh + wh.xl + wl.xh in two v_mfma_f32_32x32x16_bf16 per 32 channels x 32 steps), 0 = the VALU form. */
 int st5_conv0_set_mfma(int on);

@@ -26,6 +26,13 @@ constexpr int MAXK = 16;   // max kernel width held in registers
 constexpr int MAXMOM = MAXK + MAXK * (MAXK + 1) / 2;
 
 __host__ __device__ inline int out_len(int S, int k, int stride) { return S < k ? 0 : (S - k) / stride + 1; }
+// Per-row lengths (the *_rows forward, inference): row b of a right-padded batch holds lens[b] samples and owns the first
+// row_len(...) of the launch-wide L output frames -- what the single-row call on wav[b, :lens[b]] would produce.  (A length outside
+// [0, S] is clamped into the launch's frame range: no kernel indexes by it unclamped.)
+__device__ __forceinline__ int row_len(const int* __restrict__ lens, int b, int k, int stride, int L) {
+  const int n = lens[b];
+  return max(0, min(n < k ? 0 : (n - k) / stride + 1, L));
+}
 __host__ __device__ inline int nmom(int k) { return k + k * (k + 1) / 2; }
 // index of R_{j,j'} (j <= j') inside the moment vector (after the k first-order moments)
 __host__ __device__ inline int ridx(int k, int j, int jp) { return k + j * k - j * (j - 1) / 2 + (jp - j); }
@@ -81,18 +88,24 @@ __device__ __forceinline__ void stage_wav(float* seg, const float* __restrict__ 
 // conv0_stats2_kernel: every block of (64 channels, clip) first folds the clip's chunk partials in fp64 (fixed order), block 0 of a
 // clip also publishes them (the backward's final kernel reads them), then 64 threads evaluate mean / rstd of their channels.
 constexpr int TCM = 1024;
-template <int KW>
-__global__ __launch_bounds__(256) void conv0_moments2_kernel(const float* __restrict__ wav, float* __restrict__ part, int S, int L, int k,
-                                                             int stride, int nchm) {
+// ROWS: the row's own frame count bounds the chunk; a chunk that lies wholly past it stages nothing, accumulates nothing and WRITES ZERO
+// partials.  What makes the row's folded moments the bits of the single-row call (whose chunks are exactly this row's non-empty ones,
+// with the same nt): fold_chunk_moments assigns a chunk to one of its two lane groups BY THE CHUNK'S PARITY and adds each group's
+// chunks in index order, then ps[0] + ps[1] -- a grouping and an order that do not depend on the launch-wide chunk count nchm.  The
+// chunks past the row's end only append `+ 0.0` to each group's sum, and x + 0.0 == x.  (A fold that split the chunks by halves of
+// nchm, or by any rule that reads nchm, would break this: tests/test_speech_rows_gpu.py holds the bits.)
+template <int KW, bool ROWS>
+__global__ __launch_bounds__(256) void conv0_moments2_kernel(const float* __restrict__ wav, const int* __restrict__ lens, float* __restrict__ part,
+                                                             int S, int L, int k, int stride, int nchm) {
   __shared__ float red[4][MAXMOM];
   extern __shared__ __attribute__((aligned(16))) float segm[];      // the block's samples: (TCM - 1) stride + k floats (+ alignment slack)
   const int b = blockIdx.y, ch = blockIdx.x;
-  const int t0 = ch * TCM, nt = min(TCM, L - t0);
+  const int t0 = ch * TCM, nt = ROWS ? max(0, min(TCM, row_len(lens, b, k, stride, L) - t0)) : min(TCM, L - t0);
   {
     // coalesced 16-byte loads from the 16-byte-aligned address at or below the block's first sample
     const long long g0 = (long long)b * S + (long long)t0 * stride;
     const long long ga = g0 & ~3ll;
-    const int shift = (int)(g0 - ga), nneed = shift + (nt - 1) * stride + k;
+    const int shift = (int)(g0 - ga), nneed = (ROWS && nt == 0) ? 0 : shift + (nt - 1) * stride + k;
     const long long gend = (long long)(b + 1) * S;          // (never read past the clip: the next clip / the buffer's end)
     const float4* src = reinterpret_cast<const float4*>(wav + ga);
     const bool al16 = (reinterpret_cast<uintptr_t>(wav) & 15) == 0;
@@ -154,7 +167,8 @@ __global__ __launch_bounds__(256) void conv0_moments2_kernel(const float* __rest
     part[((long long)b * nchm + ch) * nm + i] = (red[0][i] + red[1][i]) + (red[2][i] + red[3][i]);
 }
 // the two halves of conv0_stats2_kernel as device functions (conv0_stats_wfrag_kernel below runs them too)
-// chunk partials -> fp64 sums: two 128-lane groups take every second chunk, sixteen chunks per round (sixteen loads in flight per thread:
+// chunk partials -> fp64 sums (the per-row-lengths forward relies on the grouping being independent of nchm, see conv0_moments2_kernel):
+// two 128-lane groups take every second chunk, sixteen chunks per round (sixteen loads in flight per thread:
 // with one -- a runtime-trip-count loop -- the fold was nchm / 4 dependent L2 round trips), folded in a fixed order.  The first round's
 // loads can be issued early (fold_prefetch) so that they fly together with whatever else the caller loads.
 struct FoldPre { float v[16]; };
@@ -218,11 +232,14 @@ __device__ __forceinline__ void channel_stats(Tap tap, const double* ms, int k, 
   mean = (float)mu;
   rstd = (float)(1.0 / sqrt(var + (double)eps));
 }
+template <bool ROWS>
 __global__ __launch_bounds__(256) void conv0_stats2_kernel(const float* __restrict__ part, double* __restrict__ mom, const float* __restrict__ w,
-                                                           float* __restrict__ stats, int C, int k, int L, int nchm, float eps) {
+                                                           float* __restrict__ stats, const int* __restrict__ lens, int C, int k, int stride, int L,
+                                                           int nchm, float eps) {
   __shared__ double ms[MAXMOM];
   __shared__ double ps[2][MAXMOM];
   const int b = blockIdx.y, nm = nmom(k);
+  if (ROWS) L = row_len(lens, b, k, stride, L);      // (the row's own frame count divides its sums)
   fold_chunk_moments(part, mom, ms, ps, b, nm, nchm, blockIdx.x == 0, nullptr);
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (!stats || threadIdx.x >= 64 || c >= C) return;
@@ -235,16 +252,19 @@ __global__ __launch_bounds__(256) void conv0_stats2_kernel(const float* __restri
 }
 
 // ---- forward apply: conv -> normalise -> affine -> GELU -> channels-last store ----
-template <typename T, int KW>
-__global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restrict__ wav, const float* __restrict__ w,
+// ROWS: frames at and past the row's own count are stored as ZEROS (nothing downstream then reads a value that depends on what the
+// padding holds or on a neighbour's length); the frames before it see the same staged samples and statistics as the single-row call.
+template <typename T, int KW, bool ROWS>
+__global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restrict__ wav, const int* __restrict__ lens, const float* __restrict__ w,
                                                           const float* __restrict__ gamma,
                                                           const float* __restrict__ beta,
                                                           const float* __restrict__ stats, T* __restrict__ out, int S,
                                                           int L, int C, int k, int stride) {
   extern __shared__ float seg[];
   const int b = blockIdx.y, t0 = blockIdx.x * TCH;
-  const int nt = min(TCH, L - t0);
-  stage_wav(seg, wav, b, S, t0, nt, k, stride);
+  const int ntl = min(TCH, L - t0);                                                          // frames of this block in the launch
+  const int nt = ROWS ? max(0, min(ntl, row_len(lens, b, k, stride, L) - t0)) : ntl;       // ... and of them, the row's own
+  stage_wav(seg, wav, b, S, t0, ROWS ? max(nt, 1) : nt, k, stride);
   const Geo g = geo(C);
   const int cgi = threadIdx.x % g.cg, tli = threadIdx.x / g.cg;
   const int c0 = cgi * 8;
@@ -269,6 +289,12 @@ __global__ __launch_bounds__(256) void conv0_apply_kernel(const float* __restric
       y[e] = FAST ? gelu_poly(z) : gelu_f(z);
     }
     store8f<T>(out + ((long long)b * L + t0 + t) * C + c0, y);
+  }
+  if (ROWS) {
+    float z[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) z[e] = 0.f;
+    for (int t = nt + tli; t < ntl; t += g.tl) store8f<T>(out + ((long long)b * L + t0 + t) * C + c0, z);
   }
 }
 
@@ -322,14 +348,16 @@ __global__ __launch_bounds__(128) void conv0_wfrag_kernel(const float* __restric
 // 94 us for the call against 87.)
 // The backward calls it with the forward's statistics (stats_in): no statistics are derived, and only the block of tile 0 folds the
 // moments -- to publish `mom` for conv0_bwd_final_kernel (conv0_stats2_kernel did only that there: one launch less).
+template <bool ROWS>
 __global__ __launch_bounds__(256) void conv0_stats_wfrag_kernel(const float* __restrict__ part, const float* __restrict__ w,
                                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                                 const float* __restrict__ stats_in, float* __restrict__ stats,
-                                                                double* __restrict__ mom, bf16x8* __restrict__ afrag, int C, int k, int L,
-                                                                int nchm, float eps) {
+                                                                double* __restrict__ mom, bf16x8* __restrict__ afrag, const int* __restrict__ lens,
+                                                                int C, int k, int stride, int L, int nchm, float eps) {
   __shared__ double ms[MAXMOM];
   __shared__ double ps[2][MAXMOM];
   const int mt = blockIdx.x, b = blockIdx.y, q = (threadIdx.x >> 6) & 1, l = threadIdx.x & 63;
+  if (ROWS) L = row_len(lens, b, k, stride, L);      // (the row's own frame count divides its sums)
   const int c = 32 * mt + c0_perm(l & 31), hi = l >> 5;
   float wr[10];
 #pragma unroll
@@ -373,8 +401,8 @@ __device__ __forceinline__ float gelu_tab(float z, const float2* gt) {
   asm("v_max_f32 %0, 0, %1" : "=v"(relu) : "v"(z));      // (one slot; fmaxf adds a canonicalising v_max z, z in front)
   return fmaf(-fabsf(z), q, relu);
 }
-template <bool TAB>
-__global__ __launch_bounds__(256) void conv0_apply_mfma_kernel(const float* __restrict__ wav, const bf16x8* __restrict__ afrag_g,
+template <bool TAB, bool ROWS>
+__global__ __launch_bounds__(256) void conv0_apply_mfma_kernel(const float* __restrict__ wav, const int* __restrict__ lens, const bf16x8* __restrict__ afrag_g,
                                                                bf16_t* __restrict__ out, int S, int L, int C, int k, int stride, int seg_bytes) {
   extern __shared__ __attribute__((aligned(16))) char sm0[];
   const int ntile = C / 32;
@@ -388,8 +416,9 @@ __global__ __launch_bounds__(256) void conv0_apply_mfma_kernel(const float* __re
     const_cast<float2*>(gt)[threadIdx.x] = make_float2(v0, v1 - v0);
   }
   const int b = blockIdx.y, t0 = blockIdx.x * TCH;
-  const int nt = min(TCH, L - t0);
-  stage_wav(seg, wav, b, S, t0, nt, k, stride);
+  const int nlau = min(TCH, L - t0);                                                         // frames of this block in the launch
+  const int nt = ROWS ? max(0, min(nlau, row_len(lens, b, k, stride, L) - t0)) : nlau;      // ... and of them, the row's own (ROWS)
+  stage_wav(seg, wav, b, S, t0, ROWS ? max(nt, 1) : nt, k, stride);
   const bf16x8* afb = afrag_g + (long long)b * ntile * 128;
   for (int i = threadIdx.x; i < ntile * 128; i += 256) afr[i] = afb[i];
   __syncthreads();
@@ -399,6 +428,20 @@ __global__ __launch_bounds__(256) void conv0_apply_mfma_kernel(const float* __re
   for (int ntl = 0; ntl < 2; ++ntl) {
     const int tl = wave * 64 + ntl * 32 + n;
     const bool tv = tl < nt;
+    const bool tz = ROWS && !tv && tl < nlau;     // (ROWS: a frame of the launch past the row's own count is stored as zeros)
+    if (ROWS && nt == 0) {                          // (block-uniform: nothing of this block belongs to the row)
+      if (tz) {
+        bf16x8 z;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
+        bf16_t* zrow = out + ((long long)b * L + t0 + tl) * C + 16 * hi;
+        for (int mt = 0; mt < ntile; ++mt) {
+          *reinterpret_cast<bf16x8*>(zrow + mt * 32) = z;
+          *reinterpret_cast<bf16x8*>(zrow + mt * 32 + 8) = z;
+        }
+      }
+      continue;
+    }
     const float* sp = seg + (tv ? tl : 0) * stride;
     bf16_t xh[10], xl[10];
 #pragma unroll
@@ -416,7 +459,7 @@ __global__ __launch_bounds__(256) void conv0_apply_mfma_kernel(const float* __re
       b1 = bf16x8{xh[8], xh[9], xl[0], xl[1], xl[2], xl[3], xl[4], xl[5]};
       b2 = bf16x8{xh[4], xh[5], xh[6], xh[7], xh[8], xh[9], one, one};
     }
-    bf16_t* orow = out + ((long long)b * L + t0 + (tv ? tl : 0)) * C + 16 * hi;
+    bf16_t* orow = out + ((long long)b * L + t0 + ((tv || tz) ? tl : 0)) * C + 16 * hi;
     for (int mt = 0; mt < ntile; ++mt) {
       const bf16x8 a1 = afr[(mt * 2 + 0) * 64 + lane], a2 = afr[(mt * 2 + 1) * 64 + lane];
       f32x16 acc;
@@ -433,6 +476,12 @@ __global__ __launch_bounds__(256) void conv0_apply_mfma_kernel(const float* __re
         }
         *reinterpret_cast<bf16x8*>(orow + mt * 32) = o0;
         *reinterpret_cast<bf16x8*>(orow + mt * 32 + 8) = o1;
+      } else if (ROWS && tz) {
+        bf16x8 z;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) z[e] = (bf16_t)0.f;
+        *reinterpret_cast<bf16x8*>(orow + mt * 32) = z;
+        *reinterpret_cast<bf16x8*>(orow + mt * 32 + 8) = z;
       }
     }
   }
@@ -809,14 +858,15 @@ __host__ inline Ws carve(void* ws, int B, int nch, int C, int k) {
 }
 
 // waveform moments (+ statistics when `stats` is given): two launches
+template <bool ROWS = false>
 void launch_moments_stats(const float* wav, const float* w, float* stats, const Ws& W, int B, int S, int L, int C, int k, int stride, float eps,
-                          hipStream_t s, bool with_stats = true, double* mom = nullptr) {
+                          hipStream_t s, bool with_stats = true, double* mom = nullptr, const int* lens = nullptr) {
   const int nchm = (L + TCM - 1) / TCM;
   const size_t shm2 = (size_t)(((TCM - 1) * stride + k + 8 + 3) & ~3) * sizeof(float);
   if (shm2 > 60 * 1024) return;      // (strides far beyond the recipe's 5: the caller rejects them, see st5_conv0_gn_gelu_fwd)
-  if (k <= 10) hipLaunchKernelGGL((conv0_moments2_kernel<10>), dim3(nchm, B), dim3(256), shm2, s, wav, W.part, S, L, k, stride, nchm);
-  else hipLaunchKernelGGL((conv0_moments2_kernel<MAXK>), dim3(nchm, B), dim3(256), shm2, s, wav, W.part, S, L, k, stride, nchm);
-  if (with_stats) hipLaunchKernelGGL(conv0_stats2_kernel, dim3((C + 63) / 64, B), dim3(256), 0, s, W.part, mom ? mom : W.mom, w, stats, C, k, L, nchm, eps);
+  if (k <= 10) hipLaunchKernelGGL((conv0_moments2_kernel<10, ROWS>), dim3(nchm, B), dim3(256), shm2, s, wav, lens, W.part, S, L, k, stride, nchm);
+  else hipLaunchKernelGGL((conv0_moments2_kernel<MAXK, ROWS>), dim3(nchm, B), dim3(256), shm2, s, wav, lens, W.part, S, L, k, stride, nchm);
+  if (with_stats) hipLaunchKernelGGL(conv0_stats2_kernel<ROWS>, dim3((C + 63) / 64, B), dim3(256), 0, s, W.part, mom ? mom : W.mom, w, stats, lens, C, k, stride, L, nchm, eps);
 }
 
 }  // namespace
@@ -845,9 +895,12 @@ extern "C" int st5_conv0_gn_gelu_fwd(const float* wav, const float* w, const flo
                                      int32_t stride, float eps, int dtype, void* stream) {
   return st5_conv0_gn_gelu_fwd_m(wav, w, gamma, beta, out, stats, nullptr, ws, B, S, C, k, stride, eps, dtype, stream);
 }
-extern "C" int st5_conv0_gn_gelu_fwd_m(const float* wav, const float* w, const float* gamma, const float* beta,
-                                       void* out, float* stats, double* mom, void* ws, int32_t B, int32_t S, int32_t C, int32_t k,
-                                       int32_t stride, float eps, int dtype, void* stream) {
+namespace {
+// the forward's launches; ROWS: per-row lengths `lens` (int32 [B] on the device, samples), see st5_conv0_gn_gelu_fwd_rows
+template <bool ROWS>
+int conv0_fwd(const float* wav, const int* lens, const float* w, const float* gamma, const float* beta,
+              void* out, float* stats, double* mom, void* ws, int32_t B, int32_t S, int32_t C, int32_t k,
+              int32_t stride, float eps, int dtype, void* stream) {
   if (!wav || !w || !gamma || !beta || !out || !stats || !ws) return ST5_ERR_ARG;
   if (C % 8 || C > 2048 || 256 % (C / 8 > 256 ? 256 : C / 8) || k > MAXK || k < 1 || stride < 1 || stride > 7) return ST5_ERR_ARG;
   if (C / 8 > 256) return ST5_ERR_ARG;
@@ -860,32 +913,45 @@ extern "C" int st5_conv0_gn_gelu_fwd_m(const float* wav, const float* w, const f
   const Ws W = carve(ws, B, nch, C, k);
   const bool mfma = dtype == ST5_BF16 && g_conv0_mfma && k <= 10 && C % 32 == 0 && C <= 1024;
   const bool fold = mfma && g_conv0_fold;
-  launch_moments_stats(wav, w, stats, W, B, S, L, C, k, stride, eps, s, !fold, mom);
-#define APPLY(TT, KW)                                                                                           \
-  hipLaunchKernelGGL((conv0_apply_kernel<TT, KW>), dim3(nch, B), dim3(256), shm, s, wav, w, gamma, beta, stats, \
+  launch_moments_stats<ROWS>(wav, w, stats, W, B, S, L, C, k, stride, eps, s, !fold, mom, lens);
+#define APPLY(TT, KW)                                                                                                       \
+  hipLaunchKernelGGL((conv0_apply_kernel<TT, KW, ROWS>), dim3(nch, B), dim3(256), shm, s, wav, lens, w, gamma, beta, stats, \
                      (TT*)out, S, L, C, k, stride)
   if (mfma) {
     const int seg_bytes = (int)((shm + 7) & ~(size_t)7);
     const size_t shm_m = (size_t)(C / 32) * 2048 + seg_bytes + (g_conv0_gelu_tab ? 256 * sizeof(float2) : 0);
     static bool attr = false;
     if (!attr) {
-      if (hipFuncSetAttribute((const void*)conv0_apply_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
-          hipFuncSetAttribute((const void*)conv0_apply_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
+      if (hipFuncSetAttribute((const void*)conv0_apply_mfma_kernel<false, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess ||
+          hipFuncSetAttribute((const void*)conv0_apply_mfma_kernel<true, ROWS>, hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024) != hipSuccess)
         return ST5_ERR_LAUNCH;
       attr = true;
     }
-    if (fold) hipLaunchKernelGGL(conv0_stats_wfrag_kernel, dim3(C / 32, B), dim3(256), 0, s, (const float*)W.part, w, gamma, beta, (const float*)nullptr,
-                                 stats, mom, W.afrag, C, k, L, (L + TCM - 1) / TCM, eps);
+    if (fold) hipLaunchKernelGGL(conv0_stats_wfrag_kernel<ROWS>, dim3(C / 32, B), dim3(256), 0, s, (const float*)W.part, w, gamma, beta, (const float*)nullptr,
+                                 stats, mom, W.afrag, lens, C, k, stride, L, (L + TCM - 1) / TCM, eps);
     else hipLaunchKernelGGL(conv0_wfrag_kernel, dim3(C / 32, B), dim3(128), 0, s, w, gamma, beta, stats, W.afrag, C, k);
     if (g_conv0_gelu_tab)
-      hipLaunchKernelGGL(conv0_apply_mfma_kernel<true>, dim3(nch, B), dim3(256), shm_m, s, wav, W.afrag, (bf16_t*)out, S, L, C, k, stride, seg_bytes);
+      hipLaunchKernelGGL((conv0_apply_mfma_kernel<true, ROWS>), dim3(nch, B), dim3(256), shm_m, s, wav, lens, W.afrag, (bf16_t*)out, S, L, C, k, stride, seg_bytes);
     else
-      hipLaunchKernelGGL(conv0_apply_mfma_kernel<false>, dim3(nch, B), dim3(256), shm_m, s, wav, W.afrag, (bf16_t*)out, S, L, C, k, stride, seg_bytes);
+      hipLaunchKernelGGL((conv0_apply_mfma_kernel<false, ROWS>), dim3(nch, B), dim3(256), shm_m, s, wav, lens, W.afrag, (bf16_t*)out, S, L, C, k, stride, seg_bytes);
   } else if (dtype == ST5_BF16) { if (k <= 10) APPLY(bf16_t, 10); else APPLY(bf16_t, MAXK); }
   else { if (k <= 10) APPLY(float, 10); else APPLY(float, MAXK); }
 #undef APPLY
   HIP_CHECK_LAUNCH();
   return ST5_OK;
+}
+}  // namespace
+
+extern "C" int st5_conv0_gn_gelu_fwd_m(const float* wav, const float* w, const float* gamma, const float* beta,
+                                       void* out, float* stats, double* mom, void* ws, int32_t B, int32_t S, int32_t C, int32_t k,
+                                       int32_t stride, float eps, int dtype, void* stream) {
+  return conv0_fwd<false>(wav, nullptr, w, gamma, beta, out, stats, mom, ws, B, S, C, k, stride, eps, dtype, stream);
+}
+extern "C" int st5_conv0_gn_gelu_fwd_rows(const float* wav, const int32_t* lens, const float* w, const float* gamma, const float* beta,
+                                          void* out, float* stats, void* ws, int32_t B, int32_t S, int32_t C, int32_t k,
+                                          int32_t stride, float eps, int dtype, void* stream) {
+  if (!lens) return ST5_ERR_ARG;
+  return conv0_fwd<true>(wav, lens, w, gamma, beta, out, stats, nullptr, ws, B, S, C, k, stride, eps, dtype, stream);
 }
 
 extern "C" int st5_conv0_gn_gelu_bwd(const float* wav, const float* w, const float* gamma, const float* beta,
@@ -924,8 +990,8 @@ extern "C" int st5_conv0_gn_gelu_bwd_m(const float* wav, const float* w, const f
   // (C <= 512: conv0_bwd_mfma_kernel holds at most four 128-channel tiles per wave -- G[4], dvq[4]; wider layers take the VALU kernel,
   //  whose channel loop has no such bound.  ADVICE r5: the guard said 1024 and tiles 4.. were silently never computed.)
   if (mfma) {
-    if (fold) hipLaunchKernelGGL(conv0_stats_wfrag_kernel, dim3(C / 32, B), dim3(256), 0, s, (const float*)W.part, w, gamma, beta, stats, (float*)nullptr,
-                                 W.mom, W.afrag, C, k, L, (L + TCM - 1) / TCM, 0.f);
+    if (fold) hipLaunchKernelGGL(conv0_stats_wfrag_kernel<false>, dim3(C / 32, B), dim3(256), 0, s, (const float*)W.part, w, gamma, beta, stats, (float*)nullptr,
+                                 W.mom, W.afrag, (const int*)nullptr, C, k, stride, L, (L + TCM - 1) / TCM, 0.f);
     else hipLaunchKernelGGL(conv0_wfrag_kernel, dim3(C / 32, B), dim3(128), 0, s, w, gamma, beta, stats, W.afrag, C, k);
     const size_t seg_f = (size_t)(((TCH - 1) * stride + k + MAXK + 3) & ~3);
     const size_t shm_m = (size_t)(C / 32) * 2048 + seg_f * sizeof(float) + (size_t)4 * C0_TILE_B + (g_conv0_gelu_tab ? 512 * sizeof(float2) : 0);

@@ -2571,6 +2571,45 @@ def conv_feature_extractor(wav, layers, gscale, w0, gn_w, gn_b, ws):
     return ConvFeatureExtractorFunction.apply(wav, tuple(layers), float(gscale), w0, gn_w, gn_b, *ws)
 
 
+def conv_feature_extractor_rows(wav, lens, layers, w0, gn_w, gn_b, ws):
+    """The layer walk of ConvFeatureExtractorFunction.forward for INFERENCE on a right-padded batch with per-row lengths: wav fp32
+    [B, S], lens int32 [B] on the device (samples).  Conv layer 0 takes each row's GroupNorm statistics over the row's own frames and
+    stores zeros behind them (st5_conv0_gn_gelu_fwd_rows); nothing is saved for a backward.  Frame t of row b, t below the row's
+    own frame count, reads nothing outside the row: it is what the single-row call gives.  The GEMM layers still name a
+    pre-activation output, dropped at once: st5_gemm's fused GELU epilogue is specialised for the (GELU, Cpre) pair the training
+    walk uses, and without Cpre the same GEMMs ran on the generic epilogue, 14 % slower (kernel traces at B = 8 / 32).
+    Returns channels-last features [B, T, C] in the compute dtype.  No autograd: raises when a gradient would be expected."""
+    if torch.is_grad_enabled() and any(p.requires_grad for p in (w0, gn_w, gn_b, *ws)):
+        raise RuntimeError("conv_feature_extractor_rows is inference only: call it under torch.no_grad() (training goes through conv_feature_extractor)")
+    dtype = _S.dtype
+    dev = wav.device
+    B, S = wav.shape
+    L = hip.lib()
+    C0, k0, s0 = layers[0]
+    wav = wav.contiguous()
+    assert wav.dtype == torch.float32 and lens.dtype == torch.int32 and lens.numel() == B and lens.device == dev
+    L0 = (S - k0) // s0 + 1
+    y = torch.empty(B, L0, C0, dtype=dtype, device=dev)
+    stats = torch.empty(B, C0, 2, dtype=torch.float32, device=dev)
+    wsb = hip.workspace(L.st5_conv0_ws_bytes(B, S, C0, k0, s0), dev)
+    w0f = w0.detach().reshape(C0, k0).contiguous()
+    with hip.profiler.region("conv0_gn_gelu_fwd_rows", B * S * 4 + B * L0 * C0 * y.element_size()):
+        hip.check(L.st5_conv0_gn_gelu_fwd_rows(wav.data_ptr(), lens.data_ptr(), w0f.data_ptr(), gn_w.data_ptr(), gn_b.data_ptr(), y.data_ptr(),
+                                               stats.data_ptr(), wsb.data_ptr(), B, S, C0, k0, s0, 1e-5, _dt(dtype), hip.stream()),
+                  "st5_conv0_gn_gelu_fwd_rows")
+    x, Lin, Cin = y, L0, C0
+    for i, (C, k, s) in enumerate(layers[1:]):
+        Lo = (Lin - k) // s + 1
+        Wk = _conv_w_fwd(ws[i], dtype)
+        out = torch.empty(B, Lo, C, dtype=dtype, device=dev)
+        pre = torch.empty(B, Lo, C, dtype=dtype, device=dev)
+        hip.gemm(hip.operand(x, s * Cin, rpb=Lo, bstride=Lin * Cin), hip.operand(Wk, k * Cin), hip.operand(out, C),
+                 B * Lo, C, k * Cin, _dt(dtype), Cpre=hip.operand(pre, C), act=ACT_GELU)
+        del pre
+        x, Lin, Cin = out, Lo, C
+    return x
+
+
 # -------------------------------------------------------------------------------------------------
 # extractor_mode=layer_norm (SpeechT5-Large recipe, speech_encoder_prenet.py:290-354): every block is
 # Conv1d(bias) -> LayerNorm over channels -> GELU.  Channels-last makes the LayerNorm a plain row LayerNorm; the

@@ -49,6 +49,15 @@ class ConvFeatureExtractionModel(nn.Module):
         ws = [blk[0].weight for blk in list(self.conv_layers)[1:]]
         return Fn.conv_feature_extractor(x.float(), self.conv_layers_infos, grad_scale, l0[0].weight, l0[2].weight, l0[2].bias, ws)
 
+    def forward_rows(self, x, lens):
+        """Inference on a right-padded batch with per-row lengths (lens int32 [B] on the device, samples): frame t of row b below the
+        row's own frame count is what forward() gives for the row alone.  The layer-norm extractor is exact per frame as it is."""
+        if self.mode == "layer_norm":
+            return self.forward(x)
+        l0 = self.conv_layers[0]
+        ws = [blk[0].weight for blk in list(self.conv_layers)[1:]]
+        return Fn.conv_feature_extractor_rows(x.float(), lens, self.conv_layers_infos, l0[0].weight, l0[2].weight, l0[2].bias, ws)
+
     def get_out_seq_lens_tensor(self, in_seq_lens_tensor):
         out = in_seq_lens_tensor.clone()
         for _, k, s in self.conv_layers_infos:
@@ -178,6 +187,58 @@ class SpeechEncoderPrenet(nn.Module):
         if require_feat_pen:
             return (x, features_pen, mask_indices, target_list), encoder_padding_mask
         return x, encoder_padding_mask
+
+    def forward_rows(self, source, lengths):
+        """The eval forward in which every row of a right-padded batch gets what it would get alone: source fp32 [B, S], `lengths` the
+        rows' sample counts (host list or tensor).  Returns (x [B, T, C], encoder_padding_mask bool [B, T]) like forward(mask=False);
+        frames t < T_b of row b equal the single-row call on source[b, :lengths[b]].  Three things differ from forward():
+        conv layer 0's GroupNorm runs over the row's own frames; the padding mask is t >= T_b with T_b from the conv length formula
+        (the reference's chunk rule leaves one frame too many valid on most rows); the frames behind T_b are zero when the
+        positional convolution reads them, as the zero "same" padding of a single-row call is.  No span mask, no dropout."""
+        if self.training:
+            raise RuntimeError("SpeechEncoderPrenet.forward_rows is the eval forward (no span mask, no dropout): call model.eval() first")
+        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+            raise RuntimeError("SpeechEncoderPrenet.forward_rows is inference only: call it under torch.no_grad()")
+        n = [int(v) for v in (lengths.tolist() if torch.is_tensor(lengths) else lengths)]
+        B, S = source.shape
+        if len(n) != B:
+            raise ValueError(f"{len(n)} lengths for {B} rows")
+        if max(n) > S:
+            raise ValueError(f"a length of {max(n)} samples exceeds the batch's {S}")
+        Tb = [self._frames(v) for v in n]
+        if min(Tb) < 1:
+            b = Tb.index(min(Tb))
+            raise ValueError(f"row {b} has {n[b]} samples: shorter than one frame ({self.min_samples()} samples)")
+        dev = source.device
+        lens = Fn.stage_host(lambda: torch.tensor(n, dtype=torch.int32), dev)
+        T_dev = Fn.stage_host(lambda: torch.tensor(Tb, dtype=torch.int64), dev)
+        x = self.feature_extractor.forward_rows(source, lens)             # [B, T, C]
+        T = x.size(1)
+        x = self.layer_norm(x)
+        encoder_padding_mask = torch.arange(T, device=dev)[None, :] >= T_dev[:, None]
+        if self.post_extract_proj is not None:
+            x = Fn.linear(x, self.post_extract_proj.weight, self.post_extract_proj.bias)
+        if min(Tb) < T:
+            # (st5_masked_fill_rows with a zero vector: one launch on the smallest activation of the front end; a kernel of its own
+            #  with device-side lengths would only save this mask, which the encoder needs anyway)
+            x = Fn.masked_fill_rows(x, encoder_padding_mask.reshape(-1), torch.zeros(x.size(-1), dtype=torch.float32, device=dev))
+        if self.use_conv_pos:
+            conv = self.pos_conv[0]
+            v = conv.weight_v
+            w = v * (conv.weight_g / torch.linalg.vector_norm(v, dim=(0, 1), keepdim=True))
+            x = Fn.pos_conv(x, w, conv.bias, self.conv_pos_groups)
+        if self.use_sinc_pos:
+            positions = self.embed_positions.positions(~encoder_padding_mask)
+            table = self.embed_positions.table(x.shape[1] + self.padding_idx + 2, x.device)
+            x = Fn.add_table_rows(x, table, positions.reshape(-1))
+        return x, encoder_padding_mask
+
+    def min_samples(self):
+        """The shortest clip that gives one frame (400 samples at the recipe's layers)."""
+        n = 1
+        for _, k, s in reversed(self.feature_extractor.conv_layers_infos):
+            n = (n - 1) * s + k
+        return n
 
     def forward_targets(self, features, target_list):
         """features are channels-last here ([B,T,C]); same trimming rule as the reference (:206-217)."""

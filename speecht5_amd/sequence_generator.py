@@ -118,9 +118,13 @@ def hip_fuse_lm(lprobs, logits, lm_weight):
 class SequenceGenerator(nn.Module):
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
-                 search_strategy=None, eos=None, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, ctc_weight=0.0):
+                 search_strategy=None, eos=None, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, ctc_weight=0.0,
+                 exact_rows=False):
+        """`exact_rows`: speech input is encoded through forward_encoder_rows, so that a row's hypotheses do not depend on what else
+        is in its batch (off, the default: the reference's padded batch)."""
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)
+        self.exact_rows = bool(exact_rows)      # (the generator's own: an EnsembleModel may serve several generators)
         self.tgt_dict = tgt_dict
         self.pad, self.unk = tgt_dict.pad(), tgt_dict.unk()
         self.eos = tgt_dict.eos() if eos is None else eos
@@ -196,7 +200,7 @@ class SequenceGenerator(nn.Module):
             min(int(self.max_len_a * src_len + self.max_len_b), self.max_len - 1)
         assert self.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
 
-        encoder_outs = self.model.forward_encoder(net_input)
+        encoder_outs = self.model.forward_encoder(net_input, exact_rows=True) if self.exact_rows else self.model.forward_encoder(net_input)
         # a HIP transformer_lm decodes incrementally over a slot cache (transformer_lm.py); any other LM runs the full prefix
         lm_state = None
         if self.lm_model is not None and _is_hip_lm(self.lm_model):
@@ -463,10 +467,13 @@ class EnsembleModel(nn.Module):
     def max_decoder_positions(self):
         return min([m.max_decoder_positions() for m in self.models if hasattr(m, "max_decoder_positions")] + [sys.maxsize])
 
-    def forward_encoder(self, net_input: Dict[str, Tensor]):
+    def forward_encoder(self, net_input: Dict[str, Tensor], exact_rows: bool = False):
+        """`exact_rows` (SequenceGenerator(exact_rows=True)): speech rows through forward_encoder_rows."""
         if not self.has_encoder():
             return None
         if self.is_t5_structure():
+            if exact_rows and "source" in net_input:
+                return [m.forward_encoder_rows(net_input["source"], padding_mask=net_input.get("padding_mask")) for m in self.models]
             return [m.forward_encoder_torchscript(net_input) for m in self.models]
         return [m.encoder.forward_torchscript(net_input) for m in self.models]
 

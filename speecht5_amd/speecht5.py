@@ -355,6 +355,84 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         encoder_input, encoder_padding_mask = self.speech_encoder_prenet(source, padding_mask=padding_mask, mask=False)
         return self.encoder(encoder_input, encoder_padding_mask)
 
+    # ---- length-exact batched speech encoding: every row of a right-padded batch gets what it would get alone ----
+    ROWS_BYTE_BUDGET = 2 << 30   # bytes of conv layer 0's output per chunk (DESIGN.md "Length-exact batched speech encoding")
+
+    @staticmethod
+    def _row_lengths(source, padding_mask, src_lengths):
+        """The rows' sample counts as a host list: `src_lengths` (list or tensor) when given, else from `padding_mask`; no mask =
+        every row is full.  The counts and the suffix test are a handful of bool reductions where the mask lives (on the device for
+        a device mask: no [B, S] copy to the host) and reach the host in ONE read of B + 1 integers, remembered on the mask tensor
+        (as `_st5_host` is) for a caller that passes the same tensor again."""
+        B, S = source.shape
+        if src_lengths is not None:
+            return [int(v) for v in (src_lengths.tolist() if torch.is_tensor(src_lengths) else src_lengths)]
+        if padding_mask is None:
+            return [S] * B
+        n = getattr(padding_mask, "_st5_row_lengths", None)
+        if n is None:
+            if tuple(padding_mask.shape) != (B, S):
+                raise ValueError(f"padding_mask {tuple(padding_mask.shape)} does not match source {(B, S)}")
+            pm = padding_mask.bool()
+            # right-padded = never a valid sample after a padded one: pm[:, t] implies pm[:, t + 1]
+            suffix = (pm[:, 1:] | ~pm[:, :-1]).all()
+            *n, ok = torch.cat([(~pm).sum(1), suffix.long().view(1)]).tolist()
+            if not ok:
+                raise ValueError("padding_mask is not a suffix per row: the rows path takes right-padded batches only")
+            padding_mask._st5_row_lengths = n
+        return n
+
+    def _plan_row_chunks(self, n, max_samples):
+        """Rows in order into chunks whose padded sample count B_chunk * n_max stays within `max_samples`; default: conv layer 0's
+        output of the chunk within ROWS_BYTE_BUDGET and below 2^31 elements.  A row that is over the limit alone goes alone."""
+        C0, k0, s0 = self.speech_encoder_prenet.feature_extractor.conv_layers_infos[0]
+        hard = (2 ** 31 - 1) // C0                                         # frames of layer 0 per chunk
+        if max_samples is None:
+            frames = min(hard, self.ROWS_BYTE_BUDGET // (C0 * torch.empty(0, dtype=Fn.compute_dtype()).element_size()))
+        else:
+            frames = min(hard, max(1, (int(max_samples) - k0) // s0 + 1))
+        chunks, cur, cur_max = [], [], 0
+        for b, v in enumerate(n):
+            L0 = max((v - k0) // s0 + 1, 0)
+            if L0 > hard:
+                raise ValueError(f"row {b}: {v} samples give {L0} x {C0} activations in conv layer 0, beyond 2^31 elements")
+            m = max(cur_max, L0)
+            if cur and (len(cur) + 1) * m > frames:
+                chunks.append(cur)
+                cur, m = [], L0
+            cur.append(b)
+            cur_max = m
+        chunks.append(cur)
+        return chunks
+
+    def _forward_encoder_rows(self, source, padding_mask=None, src_lengths=None, max_samples=None):
+        n = self._row_lengths(source, padding_mask, src_lengths)
+        pre = self.speech_encoder_prenet
+        xs, masks, T = [], [], [pre._frames(v) for v in n]
+        for rows in self._plan_row_chunks(n, max_samples):
+            nm = max(n[b] for b in rows)
+            x, m = pre.forward_rows(source[rows[0]:rows[-1] + 1, :nm], [n[b] for b in rows])
+            xs.append(x); masks.append(m)
+        Tm = max(T)
+        if len(xs) > 1:
+            x = xs[0].new_zeros(len(n), Tm, xs[0].size(2))
+            mask = torch.ones(len(n), Tm, dtype=torch.bool, device=x.device)
+            b0 = 0
+            for xc, mc in zip(xs, masks):
+                x[b0:b0 + xc.size(0), :xc.size(1)] = xc
+                mask[b0:b0 + xc.size(0), :xc.size(1)] = mc
+                b0 += xc.size(0)
+        else:
+            x, mask = xs[0], masks[0]
+        return self.encoder(x, mask), T
+
+    def forward_encoder_rows(self, source, padding_mask=None, src_lengths=None, max_samples=None):
+        """forward_encoder for a right-padded batch in which each row gets what it would get ALONE (inference, eval mode): the same
+        dict, `encoder_out` [T_max, B, C] and `encoder_padding_mask` [B, T_max] with T_max the longest row's frame count and row b
+        valid for t < T_b = frames(n_b).  The speech front end runs per chunk of rows (_plan_row_chunks; `max_samples` overrides the
+        byte budget as a limit on a chunk's padded samples B_chunk * n_max), the encoder once over all rows."""
+        return self._forward_encoder_rows(source, padding_mask, src_lengths, max_samples)[0]
+
     def forward_text_encoder(self, src_tokens):
         encoder_input, encoder_padding_mask = self.text_encoder_prenet(src_tokens)
         return self.encoder(encoder_input, encoder_padding_mask)
@@ -399,10 +477,12 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         return Fn.time_mean(x.transpose(0, 1))
 
     @torch.no_grad()
-    def generate_class(self, source, prev_output_tokens, **kwargs):
+    def generate_class(self, source, prev_output_tokens, exact_rows=False, **kwargs):
         """speecht5.py:1171-1186: encoder, the zeroed decoder input, decoder, speaker head on the decoder output's time mean; int64
-        classes [B].  Decoder pooling whatever --sid-pooling-layer says (as the reference)."""
-        encoder_out = self.forward_encoder(source, padding_mask=kwargs["padding_mask"])
+        classes [B].  Decoder pooling whatever --sid-pooling-layer says (as the reference).  `exact_rows`: encode through
+        forward_encoder_rows, so that a row's class does not depend on what else is in its batch (off: the reference's padded batch)."""
+        enc = self.forward_encoder_rows if exact_rows else self.forward_encoder
+        encoder_out = enc(source, padding_mask=kwargs["padding_mask"])
         x, tgt_mask = self._zero_decoder_input(prev_output_tokens)
         with self._no_attention_weights():
             decoder_output, _ = self.decoder(x, tgt_mask, encoder_out=encoder_out, alignment_layer=self.decoder.num_layers)
@@ -469,12 +549,16 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
     def _encode_rows(self, source, src_tokens, padding_mask):
         """Encoder output of B utterances as one padded batch: (encoder_out dict with [S_max, B, C] and a [B, S_max] key-padding
         mask, per-row encoder lengths T_b as a host list).  Text rows run as one padded batch (position-wise or key-masked); speech
-        rows one by one on the unpadded clip, since conv layer 0's GroupNorm and the convolutional positional embedding see the
-        padding of a padded batch."""
+        rows through the length-exact batched front end (forward_encoder_rows: conv layer 0's GroupNorm, the frame mask and the
+        convolutional positional embedding follow each row's own length), so each row is what forward_encoder gives for it alone.
+        A model in training mode (span mask / dropout semantics of forward_encoder, which the rows path does not have) keeps the
+        per-clip loop on the unpadded clips."""
         if source is None:
             enc = self.forward_text_encoder(src_tokens)
             pad = src_tokens.eq(self.text_encoder_prenet.padding_idx)
             return enc, (~pad).sum(1).tolist()
+        if not self.speech_encoder_prenet.training:
+            return self._forward_encoder_rows(source, padding_mask)
         B = source.size(0)
         n = [source.size(1)] * B if padding_mask is None else (~padding_mask.bool()).sum(1).tolist()
         outs = []
