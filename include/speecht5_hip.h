@@ -665,6 +665,39 @@ int st5_sumsq_pair(const float* x, const float* y, float* out, int64_t n, float 
 int st5_multi_transpose_bf16(const void* src_flat, void* dst_flat, const void* jobs_dev, int32_t njobs, int32_t ntiles,
                              void* stream);
 
+/* Skinny-M GEMM of the decode loops (csrc/decode_gemm.hip): out[m, n] = epilogue(sum_k x[m, k] * w[n, k] + bias[n]) for 1 <= M <= 32,
+ * w in nn.Linear layout [N, K] (stacked weights are one [sum N_i, K] matrix), x / w / res in `dtype`, fp32 accumulation.  Weight-streaming:
+ * every weight byte is read once; row m of out depends on row m of x only (same bits for any M and any other rows); the reduction order
+ * is a function of (N, K, dtype); no atomics.  Epilogue in st5_gemm's order: + bias (fp32 [N] or NULL), act (ST5 ACT_NONE / GELU / RELU /
+ * TANH), dropout (p in [0, 1), `seed` by value or tagged seed slot, element index (row0 + m) * N + n), + res (or NULL); out in `dtype`,
+ * or fp32 when out_f32 != 0.  step != NULL: the output base is out + clamp(*step, 0, step_cap - 1) * step_stride elements (device-side
+ * slot index of a decode step).  ws: fp32 workspace of st5_gemm_skinny_ws_bytes(N, K) bytes (0: none needed).  M > 32 or an unknown
+ * act: ST5_ERR_ARG; x / w not 16-byte aligned, or x_ld / w_ld / K not a multiple of 16 bytes of elements: ST5_ERR_ALIGN. */
+int64_t st5_gemm_skinny_ws_bytes(int32_t N, int32_t K);
+int st5_gemm_skinny(const void* x, int64_t x_ld, const void* w, int64_t w_ld, const float* bias, const void* res, int64_t res_ld, void* out,
+                    int64_t out_ld, int32_t M, int32_t N, int32_t K, int32_t act, float dropout_p, uint64_t seed, int32_t row0,
+                    int32_t out_f32, const int32_t* step, int64_t step_stride, int32_t step_cap, float* ws, int dtype, void* stream);
+/* Decode kernels with the step index in device memory (a decode step captured into a HIP graph cannot carry a host-side index).
+ * st5_lm_decode_attn_dev: st5_lm_decode_attn with t = clamp(*step + t_add, 1, t_max); grid and ws (st5_lm_decode_attn_ws_bytes(rows,
+ * t_max, ...)) are sized for t_max, key ranges past t exit at once, and the result is bit-equal to st5_lm_decode_attn(t).
+ * st5_decode_cross_attn_step: st5_decode_cross_attn whose record column is clamp(*step, 0, cap - 1): probs points at column 0 and
+ * p_col is the column stride (p_head >= cap * p_col).
+ * st5_tts_step_tail_dev: st5_tts_step_tail for idx = *counter + 1, then *counter = idx; with *counter outside [0, cap) nothing is
+ * written.  n_seeds > 0: seed_slots[k] = seed_table[idx * n_seeds + k] for the NEXT step (idx < cap), the per-step dropout seeds of the
+ * pre-net.  st5_tts_pe_add_step: y[b, :C] = x[b, :C] + alpha[0] * table[clamp(*step, 0, table_rows - 1), :C]. */
+int st5_lm_decode_attn_dev(const void* q, int64_t q_ld, const void* kv, int32_t rows_cap, int32_t Tmax, const int32_t* anc, int64_t anc_ld,
+                           int32_t rows, const int32_t* step, int32_t t_add, int32_t t_max, int32_t H, int32_t head_dim, void* ctx,
+                           int64_t ctx_ld, float* ws, int dtype, void* stream);
+int st5_decode_cross_attn_step(const void* q, int64_t q_ld, const void* kv, int64_t kv_ld, int64_t k_off, const uint8_t* kpm, int32_t B,
+                               int32_t S, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld, float* probs, int64_t p_row,
+                               int64_t p_head, int64_t p_col, const int32_t* step, int32_t cap, float* ws, int dtype, void* stream);
+int st5_tts_step_tail_dev(const float* y, int64_t y_ld, int32_t B, int32_t r, int32_t odim, const int32_t* minlen, const int32_t* maxlen,
+                          int32_t* done, int32_t* steps, int32_t* counter, int32_t cap, float threshold, float* mel, float* probs, void* next,
+                          int64_t next_ld, int32_t* active, const uint64_t* seed_table, uint64_t* seed_slots, int32_t n_seeds, int dtype,
+                          void* stream);
+int st5_tts_pe_add_step(const void* x, int64_t x_ld, const float* table, int32_t table_rows, const float* alpha, const int32_t* step,
+                        void* y, int64_t y_ld, int32_t B, int32_t C, int dtype, void* stream);
+
 const char* st5_version(void);
 
 #ifdef __cplusplus

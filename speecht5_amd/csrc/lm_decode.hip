@@ -51,12 +51,12 @@ __device__ __forceinline__ void load4f(const bf16_t* p, float* v) {
 // grid (nsplit, rows).  ws == nullptr (nsplit 1): ctx is written directly.  Otherwise ws holds per (row, split): H maxima, H sums,
 // then the C unnormalised accumulators.
 template <typename T, int HD>
-__global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_kernel(
+__device__ __forceinline__ void lm_decode_attn_body(
     const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int Tmax, int rows_cap, const int32_t* __restrict__ anc,
-    int64_t anc_ld, int t, int H, int chunk, float scale, T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ ws) {
+    int64_t anc_ld, int t, int H, int chunk, float scale, T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ ws, const int r,
+    const int split, const int nsplit) {
   constexpr int EPL = HD / 4;                 // elements per lane: 20 (hd 80) or 16 (hd 64)
   const int C = H * HD;
-  const int r = blockIdx.y, split = blockIdx.x, nsplit = gridDim.x;
   const int tid = threadIdx.x, g = tid >> 2, sub = tid & 3;
   const int P = LM_GROUPS / H;                // positions in flight per pass
   const int h = g % H, ps = g / H;
@@ -143,12 +143,40 @@ __global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_kernel(
   }
 }
 
+template <typename T, int HD>
+__global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_kernel(
+    const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int Tmax, int rows_cap, const int32_t* __restrict__ anc,
+    int64_t anc_ld, int t, int H, int chunk, float scale, T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ ws) {
+  lm_decode_attn_body<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, t, H, chunk, scale, ctx, ctx_ld, ws, blockIdx.y, blockIdx.x,
+                             gridDim.x);
+}
+
+// The same launch with t read from device memory (a decode step replayed from a graph): t = clamp(*step + t_add, 1, t_max); the grid is
+// sized for t_max (grid.x = lm_splits(rows, t_max), which bounds lm_splits(rows, t) for every t <= t_max); the partition of the key
+// range is the host launch's function of (rows, t), evaluated here, and workgroups past it exit at once.
+__device__ __forceinline__ int lm_dev_t(const int32_t* step, int t_add, int t_max) {
+  const int t = *step + t_add;
+  return t < 1 ? 1 : (t > t_max ? t_max : t);
+}
+template <typename T, int HD>
+__global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_dev_kernel(
+    const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int Tmax, int rows_cap, const int32_t* __restrict__ anc,
+    int64_t anc_ld, const int32_t* __restrict__ step, int t_add, int t_max, int H, float scale, T* __restrict__ ctx, int64_t ctx_ld,
+    float* __restrict__ ws) {
+  const int t = lm_dev_t(step, t_add, t_max);
+  const int nsplit = lm_splits((int)gridDim.y, t);
+  if ((int)blockIdx.x >= nsplit) return;
+  const int chunk = (t + nsplit - 1) / nsplit;
+  lm_decode_attn_body<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, t, H, chunk, scale, ctx, ctx_ld, nsplit > 1 ? ws : nullptr,
+                             blockIdx.y, blockIdx.x, nsplit);
+}
+
 // grid (C / 64, rows), one thread per output column: ctx[r, c] = sum_s e^(M_s - M) A_s / sum_s e^(M_s - M) L_s over the nsplit
 // partial states of row r.  (One column per thread keeps the nsplit loads of a thread independent of each other; a workgroup per
 // row that walked its columns in turn took ~100 us per launch at 5 rows.)
 template <typename T>
-__global__ void __launch_bounds__(64) lm_decode_combine_kernel(const float* __restrict__ ws, int nsplit, int H, int HD,
-                                                              T* __restrict__ ctx, int64_t ctx_ld) {
+__device__ __forceinline__ void lm_decode_combine_body(const float* __restrict__ ws, int nsplit, int H, int HD, T* __restrict__ ctx,
+                                                       int64_t ctx_ld) {
   const int r = blockIdx.y, C = H * HD;
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= C) return;
@@ -172,6 +200,19 @@ __global__ void __launch_bounds__(64) lm_decode_combine_kernel(const float* __re
     }
   }
   ctx[(int64_t)r * ctx_ld + c] = Elem<T>::from_f(A / L);
+}
+template <typename T>
+__global__ void __launch_bounds__(64) lm_decode_combine_kernel(const float* __restrict__ ws, int nsplit, int H, int HD,
+                                                              T* __restrict__ ctx, int64_t ctx_ld) {
+  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld);
+}
+// device-t form: nothing to combine while the step's key range is one workgroup's (the attention kernel wrote ctx itself)
+template <typename T>
+__global__ void __launch_bounds__(64) lm_decode_combine_dev_kernel(const float* __restrict__ ws, const int32_t* __restrict__ step, int t_add,
+                                                                  int t_max, int H, int HD, T* __restrict__ ctx, int64_t ctx_ld) {
+  const int nsplit = lm_splits((int)gridDim.y, lm_dev_t(step, t_add, t_max));
+  if (nsplit <= 1) return;
+  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld);
 }
 
 // anc_new[r, j] = anc[order[r], j] for j < t, = r for t <= j < Tmax (the row's own slots from position t on); an order entry
@@ -233,6 +274,22 @@ int launch_attn(const void* q, int64_t q_ld, const void* kv, int Tmax, int rows_
   return ST5_OK;
 }
 
+template <typename T, int HD>
+int launch_attn_dev(const void* q, int64_t q_ld, const void* kv, int Tmax, int rows_cap, const int32_t* anc, int64_t anc_ld, int rows,
+                    const int32_t* step, int t_add, int t_max, int H, void* ctx, int64_t ctx_ld, float* ws, hipStream_t st) {
+  const int nsplit = lm_splits(rows, t_max);
+  const float scale = 1.0f / sqrtf((float)HD);
+  hipLaunchKernelGGL((lm_decode_attn_dev_kernel<T, HD>), dim3(nsplit, rows), dim3(LM_THREADS), 0, st, static_cast<const T*>(q), q_ld,
+                     static_cast<const T*>(kv), Tmax, rows_cap, anc, anc_ld, step, t_add, t_max, H, scale, static_cast<T*>(ctx), ctx_ld, ws);
+  if (hipGetLastError() != hipSuccess) return ST5_ERR_LAUNCH;
+  if (nsplit > 1) {
+    hipLaunchKernelGGL((lm_decode_combine_dev_kernel<T>), dim3((H * HD + 63) / 64, rows), dim3(64), 0, st, ws, step, t_add, t_max, H, HD,
+                       static_cast<T*>(ctx), ctx_ld);
+    if (hipGetLastError() != hipSuccess) return ST5_ERR_LAUNCH;
+  }
+  return ST5_OK;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
@@ -261,6 +318,25 @@ extern "C" int st5_lm_decode_attn(const void* q, int64_t q_ld, const void* kv, i
                           : launch_attn<float, 64>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, rows, t, H, ctx, ctx_ld, ws, st);
   return head_dim == 80 ? launch_attn<bf16_t, 80>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, rows, t, H, ctx, ctx_ld, ws, st)
                         : launch_attn<bf16_t, 64>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, rows, t, H, ctx, ctx_ld, ws, st);
+}
+
+extern "C" int st5_lm_decode_attn_dev(const void* q, int64_t q_ld, const void* kv, int32_t rows_cap, int32_t Tmax, const int32_t* anc,
+                                      int64_t anc_ld, int32_t rows, const int32_t* step, int32_t t_add, int32_t t_max, int32_t H,
+                                      int32_t head_dim, void* ctx, int64_t ctx_ld, float* ws, int dtype, void* stream) {
+  if (!q || !kv || !anc || !ctx || !step) return ST5_ERR_ARG;
+  if (head_dim != 64 && head_dim != 80) return ST5_ERR_ARG;
+  if (dtype != ST5_F32 && dtype != ST5_BF16) return ST5_ERR_ARG;
+  if (rows <= 0 || rows > rows_cap || rows > 65535 || t_max <= 0 || t_max > Tmax || H <= 0 || H > LM_GROUPS) return ST5_ERR_ARG;
+  const int64_t C = (int64_t)H * head_dim;
+  if (q_ld < C || ctx_ld < C || anc_ld < t_max) return ST5_ERR_ARG;
+  if (lm_splits(rows, t_max) > 1 && !ws) return ST5_ERR_ARG;
+  const int64_t vec = dtype == ST5_F32 ? 4 : 8;
+  if (!aligned16(q) || !aligned16(kv) || q_ld % vec || (ws && !aligned16(ws))) return ST5_ERR_ALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define ST5_LM_DEV(T, HD) launch_attn_dev<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, rows, step, t_add, t_max, H, ctx, ctx_ld, ws, st)
+  if (dtype == ST5_F32) return head_dim == 80 ? ST5_LM_DEV(float, 80) : ST5_LM_DEV(float, 64);
+  return head_dim == 80 ? ST5_LM_DEV(bf16_t, 80) : ST5_LM_DEV(bf16_t, 64);
+#undef ST5_LM_DEV
 }
 
 extern "C" int st5_lm_reorder(const int32_t* anc, int64_t anc_ld, const int64_t* order, int32_t rows_old, int32_t rows_new, int32_t t,

@@ -40,6 +40,13 @@ __host__ __device__ inline int xa_splits(int B, int S) {
   return want < 2 ? 2 : want;
 }
 
+// offset of this step's record column when the step index lives on the device: clamp(*step, 0, cap - 1) * p_col (0 without a counter)
+__device__ __forceinline__ int64_t xa_step_off(const int32_t* step, int cap, int64_t p_col) {
+  if (!step) return 0;
+  const int s = *step;
+  return (int64_t)(s < 0 ? 0 : (s >= cap ? cap - 1 : s)) * p_col;
+}
+
 // 16 consecutive elements as floats: fp32 four 16-byte loads, bf16 two
 template <typename T>
 __device__ __forceinline__ void load16f(const T* p, float* v) {
@@ -56,7 +63,7 @@ template <typename T>
 __global__ void __launch_bounds__(XA_THREADS) decode_cross_attn_kernel(
     const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int64_t kv_ld, int64_t k_off, const uint8_t* __restrict__ kpm,
     int S, int H, int chunk, float scale, T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ probs, int64_t p_row,
-    int64_t p_head, float* __restrict__ ws) {
+    int64_t p_head, float* __restrict__ ws, const int32_t* __restrict__ step, int step_cap, int64_t p_col) {
   const int C = H * XA_HD;
   const int b = blockIdx.y, split = blockIdx.x, nsplit = gridDim.x;
   const int tid = threadIdx.x, g = tid >> 2, sub = tid & 3;
@@ -68,7 +75,7 @@ __global__ void __launch_bounds__(XA_THREADS) decode_cross_attn_kernel(
   const int col = h * XA_HD + sub * XA_EPL;
   const T* kvb = kv + (int64_t)b * S * kv_ld + k_off + col;
   const uint8_t* mb = kpm ? kpm + (int64_t)b * S : nullptr;
-  float* pb = probs ? probs + (int64_t)b * p_row + (int64_t)h * p_head : nullptr;
+  float* pb = probs ? probs + (int64_t)b * p_row + (int64_t)h * p_head + xa_step_off(step, step_cap, p_col) : nullptr;
 
   float qf[XA_EPL], acc[XA_EPL];
   float m = -INFINITY, l = 0.f;
@@ -153,7 +160,8 @@ __global__ void __launch_bounds__(XA_THREADS) decode_cross_attn_kernel(
 template <typename T>
 __global__ void __launch_bounds__(XA_THREADS) decode_cross_combine_kernel(const float* __restrict__ ws, int S, int H, int chunk,
                                                                           T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ probs,
-                                                                          int64_t p_row, int64_t p_head) {
+                                                                          int64_t p_row, int64_t p_head, const int32_t* __restrict__ step,
+                                                                          int step_cap, int64_t p_col) {
   const int b = blockIdx.y, split = blockIdx.x, nsplit = gridDim.x, tid = threadIdx.x;
   const int C = H * XA_HD;
   const int64_t stride = 2 * H + C;
@@ -189,9 +197,10 @@ __global__ void __launch_bounds__(XA_THREADS) decode_cross_combine_kernel(const 
     const int j0 = split * chunk;
     const int n = min(S, j0 + chunk) - j0;
     if (n <= 0) return;
+    const int64_t col_off = xa_step_off(step, step_cap, p_col);
     for (int i = tid; i < H * n; i += XA_THREADS) {
       const int h = i / n, j = j0 + i % n;
-      float* p = probs + (int64_t)b * p_row + (int64_t)h * p_head + j;
+      float* p = probs + (int64_t)b * p_row + (int64_t)h * p_head + j + col_off;
       *p = expf(*p - s_M[h]) / s_L[h];
     }
   }
@@ -199,17 +208,18 @@ __global__ void __launch_bounds__(XA_THREADS) decode_cross_combine_kernel(const 
 
 template <typename T>
 int launch_cross(const void* q, int64_t q_ld, const void* kv, int64_t kv_ld, int64_t k_off, const uint8_t* kpm, int B, int S, int H,
-                 void* ctx, int64_t ctx_ld, float* probs, int64_t p_row, int64_t p_head, float* ws, hipStream_t st) {
+                 void* ctx, int64_t ctx_ld, float* probs, int64_t p_row, int64_t p_head, float* ws, hipStream_t st,
+                 const int32_t* step = nullptr, int step_cap = 0, int64_t p_col = 0) {
   const int nsplit = xa_splits(B, S);
   const int chunk = (S + nsplit - 1) / nsplit;
   const float scale = 1.0f / sqrtf((float)XA_HD);
   hipLaunchKernelGGL((decode_cross_attn_kernel<T>), dim3(nsplit, B), dim3(XA_THREADS), 0, st, static_cast<const T*>(q), q_ld,
                      static_cast<const T*>(kv), kv_ld, k_off, kpm, S, H, chunk, scale, static_cast<T*>(ctx), ctx_ld, probs, p_row, p_head,
-                     nsplit > 1 ? ws : nullptr);
+                     nsplit > 1 ? ws : nullptr, step, step_cap, p_col);
   if (hipGetLastError() != hipSuccess) return ST5_ERR_LAUNCH;
   if (nsplit > 1) {
     hipLaunchKernelGGL((decode_cross_combine_kernel<T>), dim3(nsplit, B), dim3(XA_THREADS), 0, st, ws, S, H, chunk, static_cast<T*>(ctx),
-                       ctx_ld, probs, p_row, p_head);
+                       ctx_ld, probs, p_row, p_head, step, step_cap, p_col);
     if (hipGetLastError() != hipSuccess) return ST5_ERR_LAUNCH;
   }
   return ST5_OK;
@@ -220,10 +230,15 @@ __global__ void __launch_bounds__(TAIL_THREADS) tts_step_tail_kernel(
     const float* __restrict__ y, int64_t y_ld, int B, int r, int odim, const int32_t* __restrict__ minlen,
     const int32_t* __restrict__ maxlen, int32_t* __restrict__ done, int32_t* __restrict__ steps, int idx, float threshold,
     float* __restrict__ mel, int64_t mel_ld, float* __restrict__ prob, int64_t prob_ld, T* __restrict__ next, int64_t next_ld,
-    int32_t* __restrict__ active) {
+    int32_t* __restrict__ active, int32_t* __restrict__ counter, int cap, const unsigned long long* __restrict__ seed_table,
+    unsigned long long* __restrict__ seed_slots, int n_seeds) {
   __shared__ uint8_t live[TAIL_MAX_ROWS];
   __shared__ int part[TAIL_THREADS / 64];
   const int tid = threadIdx.x;
+  if (counter) {                               // step index on the device: this is step *counter + 1; past the cap nothing is written
+    idx = *counter + 1;
+    if (idx < 1 || idx > cap) return;
+  }
   const int F = r * odim;
   int running = 0;
   for (int b = tid; b < B; b += TAIL_THREADS) {
@@ -252,7 +267,9 @@ __global__ void __launch_bounds__(TAIL_THREADS) tts_step_tail_kernel(
 #pragma unroll
     for (int w = 0; w < TAIL_THREADS / 64; ++w) n += part[w];
     *active = n;
+    if (counter) *counter = idx;               // (every thread read it in front of the barrier above)
   }
+  if (counter && seed_table && tid < n_seeds && idx < cap) seed_slots[tid] = seed_table[(int64_t)idx * n_seeds + tid];
   for (int64_t i = tid; i < (int64_t)B * F; i += TAIL_THREADS) {
     const int b = (int)(i / F), e = (int)(i % F);
     if (live[b]) mel[(int64_t)b * mel_ld + (int64_t)(idx - 1) * F + e] = y[(int64_t)b * y_ld + e];
@@ -303,9 +320,82 @@ extern "C" int st5_tts_step_tail(const float* y, int64_t y_ld, int32_t B, int32_
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == ST5_F32)
     hipLaunchKernelGGL(tts_step_tail_kernel<float>, dim3(1), dim3(TAIL_THREADS), 0, st, y, y_ld, B, r, odim, minlen, maxlen, done, steps,
-                       idx, threshold, mel, mel_ld, probs, prob_ld, static_cast<float*>(next), next_ld, active);
+                       idx, threshold, mel, mel_ld, probs, prob_ld, static_cast<float*>(next), next_ld, active, nullptr, cap, nullptr, nullptr, 0);
   else
     hipLaunchKernelGGL(tts_step_tail_kernel<bf16_t>, dim3(1), dim3(TAIL_THREADS), 0, st, y, y_ld, B, r, odim, minlen, maxlen, done, steps,
-                       idx, threshold, mel, mel_ld, probs, prob_ld, static_cast<bf16_t*>(next), next_ld, active);
+                       idx, threshold, mel, mel_ld, probs, prob_ld, static_cast<bf16_t*>(next), next_ld, active, nullptr, cap, nullptr, nullptr, 0);
+  return hipGetLastError() == hipSuccess ? ST5_OK : ST5_ERR_LAUNCH;
+}
+
+// ---- the same three with the step index in device memory (one int32 counter c = steps completed, owned by the decode state) ----
+extern "C" int st5_decode_cross_attn_step(const void* q, int64_t q_ld, const void* kv, int64_t kv_ld, int64_t k_off, const uint8_t* kpm,
+                                          int32_t B, int32_t S, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld, float* probs,
+                                          int64_t p_row, int64_t p_head, int64_t p_col, const int32_t* step, int32_t cap, float* ws,
+                                          int dtype, void* stream) {
+  if (!q || !kv || !ctx) return ST5_ERR_ARG;
+  if (head_dim != XA_HD) return ST5_ERR_ARG;
+  if (dtype != ST5_F32 && dtype != ST5_BF16) return ST5_ERR_ARG;
+  if (B <= 0 || B > 65535 || S <= 0 || H <= 0 || H > XA_GROUPS) return ST5_ERR_ARG;
+  const int64_t C = (int64_t)H * head_dim;
+  if (q_ld < C || ctx_ld < C || k_off < 0 || kv_ld < k_off + 2 * C) return ST5_ERR_ARG;
+  if (probs && (!step || cap <= 0 || p_col < S || p_head < (int64_t)cap * p_col || p_row < (int64_t)H * p_head)) return ST5_ERR_ARG;
+  if (xa_splits(B, S) > 1 && !ws) return ST5_ERR_ARG;
+  const int64_t vec = dtype == ST5_F32 ? 4 : 8;
+  if (!aligned16(q) || !aligned16(kv) || q_ld % vec || kv_ld % vec || k_off % vec || (ws && !aligned16(ws))) return ST5_ERR_ALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == ST5_F32)
+    return launch_cross<float>(q, q_ld, kv, kv_ld, k_off, kpm, B, S, H, ctx, ctx_ld, probs, p_row, p_head, ws, st, step, cap, p_col);
+  return launch_cross<bf16_t>(q, q_ld, kv, kv_ld, k_off, kpm, B, S, H, ctx, ctx_ld, probs, p_row, p_head, ws, st, step, cap, p_col);
+}
+
+extern "C" int st5_tts_step_tail_dev(const float* y, int64_t y_ld, int32_t B, int32_t r, int32_t odim, const int32_t* minlen,
+                                     const int32_t* maxlen, int32_t* done, int32_t* steps, int32_t* counter, int32_t cap, float threshold,
+                                     float* mel, float* probs, void* next, int64_t next_ld, int32_t* active, const uint64_t* seed_table,
+                                     uint64_t* seed_slots, int32_t n_seeds, int dtype, void* stream) {
+  if (!y || !minlen || !maxlen || !done || !steps || !mel || !probs || !next || !active || !counter) return ST5_ERR_ARG;
+  if (dtype != ST5_F32 && dtype != ST5_BF16) return ST5_ERR_ARG;
+  if (B <= 0 || B > TAIL_MAX_ROWS || r <= 0 || odim <= 0 || cap < 1) return ST5_ERR_ARG;
+  if (y_ld < (int64_t)r * odim + r || next_ld < odim) return ST5_ERR_ARG;
+  if (n_seeds < 0 || n_seeds > TAIL_THREADS || (n_seeds > 0 && (!seed_table || !seed_slots))) return ST5_ERR_ARG;
+  const int64_t mel_ld = (int64_t)cap * r * odim, prob_ld = (int64_t)cap * r;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const unsigned long long* tab = reinterpret_cast<const unsigned long long*>(n_seeds ? seed_table : nullptr);
+  unsigned long long* slots = reinterpret_cast<unsigned long long*>(n_seeds ? seed_slots : nullptr);
+  if (dtype == ST5_F32)
+    hipLaunchKernelGGL(tts_step_tail_kernel<float>, dim3(1), dim3(TAIL_THREADS), 0, st, y, y_ld, B, r, odim, minlen, maxlen, done, steps,
+                       0, threshold, mel, mel_ld, probs, prob_ld, static_cast<float*>(next), next_ld, active, counter, cap, tab, slots, n_seeds);
+  else
+    hipLaunchKernelGGL(tts_step_tail_kernel<bf16_t>, dim3(1), dim3(TAIL_THREADS), 0, st, y, y_ld, B, r, odim, minlen, maxlen, done, steps,
+                       0, threshold, mel, mel_ld, probs, prob_ld, static_cast<bf16_t*>(next), next_ld, active, counter, cap, tab, slots, n_seeds);
+  return hipGetLastError() == hipSuccess ? ST5_OK : ST5_ERR_LAUNCH;
+}
+
+// y[b, :C] = x[b, :C] + alpha[0] * table[clamp(*step, 0, table_rows - 1), :C]: the scaled positional row of the step whose index lives
+// on the device (ScaledPEAdd with pos_offset = *step), written at a caller-chosen row stride (the left part of [x ; speaker] rows).
+template <typename T>
+__global__ void __launch_bounds__(256) tts_pe_add_step_kernel(const T* __restrict__ x, int64_t x_ld, const float* __restrict__ table,
+                                                              int table_rows, const float* __restrict__ alpha,
+                                                              const int32_t* __restrict__ step, T* __restrict__ y, int64_t y_ld, int C) {
+  const int b = blockIdx.x;
+  int s = *step;
+  s = s < 0 ? 0 : (s >= table_rows ? table_rows - 1 : s);
+  const float a = alpha[0];
+  const float* trow = table + (int64_t)s * C;
+  for (int c = threadIdx.x; c < C; c += 256)
+    y[(int64_t)b * y_ld + c] = Elem<T>::from_f(fmaf(a, trow[c], Elem<T>::to_f(x[(int64_t)b * x_ld + c])));
+}
+
+extern "C" int st5_tts_pe_add_step(const void* x, int64_t x_ld, const float* table, int32_t table_rows, const float* alpha,
+                                   const int32_t* step, void* y, int64_t y_ld, int32_t B, int32_t C, int dtype, void* stream) {
+  if (!x || !table || !alpha || !step || !y) return ST5_ERR_ARG;
+  if (dtype != ST5_F32 && dtype != ST5_BF16) return ST5_ERR_ARG;
+  if (B <= 0 || B > 65535 || C <= 0 || table_rows <= 0 || x_ld < C || y_ld < C) return ST5_ERR_ARG;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (dtype == ST5_F32)
+    hipLaunchKernelGGL(tts_pe_add_step_kernel<float>, dim3(B), dim3(256), 0, st, static_cast<const float*>(x), x_ld, table, table_rows, alpha,
+                       step, static_cast<float*>(y), y_ld, C);
+  else
+    hipLaunchKernelGGL(tts_pe_add_step_kernel<bf16_t>, dim3(B), dim3(256), 0, st, static_cast<const bf16_t*>(x), x_ld, table, table_rows,
+                       alpha, step, static_cast<bf16_t*>(y), y_ld, C);
   return hipGetLastError() == hipSuccess ? ST5_OK : ST5_ERR_LAUNCH;
 }

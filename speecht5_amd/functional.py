@@ -49,6 +49,16 @@ def next_seed():
     return ((_S.seed << 32) | (_S.counter & 0xFFFFFFFF)) & 0xFFFFFFFFFFFFFFFF
 
 
+def next_seeds(n):
+    """The next n dropout seeds of the host counter as an int64 CPU tensor: what n calls of next_seed() return, in order."""
+    import numpy as np
+    assert _S.slots is None
+    base = _S.counter
+    _S.counter += n
+    vals = (np.uint64(_S.seed) << np.uint64(32)) | ((np.arange(1, n + 1, dtype=np.uint64) + np.uint64(base)) & np.uint64(0xFFFFFFFF))
+    return torch.from_numpy(vals.astype(np.int64))
+
+
 class SeedSlots:
     """Device array of 64-bit seeds + its pinned host image; slot k of a step holds the k-th next_seed() of that step."""
 
@@ -3157,6 +3167,118 @@ def tts_step_tail(y, r, odim, minlen, maxlen, done, steps, idx, threshold, mel, 
     hip.check(hip.lib().st5_tts_step_tail(y.data_ptr(), y.stride(0), B, r, odim, minlen.data_ptr(), maxlen.data_ptr(), done.data_ptr(),
                                           steps.data_ptr(), int(idx), cap, float(threshold), mel.data_ptr(), probs.data_ptr(),
                                           nxt.data_ptr(), nxt.stride(0), active.data_ptr(), _dt(nxt), hip.stream()), "st5_tts_step_tail")
+
+
+# -------------------------------------------------------------------------------------------------
+# Decode-step kernels with the step index on the device (csrc/decode_gemm.hip and the *_dev / *_step entries of lm_decode.hip /
+# tts_decode.hip): what generate_speech_batch(decode="device" / "graph") launches.  Every wrapper writes into caller-owned buffers and
+# allocates nothing, so a step is the same launch sequence eagerly and under graph capture.  Inference only, no autograd.
+# -------------------------------------------------------------------------------------------------
+SKINNY_MAX_M = 32
+
+
+def gemm_skinny_ws(N, K, device):
+    """fp32 workspace of st5_gemm_skinny for an [N, K] weight (None when the product needs none)."""
+    n = int(hip.lib().st5_gemm_skinny_ws_bytes(N, K))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device) if n else None
+
+
+def linear_skinny(x, w, bias=None, *, out=None, act=ACT_NONE, residual=None, dropout_p=0.0, seed=0, out_f32=False, step=None,
+                  step_stride=0, step_cap=0, ws=None, out_ld=None):
+    """out = epilogue(x . w^T + bias) on the weight-streaming skinny-M kernel.  x [M, K] rows (compute dtype, row stride x.stride(0));
+    w [N, K] compute-dtype matrix (Fn.fused_weight of one or several nn.Linear weights); bias fp32 [N] or None; residual [M, N] rows.
+    out: tensor [M, N] rows (row stride out.stride(0)), or with `step` (int32 device scalar) the buffer whose slot
+    clamp(step, 0, step_cap - 1) receives the rows: row m lands at out + slot * step_stride + m * out_ld elements.  More than 32 rows
+    run as row chunks of 32 (row m's bits do not depend on the chunking).  Returns out."""
+    M, K = x.shape
+    N = w.shape[0]
+    assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and w.dtype == x.dtype
+    if out is None:
+        out = torch.empty(M, N, dtype=torch.float32 if out_f32 else x.dtype, device=x.device)
+    assert out.dtype == (torch.float32 if out_f32 else x.dtype)
+    if out_ld is None:
+        assert out.dim() == 2 and out.stride(1) == 1
+        out_ld = out.stride(0)
+    if ws is None:
+        ws = gemm_skinny_ws(N, K, x.device)
+    L = hip.lib()
+    st = hip.stream()
+    es, eo = x.element_size(), out.element_size()
+    for m0 in range(0, M, SKINNY_MAX_M):
+        m = min(SKINNY_MAX_M, M - m0)
+        hip.check(L.st5_gemm_skinny(x.data_ptr() + m0 * x.stride(0) * es, x.stride(0), w.data_ptr(), w.stride(0), hip.ptr(bias),
+                                    0 if residual is None else residual.data_ptr() + m0 * residual.stride(0) * es,
+                                    0 if residual is None else residual.stride(0), out.data_ptr() + m0 * out_ld * eo, out_ld, m, N, K,
+                                    int(act), float(dropout_p), int(seed), m0, int(bool(out_f32)), hip.ptr(step), int(step_stride),
+                                    int(step_cap), hip.ptr(ws), _dt(x), st), "st5_gemm_skinny")
+    return out
+
+
+def lm_decode_attn_dev(q, kv, anc, step, t_add, t_max, H, hd, ctx, ws):
+    """lm_decode_attn for t = clamp(step + t_add, 1, t_max) with `step` an int32 device scalar; ctx [rows, C] and ws (lm_decode_attn_ws
+    for t_max) are the caller's.  Bit-equal to lm_decode_attn(t)."""
+    rows = q.shape[0]
+    C = H * hd
+    assert kv.shape[2] == 2 * C and kv.is_contiguous() and anc.dtype == torch.int32 and anc.stride(1) == 1 and q.stride(1) == 1
+    assert kv.dtype == q.dtype == ctx.dtype and ctx.stride(1) == 1 and step.dtype == torch.int32
+    hip.check(hip.lib().st5_lm_decode_attn_dev(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.shape[0], kv.shape[1], anc.data_ptr(),
+                                               anc.stride(0), rows, step.data_ptr(), int(t_add), int(t_max), H, hd, ctx.data_ptr(),
+                                               ctx.stride(0), hip.ptr(ws), _dt(q), hip.stream()), "st5_lm_decode_attn_dev")
+    return ctx
+
+
+def decode_cross_attn_step(q, kv, k_off, S, H, hd, ctx, step, cap, kpm=None, rec=None, ws=None):
+    """decode_cross_attn whose record column is the int32 device scalar `step` (clamped into [0, cap)): rec fp32 [B, H, cap, S] view
+    (strides (row, head, S, 1)) or None; ctx [B, C] is the caller's."""
+    B = q.shape[0]
+    assert kv.stride(1) == 1 and q.stride(1) == 1 and kv.dtype == q.dtype == ctx.dtype and kv.shape[0] == B * S
+    p_row = p_head = p_col = 0
+    if rec is not None:
+        assert rec.dtype == torch.float32 and rec.shape == (B, H, cap, S) and rec.stride(3) == 1
+        p_row, p_head, p_col = rec.stride(0), rec.stride(1), rec.stride(2)
+    hip.check(hip.lib().st5_decode_cross_attn_step(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), int(k_off), hip.ptr(kpm), B, S,
+                                                   H, hd, ctx.data_ptr(), ctx.stride(0), hip.ptr(rec), p_row, p_head, p_col,
+                                                   step.data_ptr(), int(cap), hip.ptr(ws), _dt(q), hip.stream()),
+              "st5_decode_cross_attn_step")
+    return ctx
+
+
+def tts_step_tail_dev(y, r, odim, minlen, maxlen, done, steps, counter, threshold, mel, probs, nxt, active, seed_table=None,
+                      seed_slots=None):
+    """tts_step_tail for step idx = counter + 1 (int32 device scalar), which it then advances; nothing is written once counter >= cap.
+    seed_table int64 [cap, n] / seed_slots int64 [n]: the next step's n dropout seeds are moved into the slots."""
+    B = y.shape[0]
+    cap = probs.shape[1] // r
+    assert y.dtype == torch.float32 and y.stride(1) == 1 and nxt.stride(1) == 1 and counter.dtype == torch.int32
+    assert mel.is_contiguous() and probs.is_contiguous() and mel.shape == (B, cap * r, odim) and probs.shape == (B, cap * r)
+    n = 0
+    if seed_table is not None:
+        n = seed_slots.numel()
+        assert seed_table.dtype == seed_slots.dtype == torch.int64 and seed_table.is_contiguous() and seed_table.shape == (cap, n)
+    hip.check(hip.lib().st5_tts_step_tail_dev(y.data_ptr(), y.stride(0), B, r, odim, minlen.data_ptr(), maxlen.data_ptr(), done.data_ptr(),
+                                              steps.data_ptr(), counter.data_ptr(), cap, float(threshold), mel.data_ptr(),
+                                              probs.data_ptr(), nxt.data_ptr(), nxt.stride(0), active.data_ptr(), hip.ptr(seed_table),
+                                              hip.ptr(seed_slots), n, _dt(nxt), hip.stream()), "st5_tts_step_tail_dev")
+
+
+def tts_pe_add_step(x, table, alpha, step, y):
+    """y[:, :C] = x + alpha * table[clamp(step, 0, rows - 1)] (ScaledPEAdd at the position held by the int32 device scalar `step`);
+    y may be wider rows than x (its row stride is used)."""
+    B, C = x.shape
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] == C and x.stride(1) == 1 and y.stride(1) == 1
+    hip.check(hip.lib().st5_tts_pe_add_step(x.data_ptr(), x.stride(0), table.data_ptr(), table.shape[0], alpha.data_ptr(),
+                                            step.data_ptr(), y.data_ptr(), y.stride(0), B, C, _dt(x), hip.stream()),
+              "st5_tts_pe_add_step")
+    return y
+
+
+def layer_norm_into(x, weight, bias, eps, y, stats):
+    """y = LayerNorm(x) into the caller's buffer (inference; stats: fp32 [2, rows] scratch for the kernel's mean / rstd)."""
+    rows, cols = x.shape
+    assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape and stats.numel() >= 2 * rows
+    hip.check(hip.lib().st5_layernorm_fwd(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), stats.data_ptr(),
+                                          stats.data_ptr() + 4 * rows, rows, cols, float(eps), _dt(x), hip.stream()), "st5_layernorm_fwd")
+    return y
 
 
 # -------------------------------------------------------------------------------------------------

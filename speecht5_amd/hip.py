@@ -209,6 +209,18 @@ _SIGS = {
                                       c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
     "st5_tts_step_tail": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
                                   c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "st5_gemm_skinny_ws_bytes": (c_int64, [c_int32, c_int32]),
+    "st5_gemm_skinny": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32,
+                                c_int32, c_float, c_uint64, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int, c_void_p]),
+    "st5_lm_decode_attn_dev": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32,
+                                       c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "st5_decode_cross_attn_step": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int,
+                                           c_void_p]),
+    "st5_tts_step_tail_dev": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                      c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int, c_void_p]),
+    "st5_tts_pe_add_step": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int,
+                                    c_void_p]),
     "st5_angular_margin_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
     "st5_angular_margin_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float,
                                        c_float, c_void_p]),

@@ -622,14 +622,28 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
                     break
         return mel_rec, prob_rec, rec, steps.tolist(), T_in
 
+    def _decode_rows_mode(self, decode, source, src_tokens, spkembs, padding_mask, need_attn, **kwargs):
+        """_decode_rows in the requested mode: "eager" (the loop above), "device" (every kernel of a step reads the step index from
+        device memory: speecht5_amd/tts_graph.py) or "graph" (that step captured once and replayed).  Records what ran in
+        tts_decode_mode / tts_polls / tts_device_steps / tts_graph_replays."""
+        from . import tts_graph
+        if decode not in tts_graph.DECODE_MODES:
+            raise ValueError(f"decode must be one of {tts_graph.DECODE_MODES}, got {decode!r}")
+        self.tts_decode_mode, self.tts_device_steps, self.tts_graph_replays = decode, 0, 0
+        if decode == "eager":
+            return self._decode_rows(source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
+        return tts_graph.decode_rows(self, source, src_tokens, spkembs, padding_mask, need_attn, decode, **kwargs)
+
     @torch.no_grad()
-    def generate_speech_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, need_attn=True, **kwargs):
+    def generate_speech_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, need_attn=True, decode="eager",
+                              **kwargs):
         """generate_speech for B utterances in one decode loop.  Returns B tuples (mel [L_b, odim], probs [L_b], attn
         [decoder_layers, H, L_b / r, S_b] or None) in row order, each as generate_speech returns it for that row alone.  Text rows
         are right-padded (TextToSpeechCollater); speech rows come with `padding_mask`.  Row b stops at the first step idx >= minlen_b
         at which one of its r stop probabilities reaches `threshold` or idx >= maxlen_b; rows that stopped keep computing (their
-        records are final) until the host sees no active row, every TTS_POLL_STEPS steps."""
-        mel_rec, prob_rec, rec, L, T_in = self._decode_rows(source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
+        records are final) until the host sees no active row, every TTS_POLL_STEPS steps.  decode: "eager" (default), or the
+        device-stepped loop on the skinny-M GEMM kernel launched kernel by kernel ("device") or replayed from a HIP graph ("graph")."""
+        mel_rec, prob_rec, rec, L, T_in = self._decode_rows_mode(decode, source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
         post, r = self.speech_decoder_postnet, self.reduction_factor
         out = []
         for b in range(len(L)):
@@ -642,15 +656,15 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
 
     @torch.no_grad()
     def synthesize_batch(self, source=None, src_tokens=None, spkembs=None, padding_mask=None, vocoder=None, need_attn=False,
-                         max_frames=None, **kwargs):
+                         max_frames=None, decode="eager", **kwargs):
         """B texts (or B source clips) in, B waveforms out: the decode loop of generate_speech_batch, then the mel post-net and the
         HiFi-GAN `vocoder` over packed sequences (speecht5_amd/ragged.py) instead of once per row.  Returns B tuples (wav fp32
         [hop * L_b] or None without a vocoder, mel [L_b, odim], probs [L_b], attn or None), each row what generate_speech, the
         post-net and vocoder.forward give for that row alone.  The mel records are packed on the device straight from the decode
         loop's record; one layout (the vocoder's gap when there is one) serves the post-net and the vocoder.  Rows go in order into
-        chunks of at most `max_frames` mel frames (default: the vocoder's byte budget)."""
+        chunks of at most `max_frames` mel frames (default: the vocoder's byte budget).  decode: as in generate_speech_batch."""
         from . import ragged
-        mel_rec, prob_rec, rec, steps, T_in = self._decode_rows(source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
+        mel_rec, prob_rec, rec, steps, T_in = self._decode_rows_mode(decode, source, src_tokens, spkembs, padding_mask, need_attn, **kwargs)
         post, r = self.speech_decoder_postnet, self.reduction_factor
         B, rows_per, odim = mel_rec.shape
         lengths = [n * r for n in steps]
