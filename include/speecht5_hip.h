@@ -587,6 +587,23 @@ int st5_layernorm_set_max_blocks(int n);
 int st5_ctc_initial_state(const float* x, int32_t T, int32_t V, int32_t blank, float* r, void* stream);
 int st5_ctc_prefix_score(const float* x, int32_t T, int32_t V, int32_t blank, int32_t eos, const float* r_prev, const int64_t* last,
                          int32_t out_len, const int64_t* cs, int32_t nh, int32_t nc, float* log_psi, float* r_new, void* stream);
+/* Rows form, for a batch: x [S][Tmax][V] right-padded in time, lens[S] int32 (device) the sentences' frame counts, sent[nh] int32
+ * (device) the sentence of each hypothesis row.  Per (row, candidate) pair the arithmetic is st5_ctc_prefix_score's on
+ * x[sent[h]][:lens[sent[h]]], bit for bit; no frame at or behind a sentence's count is read.  out_len may exceed a sentence's
+ * frame count: eos scores logaddexp(r_prev[T_s - 1]), every other candidate logzero, the state is logzero.
+ * st5_ctc_initial_state_rows: r[S][Tmax][2], logzero behind each sentence's frames.
+ * st5_ctc_prefix_score_rows: r_prev[nh][Tmax][2]; log_psi[nh][nc]; r_new[nh][Tmax][nc][2] (candidates innermost), written for
+ * frames < lens[sent[h]] only.
+ * st5_ctc_select_rows: for n continued hypotheses, parent[n] (row of that launch) and token[n] (int64): state[n][Tmax][2] of the
+ * extension (logzero behind the frames), prev_psi[n] its log_psi, known[n] (uint8) 0 when the token is not in cs[parent[n]]
+ * (slot 0 is gathered then), sent_out[n] (int32, may be NULL) = sent[parent[n]]. */
+int st5_ctc_initial_state_rows(const float* x, const int32_t* lens, int32_t S, int32_t Tmax, int32_t V, int32_t blank, float* r, void* stream);
+int st5_ctc_prefix_score_rows(const float* x, const int32_t* lens, const int32_t* sent, int32_t S, int32_t Tmax, int32_t V, int32_t blank,
+                              int32_t eos, const float* r_prev, const int64_t* last, int32_t out_len, const int64_t* cs, int32_t nh,
+                              int32_t nc, float* log_psi, float* r_new, void* stream);
+int st5_ctc_select_rows(const int32_t* lens, const int32_t* sent, int32_t S, int32_t Tmax, const int64_t* cs, int32_t nh, int32_t nc,
+                        const float* log_psi, const float* r_new, const int64_t* parent, const int64_t* token, int32_t n, float* state,
+                        float* prev_psi, uint8_t* known, int32_t* sent_out, void* stream);
 /* ---- shallow-fusion LM decoding (csrc/lm_decode.hip): replaces the full-prefix LM call of ASR beam search,
  * SpeechT5/speecht5/sequence_generator.py:420-425 (lm_model(tokens[:, :step + 1]) + log_softmax + lprobs[:, :V_lm] += w * probs) ----
  * Slot cache of one layer: kv [rows_cap][Tmax][2C] (compute dtype, C = H * head_dim): slot (r, j) = [k | v] of hypothesis row r at

@@ -199,6 +199,11 @@ _SIGS = {
     "st5_ctc_initial_state": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "st5_ctc_prefix_score": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_int32,
                                      c_void_p, c_void_p, c_void_p]),
+    "st5_ctc_initial_state_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
+    "st5_ctc_prefix_score_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                          c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "st5_ctc_select_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "st5_lm_decode_attn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "st5_lm_decode_attn": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_int32, c_int32, c_int32,
                                    c_void_p, c_int64, c_void_p, c_int, c_void_p]),

@@ -8,6 +8,8 @@ over beam x vocabulary of cumulative log-probabilities, first step from the firs
 the top `beam` are finalized, finished sentences leave the batch, length normalisation by (len)^lenpen.  With --ctc-weight > 0
 every step re-scores the best `7 x beam` next tokens of each hypothesis with the CTC prefix probability of the FIRST sentence's
 encoder output (sequence_generator.py:273-284, 370-418):  lprob' = (1 - w) lprob + w (log psi(h.c) - log psi(h)).
+`ctc_rows=True` (not in the reference, off by default) scores every sentence against its own posterior and frame count instead,
+which is what makes the joint recipe batchable (CTCPrefixScorerRows, the st5_ctc_*_rows entries of csrc/ctc_prefix.hip).
 
 What differs is where it runs: the reference moves every hypothesis to the host, scores it with numpy and keeps the prefix
 states in a Python dict keyed by the token string (one device sync per hypothesis and step); here the CTC posterior, the
@@ -104,6 +106,60 @@ class CTCPrefixScorer:
         return log_psi, r_new
 
 
+class CTCPrefixScorerRows:
+    """Device-resident CTC prefix scorer over a BATCH of posteriors x [S, Tmax, V] (fp32 log-probabilities, right-padded in time),
+    sentence s on its own frames x[s, :lens[s]].  state: r [n, Tmax, 2] (LOGZERO behind the sentence's frames);  score(): log psi
+    [n, nc] and the extensions' states [n, Tmax, nc, 2] (candidates innermost; frames behind the sentence's are left unwritten);
+    select(): the states, prefix scores and sentences of the hypotheses that continue.  Per (row, candidate) pair the arithmetic is
+    CTCPrefixScorer's on the sentence's own slice, bit for bit."""
+
+    def __init__(self, x, lens, blank, eos):
+        if not x.is_cuda:
+            raise hip.HipKernelError("CTCPrefixScorerRows needs the CTC posterior on the GPU (there is no CPU path)")
+        self.x = x.detach().float().contiguous()
+        self.S, self.T, self.V = self.x.shape
+        self.lens = lens.to(device=self.x.device, dtype=torch.int32).contiguous()
+        if self.lens.numel() != self.S:
+            raise ValueError(f"{self.lens.numel()} lengths for {self.S} sentences")
+        self.blank, self.eos = int(blank), int(eos)
+
+    def initial_state(self):
+        r = torch.empty(self.S, self.T, 2, dtype=torch.float32, device=self.x.device)
+        hip.check(hip.lib().st5_ctc_initial_state_rows(self.x.data_ptr(), self.lens.data_ptr(), self.S, self.T, self.V, self.blank,
+                                                       r.data_ptr(), hip.stream()), "st5_ctc_initial_state_rows")
+        return r
+
+    def score(self, sent, last, out_len, cs, r_prev):
+        """sent [n] int32: each row's sentence (an index into x); last [n] int64; out_len: labels after <sos>; cs [n, nc] int64;
+        r_prev [n, Tmax, 2]."""
+        n, nc = cs.shape
+        assert sent.dtype == torch.int32 and sent.numel() == n and tuple(r_prev.shape) == (n, self.T, 2)
+        log_psi = torch.empty(n, nc, dtype=torch.float32, device=self.x.device)
+        r_new = torch.empty(n, self.T, nc, 2, dtype=torch.float32, device=self.x.device)
+        hip.check(hip.lib().st5_ctc_prefix_score_rows(self.x.data_ptr(), self.lens.data_ptr(), sent.contiguous().data_ptr(), self.S, self.T,
+                                                      self.V, self.blank, self.eos, r_prev.contiguous().data_ptr(),
+                                                      last.contiguous().data_ptr(), int(out_len), cs.contiguous().data_ptr(), n, nc,
+                                                      log_psi.data_ptr(), r_new.data_ptr(), hip.stream()), "st5_ctc_prefix_score_rows")
+        return log_psi, r_new
+
+    def select(self, sent, cs, log_psi, r_new, parent, token):
+        """parent [m] int64: rows of the score() call that gave (sent, cs, log_psi, r_new); token [m] int64.  Returns the state
+        [m, Tmax, 2], the prefix score [m], known [m] bool (False: the token was not among the parent's candidates) and the
+        sentence [m] int32 of every continued hypothesis."""
+        n, nc = cs.shape
+        m = parent.numel()
+        dev = self.x.device
+        state = torch.empty(m, self.T, 2, dtype=torch.float32, device=dev)
+        prev = torch.empty(m, dtype=torch.float32, device=dev)
+        known = torch.empty(m, dtype=torch.bool, device=dev)
+        sent_out = torch.empty(m, dtype=torch.int32, device=dev)
+        hip.check(hip.lib().st5_ctc_select_rows(self.lens.data_ptr(), sent.contiguous().data_ptr(), self.S, self.T, cs.contiguous().data_ptr(),
+                                                n, nc, log_psi.data_ptr(), r_new.data_ptr(), parent.contiguous().data_ptr(),
+                                                token.contiguous().data_ptr(), m, state.data_ptr(), prev.data_ptr(), known.data_ptr(),
+                                                sent_out.data_ptr(), hip.stream()), "st5_ctc_select_rows")
+        return state, prev, known, sent_out
+
+
 def _is_hip_lm(lm):
     from .transformer_lm import TransformerLanguageModel
     return isinstance(lm, TransformerLanguageModel)
@@ -119,12 +175,15 @@ class SequenceGenerator(nn.Module):
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
                  search_strategy=None, eos=None, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, ctc_weight=0.0,
-                 exact_rows=False):
+                 exact_rows=False, ctc_rows=False):
         """`exact_rows`: speech input is encoded through forward_encoder_rows, so that a row's hypotheses do not depend on what else
-        is in its batch (off, the default: the reference's padded batch)."""
+        is in its batch (off, the default: the reference's padded batch).
+        `ctc_rows`: with ctc_weight > 0 every sentence is re-scored against its OWN CTC posterior and frame count
+        (CTCPrefixScorerRows; off, the default: the reference's way, every sentence against sentence 0's)."""
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)
         self.exact_rows = bool(exact_rows)      # (the generator's own: an EnsembleModel may serve several generators)
+        self.ctc_rows = bool(ctc_rows)
         self.tgt_dict = tgt_dict
         self.pad, self.unk = tgt_dict.pad(), tgt_dict.unk()
         self.eos = tgt_dict.eos() if eos is None else eos
@@ -210,9 +269,19 @@ class SequenceGenerator(nn.Module):
         ctc = None
         if self.ctc_weight > 0:
             post = self.model.models[0].get_normalized_probs_for_ctc(encoder_outs[0], log_probs=True).transpose(0, 1)  # B x T x V
-            ctc = CTCPrefixScorer(post[0], self.blank, self.eos)
             ctc_beam = min(post.shape[-1] - self.mask_idxs.numel(), int(beam * CTC_SCORING_RATIO))
-            ctc_state = ctc.initial_state().unsqueeze(0).repeat(bsz * beam, 1, 1)        # [rows, T, 2]
+            if self.ctc_rows:
+                # every sentence against its own posterior and frame count; ctc_sent: the ORIGINAL sentence of each live row
+                pm = encoder_outs[0]["encoder_padding_mask"]
+                pm = pm[0] if isinstance(pm, (list, tuple)) and len(pm) > 0 else (pm if isinstance(pm, Tensor) else None)
+                frames = torch.full((bsz,), post.size(1), dtype=torch.int32, device=dev) if pm is None or pm.numel() == 0 \
+                    else (post.size(1) - pm.sum(dim=1)).to(torch.int32)
+                ctc = CTCPrefixScorerRows(post, frames, self.blank, self.eos)
+                ctc_sent = torch.arange(bsz, dtype=torch.int32, device=dev).repeat_interleave(beam)
+                ctc_state = ctc.initial_state().repeat_interleave(beam, dim=0)           # [rows, Tmax, 2]
+            else:
+                ctc = CTCPrefixScorer(post[0], self.blank, self.eos)
+                ctc_state = ctc.initial_state().unsqueeze(0).repeat(bsz * beam, 1, 1)    # [rows, T, 2]
             ctc_prev = torch.zeros(bsz * beam, dtype=torch.float32, device=dev)          # log psi of each row's prefix
             ctc_known = torch.ones(bsz * beam, dtype=torch.bool, device=dev)             # row's prefix was re-scored when created
 
@@ -254,11 +323,15 @@ class SequenceGenerator(nn.Module):
                                    f"(ctc_beam={ctc_beam}); its prefix state does not exist")
                 cand_lp = self._never(lprobs.clone())
                 cs = torch.topk(cand_lp, ctc_beam, dim=-1)[1]                              # [rows, ctc_beam]
-                log_psi, states = ctc.score(tokens[:, step], step, cs, ctc_state)
+                if self.ctc_rows:
+                    log_psi, states = ctc.score(ctc_sent, tokens[:, step], step, cs, ctc_state)
+                else:
+                    log_psi, states = ctc.score(tokens[:, step], step, cs, ctc_state)
                 mixed = (1 - self.ctc_weight) * lprobs.gather(1, cs) + self.ctc_weight * (log_psi - ctc_prev.unsqueeze(1))
                 lprobs.scatter_(1, cs, mixed.to(lprobs.dtype))
-                slot_of = torch.full_like(lprobs, -1, dtype=torch.long).scatter_(
-                    1, cs, torch.arange(ctc_beam, device=dev).expand_as(cs))
+                if not self.ctc_rows:
+                    slot_of = torch.full_like(lprobs, -1, dtype=torch.long).scatter_(
+                        1, cs, torch.arange(ctc_beam, device=dev).expand_as(cs))
 
             if lm_state is not None:
                 hip_fuse_lm(lprobs, self.lm_model.decode_step(tokens[:, step], lm_state), self.lm_weight)
@@ -348,11 +421,17 @@ class SequenceGenerator(nn.Module):
             if ctc is not None:
                 # prefix state of every continued hypothesis = the re-scored extension (parent row, candidate slot) of this step
                 parent_old = active_bbsz_idx if keep_rows is None else keep_rows[active_bbsz_idx]
-                slot = slot_of[parent_old, next_tokens.view(-1)]
-                ctc_known = slot.ge(0) | cands_to_ignore.view(-1)        # (ignored rows hold finished hypotheses)
-                slot_c = slot.clamp(min=0)
-                ctc_state = states[parent_old, slot_c]
-                ctc_prev = log_psi[parent_old, slot_c]
+                if self.ctc_rows:
+                    # (parent_old indexes this step's launch, so ctc_sent follows the rows through the shrink as well)
+                    ctc_state, ctc_prev, ctc_known, ctc_sent = ctc.select(ctc_sent, cs, log_psi, states, parent_old,
+                                                                          next_tokens.view(-1))
+                    ctc_known = ctc_known | cands_to_ignore.view(-1)     # (ignored rows hold finished hypotheses)
+                else:
+                    slot = slot_of[parent_old, next_tokens.view(-1)]
+                    ctc_known = slot.ge(0) | cands_to_ignore.view(-1)    # (ignored rows hold finished hypotheses)
+                    slot_c = slot.clamp(min=0)
+                    ctc_state = states[parent_old, slot_c]
+                    ctc_prev = log_psi[parent_old, slot_c]
 
             tokens[:, : step + 1] = torch.index_select(tokens[:, : step + 1], dim=0, index=active_bbsz_idx)
             tokens.view(bsz, beam, -1)[:, :, step + 1] = next_tokens
