@@ -682,6 +682,24 @@ int st5_sumsq_pair(const float* x, const float* y, float* out, int64_t n, float 
 int st5_multi_transpose_bf16(const void* src_flat, void* dst_flat, const void* jobs_dev, int32_t njobs, int32_t ntiles,
                              void* stream);
 
+/* ---- Beam search over a slot cache (SequenceGenerator(decode="slots"); csrc/beam_decode.hip) ----
+ * st5_beam_cross_attn (multihead_attention.py:340-389 with one query per hypothesis row r, rows = n_live * beam): row r belongs to live
+ * sentence r / beam and reads the K/V block of original sentence s = sent[r / beam] (int32 [n_live]), of which all beam rows share
+ * ONE copy: ctx[r][h*64 + i] = softmax_j(q[r] . k_j * 64^-0.5) v_j over the S encoder positions of sentence s,
+ * k_j = kv[(s*S + j)*kv_ld + k_off + h*64 ...], v_j at + H*64 (one projection may hold all layers' K|V side by side); a set byte
+ * kpm[s*S + j] (uint8 [n_sent][S], or NULL) excludes key j.  Scores, softmax and accumulation fp32; ctx [rows][ctx_ld] and
+ * q [rows][q_ld] in `dtype`.  probs (fp32, or NULL): probs[r*p_row + h*p_head + j] = the probability of key j (exactly 0 at an
+ * excluded key); nothing else of the record is written, and ctx is the same bits with and without it.  A K/V element is read once per
+ * sentence and step (a workgroup covers up to 16 rows of a sentence; larger beams take further row groups).  The key-range split and
+ * the reduction order are a function of (S, H, head_dim, dtype): a row's ctx bits do not depend on n_live, beam or the other rows.
+ * No atomics.  head_dim 64 only and H <= 64, else ST5_ERR_ARG.  q / kv 16-byte aligned and q_ld, kv_ld, k_off multiples of 4 (fp32) /
+ * 8 (bf16), else ST5_ERR_ALIGN.  A sent entry outside [0, n_sent) gives NaN in that sentence's rows (ctx and record) and is never
+ * dereferenced.  ws: fp32 workspace of st5_beam_cross_attn_ws_bytes(rows, S, H, head_dim) bytes (16-byte aligned; NULL when 0). */
+int64_t st5_beam_cross_attn_ws_bytes(int32_t rows, int32_t S, int32_t H, int32_t head_dim);
+int st5_beam_cross_attn(const void* q, int64_t q_ld, const void* kv, int64_t kv_ld, int64_t k_off, const uint8_t* kpm, const int32_t* sent,
+                        int32_t n_sent, int32_t n_live, int32_t beam, int32_t S, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld,
+                        float* probs, int64_t p_row, int64_t p_head, float* ws, int dtype, void* stream);
+
 /* Skinny-M GEMM of the decode loops (csrc/decode_gemm.hip): out[m, n] = epilogue(sum_k x[m, k] * w[n, k] + bias[n]) for 1 <= M <= 32,
  * w in nn.Linear layout [N, K] (stacked weights are one [sum N_i, K] matrix), x / w / res in `dtype`, fp32 accumulation.  Weight-streaming:
  * every weight byte is read once; row m of out depends on row m of x only (same bits for any M and any other rows); the reduction order

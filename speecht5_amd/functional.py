@@ -3155,6 +3155,38 @@ def decode_cross_attn(q, kv, k_off, S, H, hd, kpm=None, probs=None, ws=None):
     return ctx
 
 
+# -------------------------------------------------------------------------------------------------
+# Beam search over a slot cache (csrc/beam_decode.hip): one-query cross-attention in which the `beam` hypothesis rows of a sentence
+# share one copy of that sentence's projected encoder K|V.  Inference only, no autograd.
+# -------------------------------------------------------------------------------------------------
+def beam_cross_attn_ws(rows, S, H, hd, device):
+    """fp32 workspace of st5_beam_cross_attn for `rows` hypothesis rows over S keys (None when that launch needs none)."""
+    n = int(hip.lib().st5_beam_cross_attn_ws_bytes(rows, S, H, hd))
+    return torch.empty((n + 3) // 4, dtype=torch.float32, device=device) if n else None
+
+
+def beam_cross_attn(q, kv, k_off, sent, n_sent, beam, S, H, hd, kpm=None, probs=None, ws=None):
+    """q [n_live * beam, >= C] (compute dtype, row stride q.stride(0)); kv [n_sent * S, kv_ld] rows holding this layer's K at column
+    k_off and V at k_off + C, once per sentence; sent int32 [n_live]: row r reads the block of sentence sent[r // beam]; kpm uint8
+    [n_sent, S] (1 = padded key) or None.  probs: None, or (fp32 tensor whose first element is row 0 / head 0 / key 0 of the record,
+    row stride, head stride).  Returns ctx [n_live * beam, C]."""
+    rows = q.shape[0]
+    n_live = sent.numel()
+    C = H * hd
+    assert rows == n_live * beam and sent.dtype == torch.int32 and sent.is_contiguous()
+    assert kv.stride(1) == 1 and q.stride(1) == 1 and kv.dtype == q.dtype and kv.shape[0] == n_sent * S
+    assert kpm is None or (kpm.dtype == torch.uint8 and kpm.is_contiguous() and kpm.shape == (n_sent, S))
+    if ws is None or ws.numel() * 4 < hip.lib().st5_beam_cross_attn_ws_bytes(rows, S, H, hd):
+        ws = beam_cross_attn_ws(rows, S, H, hd, q.device)
+    p, p_row, p_head = probs if probs is not None else (None, 0, 0)
+    assert p is None or p.dtype == torch.float32
+    ctx = torch.empty(rows, C, dtype=q.dtype, device=q.device)
+    hip.check(hip.lib().st5_beam_cross_attn(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), int(k_off), hip.ptr(kpm),
+                                            sent.data_ptr(), n_sent, n_live, beam, S, H, hd, ctx.data_ptr(), C, hip.ptr(p), p_row, p_head,
+                                            hip.ptr(ws), _dt(q), hip.stream()), "st5_beam_cross_attn")
+    return ctx
+
+
 def tts_step_tail(y, r, odim, minlen, maxlen, done, steps, idx, threshold, mel, probs, nxt, active):
     """Step idx (1-based) of B rows: y fp32 [B, >= r*odim + r]; int32 [B] minlen / maxlen / done / steps; records mel [B, cap*r, odim]
     and probs [B, cap*r] fp32; nxt [B, odim] (compute dtype) the next decoder input; active int32 [1] (rows still running)."""

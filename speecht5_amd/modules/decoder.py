@@ -6,12 +6,32 @@ from .. import functional as Fn
 from ..fairseq_compat import FairseqIncrementalDecoder
 from .common import LayerNorm
 from .encoder import RelativePositionalEncoding
+from .multihead_attention import _mask_bytes
 from .transformer_layer import TransformerDecoderLayer
 
 
 def state_B(state, rows):
     """Batch size of a cached [B*S, C] row tensor (S is recorded when the encoder rows are first cached)."""
     return rows.shape[0] // state["S"]
+
+
+class BeamSlotState:
+    """Per-generate() state of beam search over a slot cache (TransformerDecoder.init_beam_slots).
+    kv[l] [rows, Tmax, 2C]: self-attention slot cache of layer l, slot (r, j) = [k | v] that hypothesis row r produced at position j,
+    written once; anc [rows, Tmax] int32 (one table for all layers, double-buffered: a reorder gathers into the other buffer): row r
+    reads position j from slot (anc[r, j], j); t: positions written.  enc_rows [n_sent * S, C]: the encoder rows, once per SENTENCE;
+    xkv[l] = (tensor [n_sent * S, ld], column of layer l's [K | V]): their cross-attention projections; kpm uint8 [n_sent, S] or None;
+    sent int32 [n_live]: the original sentence of every live one (hypothesis row r belongs to live sentence r // beam).  Nothing but
+    anc and sent changes after construction."""
+
+    def __init__(self, kv, anc_bufs, Tmax, self_ws, enc_rows, xkv, kpm, sent, n_sent, beam, S, cross_ws):
+        self.kv, self.bufs, self.cur, self.anc, self.t, self.Tmax, self.self_ws = kv, anc_bufs, 0, anc_bufs[0], 0, Tmax, self_ws
+        self.enc_rows, self.xkv, self.kpm, self.sent = enc_rows, xkv, kpm, sent
+        self.n_sent, self.beam, self.S, self.cross_ws = n_sent, beam, S, cross_ws
+
+    @property
+    def rows(self):
+        return self.anc.shape[0]
 
 
 class TransformerDecoder(FairseqIncrementalDecoder):
@@ -130,6 +150,9 @@ class TransformerDecoder(FairseqIncrementalDecoder):
     def _extract_features_incremental(self, prev_output_tokens, tgt_mask, encoder_out, incremental_state, alignment_layer,
                                       alignment_heads):
         B, T, C = prev_output_tokens.shape
+        if self._BEAM_KEY in incremental_state:      # beam search over a slot cache: the state carries the encoder side
+            return self._extract_features_beam_slots(prev_output_tokens, incremental_state[self._BEAM_KEY], alignment_layer,
+                                                     alignment_heads)
         state = incremental_state.setdefault(self._CACHE_KEY, {"layers": [dict() for _ in self.layers]})
         enc_rows, S, enc_pad = None, None, None
         if encoder_out is not None and len(encoder_out["encoder_out"]) > 0:
@@ -166,6 +189,9 @@ class TransformerDecoder(FairseqIncrementalDecoder):
 
     def reorder_incremental_state_scripting(self, incremental_state, new_order):
         """Beam search re-ordering (decoder.py:301-314 of the reference): every cached tensor is batch-major."""
+        if incremental_state is not None and self._BEAM_KEY in incremental_state:
+            self.reorder_beam_slots(incremental_state[self._BEAM_KEY], new_order)
+            return incremental_state
         state = incremental_state.get(self._CACHE_KEY) if incremental_state is not None else None
         if state is None:
             return incremental_state
@@ -179,6 +205,105 @@ class TransformerDecoder(FairseqIncrementalDecoder):
             er = state["enc_rows"]
             state["enc_rows"] = er.view(state_B(state, er), -1, er.shape[1]).index_select(0, new_order).reshape(-1, er.shape[1])
         return incremental_state
+
+    # ---- beam search over a slot cache (SequenceGenerator(decode="slots")) ----
+    _BEAM_KEY = "st5_decoder_beam_slots"
+
+    def check_beam_slots(self):
+        """ValueError naming what of this decoder the slot path does not cover (SequenceGenerator(decode="slots") asks at construction):
+        st5_lm_decode_attn takes head dims 64 / 80, st5_beam_cross_attn 64 only, both at most 64 heads; the layers either all have
+        an encoder attention or none has."""
+        cross = [l.encoder_attn for l in self.layers]
+        if any(a is None for a in cross) and not all(a is None for a in cross):
+            raise ValueError("decode='slots': some decoder layers have an encoder attention and some have none")
+        for a, dims in [(l.self_attn, (64, 80)) for l in self.layers] + [(a, (64,)) for a in cross if a is not None]:
+            if a.head_dim not in dims or a.num_heads > 64:
+                raise ValueError(f"decode='slots': {a.num_heads} heads of {a.head_dim} are not covered by the slot-cache kernels "
+                                 f"(head dim {' / '.join(map(str, dims))}, at most 64 heads); use decode='concat'")
+
+    @torch.no_grad()
+    def init_beam_slots(self, n_sent, beam, max_len, encoder_out):
+        """State of one generate() call for n_sent sentences x beam hypothesis rows and up to max_len positions (BeamSlotState):
+        per layer a self-attention slot cache, one ancestry table, the attention workspaces, and the encoder side ONCE PER SENTENCE:
+        encoder rows, key-padding bytes and the cross-attention K|V of all layers from one projection GEMM (N = layers * 2C).  The
+        generator puts it into the model's incremental state under _BEAM_KEY; a decode step then runs through
+        forward(..., incremental_state=...) and a beam reorder through reorder_beam_slots."""
+        self.check_beam_slots()
+        sa = self.layers[0].self_attn
+        H, hd, C = sa.num_heads, sa.head_dim, sa.embed_dim
+        dev, dtype = sa.q_proj.weight.device, Fn.compute_dtype()
+        rows = n_sent * beam
+        kv = [torch.empty(rows, max_len, 2 * C, dtype=dtype, device=dev) for _ in self.layers]
+        ident = torch.arange(rows, dtype=torch.int32, device=dev).unsqueeze(1).expand(rows, max_len)
+        bufs = [ident.contiguous(), torch.empty(rows, max_len, dtype=torch.int32, device=dev)]
+        self_ws = Fn.lm_decode_attn_ws(rows, max_len, H, hd, dev)
+        enc_rows, xkv, kpm, S, cross_ws = None, None, None, 0, None
+        cross = [l.encoder_attn for l in self.layers]
+        if encoder_out is not None and len(encoder_out["encoder_out"]) > 0 and all(a is not None for a in cross):
+            enc = encoder_out["encoder_out"][0]  # S x n_sent x C
+            assert enc.size(1) == n_sent, f"Expected enc.shape == (t, {n_sent}, c) got {enc.shape}"
+            S = enc.size(0)
+            enc_rows = Fn.as_compute(enc.transpose(0, 1).contiguous()).view(n_sent * S, -1)
+            if len(encoder_out["encoder_padding_mask"]) > 0:
+                kpm = _mask_bytes(encoder_out["encoder_padding_mask"][0])
+            ws = [w for a in cross for w in (a.k_proj.weight, a.v_proj.weight)]
+            bs = [b for a in cross for b in (a.k_proj.bias, a.v_proj.bias)]
+            if all(b is not None for b in bs) and all(w.shape == ws[0].shape for w in ws):
+                kv_all = Fn.linear(enc_rows, ws, bs)                        # [n_sent * S, L * 2C], layer l = columns l * 2C ...
+                xkv = [(kv_all, idx * 2 * C) for idx in range(len(cross))]
+            else:
+                xkv = [(Fn.linear(enc_rows, [a.k_proj.weight, a.v_proj.weight], [a.k_proj.bias, a.v_proj.bias]), 0) for a in cross]
+            cross_ws = Fn.beam_cross_attn_ws(rows, S, cross[0].num_heads, cross[0].head_dim, dev)
+        sent = torch.arange(n_sent, dtype=torch.int32, device=dev)
+        return BeamSlotState(kv, bufs, max_len, self_ws, enc_rows, xkv, kpm, sent, n_sent, beam, S, cross_ws)
+
+    @torch.no_grad()
+    def _extract_features_beam_slots(self, prev_output_tokens, st, alignment_layer, alignment_heads):
+        """One decode step over the slot state: prev_output_tokens [n_live * beam, 1, C] = the newest position of every hypothesis
+        row.  Returns what _extract_features_incremental returns (the alignment layer's attention [rows, 1, S], head mean)."""
+        B, T, C = prev_output_tokens.shape
+        if T != 1 or B != st.rows:
+            raise ValueError(f"beam-slot decode step: got {B} rows x {T} positions for a state of {st.rows} rows (one position per step)")
+        if st.t >= st.Tmax:
+            raise ValueError(f"beam-slot decode step: position {st.t} is past the {st.Tmax} positions of this state")
+        x = Fn.as_compute(prev_output_tokens.contiguous())[:, 0].contiguous()
+        inner_states = [x.view(B, 1, C).transpose(0, 1)]
+        attn_list, attn = [], None
+        for idx, layer in enumerate(self.layers):
+            want = bool(idx == alignment_layer or alignment_layer == -1) and st.xkv is not None and layer.encoder_attn is not None
+            rec, r = None, None
+            if want:
+                r = torch.empty(B, layer.encoder_attn.num_heads, st.S, dtype=torch.float32, device=x.device)
+                rec = (r, r.stride(0), r.stride(1))
+            x = layer.forward_rows_beam_slots(x, st, idx, rec)
+            inner_states.append(x.view(B, 1, C).transpose(0, 1))
+            if want:
+                layer_attn = r.unsqueeze(2)                  # [B,H,1,S]
+                attn = layer_attn.transpose(0, 1)            # [H,B,1,S]
+                attn_list.append(layer_attn)
+        st.t += 1
+        if attn is not None and len(attn_list) == 1:
+            if alignment_heads is not None:
+                attn = attn[:alignment_heads]
+            attn = attn.mean(dim=0)
+        if self.layer_norm is not None:
+            x = self.layer_norm(x)
+        return x.view(B, 1, C), {"attn": [attn if len(attn_list) <= 1 else attn_list], "inner_states": inner_states}
+
+    @torch.no_grad()
+    def reorder_beam_slots(self, st, order, batch_idxs=None):
+        """Hypothesis row r continues row order[r] of the previous step (len(order) < rows when sentences left the batch; the entries
+        index the rows BEFORE the shrink): one gather of the int32 ancestry table; no key, value or encoder tensor moves.
+        batch_idxs: the live sentences that stay, when some left (None: derived from `order`)."""
+        other = st.bufs[1 - st.cur]
+        n_old = st.rows
+        st.anc = Fn.lm_reorder(st.anc, order, st.t, other)
+        st.cur = 1 - st.cur
+        if batch_idxs is not None:
+            st.sent = st.sent.index_select(0, batch_idxs).contiguous()
+        elif order.numel() != n_old:
+            st.sent = st.sent.index_select(0, torch.div(order.view(-1, st.beam)[:, 0], st.beam, rounding_mode="trunc")).contiguous()
+        return st
 
     def set_num_updates(self, num_updates):
         def _apply(m):

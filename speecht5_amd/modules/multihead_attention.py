@@ -160,6 +160,18 @@ class MultiheadAttention(nn.Module, IncrementalState):
         ctx = Fn.decode_cross_attn(q, cache["kvp"], 0, S, H, hd, kpm=cache["kpm"], probs=rec, ws=cache["ws"])
         return Fn.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual)
 
+    # ---- beam search over a slot cache (SequenceGenerator(decode="slots")): K|V once per sentence, one query per hypothesis ----
+    @torch.no_grad()
+    def forward_rows_beam_query(self, x, st, kv, k_off, residual, rec=None):
+        """Cross-attention of one query per hypothesis row x [n_live * beam, C] over the projected encoder rows kv [n_sent * S, ld]
+        (this layer's K at column k_off, V at k_off + C), which the beam rows of a sentence share (st: the decoder's BeamSlotState).
+        rec: None, or (fp32 tensor at row 0 / head 0, row stride, head stride) that receives the probabilities [rows, H, S]
+        (st5_beam_cross_attn)."""
+        H, hd = self.num_heads, self.head_dim
+        q = Fn.linear(x, self.q_proj.weight, self.q_proj.bias)
+        ctx = Fn.beam_cross_attn(q, kv, k_off, st.sent, st.n_sent, st.beam, st.S, H, hd, kpm=st.kpm, probs=rec, ws=st.cross_ws)
+        return Fn.linear(ctx, self.out_proj.weight, self.out_proj.bias, residual=residual)
+
     # ---- reference-compatible Time x Batch x Channel interface ----
     def forward(self, query, key, value, key_padding_mask=None, incremental_state=None, need_weights=True,
                 static_kv=False, attn_mask=None, before_softmax=False, need_head_weights=False, position_bias=None):

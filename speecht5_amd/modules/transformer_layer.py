@@ -196,6 +196,31 @@ class TransformerDecoderLayer(nn.Module):
             x = self.final_layer_norm(x)
         return x, None
 
+    @torch.no_grad()
+    def forward_rows_beam_slots(self, x, st, idx, rec=None):
+        """Decode step of beam search over a slot cache (TransformerDecoder.init_beam_slots): x [n_live * beam, C] = the newest position
+        of every hypothesis row.  Self-attention K|V are written into slot st.t of this layer's cache and read back over the ancestry
+        table; the cross-attention reads the sentence's K|V (st.xkv[idx]) once for all of its beam rows.  rec: where the
+        cross-attention probabilities go (None: nowhere).  Returns rows [n_live * beam, C]."""
+        nb = self.normalize_before
+        B = x.shape[0]
+        cache = {"slots": st.kv[idx], "t": st.t, "anc": st.anc, "ws": st.self_ws}
+        h = self.self_attn_layer_norm(x) if nb else x
+        x = self.self_attn.forward_rows_slots(h, B, cache, residual=x)
+        if not nb:
+            x = self.self_attn_layer_norm(x)
+        if self.encoder_attn is not None and st.xkv is not None:
+            h = self.encoder_attn_layer_norm(x) if nb else x
+            kv, k_off = st.xkv[idx]
+            x = self.encoder_attn.forward_rows_beam_query(h, st, kv, k_off, residual=x, rec=rec)
+            if not nb:
+                x = self.encoder_attn_layer_norm(x)
+        h = self.final_layer_norm(x) if nb else x
+        x = Fn.ffn(h, x, self.fc1, self.fc2, self.act, 0.0, 0.0)
+        if not nb:
+            x = self.final_layer_norm(x)
+        return x
+
     def forward(self, x, encoder_out=None, encoder_padding_mask=None, incremental_state=None, prev_self_attn_state=None,
                 prev_attn_state=None, self_attn_mask=None, self_attn_padding_mask=None, need_attn=False,
                 need_head_weights=False, pos_bias=None):

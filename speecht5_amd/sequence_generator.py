@@ -175,13 +175,28 @@ class SequenceGenerator(nn.Module):
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
                  search_strategy=None, eos=None, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, ctc_weight=0.0,
-                 exact_rows=False, ctc_rows=False):
+                 exact_rows=False, ctc_rows=False, decode="concat"):
         """`exact_rows`: speech input is encoded through forward_encoder_rows, so that a row's hypotheses do not depend on what else
         is in its batch (off, the default: the reference's padded batch).
         `ctc_rows`: with ctc_weight > 0 every sentence is re-scored against its OWN CTC posterior and frame count
-        (CTCPrefixScorerRows; off, the default: the reference's way, every sentence against sentence 0's)."""
+        (CTCPrefixScorerRows; off, the default: the reference's way, every sentence against sentence 0's).
+        `decode`: "concat" (the default: the reference's incremental state, keys / values concatenated per step, encoder output
+        replicated by beam and re-ordered every step) or "slots": every model decodes over a slot cache with an ancestry table and
+        keeps the encoder side once per sentence (TransformerDecoder.init_beam_slots, csrc/beam_decode.hip); a beam reorder is one
+        gather of an int32 table.  A model whose decoder has no slot API is refused (ValueError), there is no fallback."""
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)
+        if decode not in ("concat", "slots"):
+            raise ValueError(f"decode={decode!r}: expected 'concat' or 'slots'")
+        if decode == "slots":
+            for m in self.model.models:
+                if not hasattr(getattr(m, "decoder", None), "init_beam_slots"):
+                    raise ValueError(f"decode='slots' needs a decoder with init_beam_slots / reorder_beam_slots; "
+                                     f"{type(m).__name__} has none (use decode='concat')")
+                check = getattr(m.decoder, "check_beam_slots", None)
+                if check is not None:
+                    check()                  # (head dims / head counts the slot-cache kernels do not cover: ValueError here, not at step 0)
+        self.decode = decode
         self.exact_rows = bool(exact_rows)      # (the generator's own: an EnsembleModel may serve several generators)
         self.ctc_rows = bool(ctc_rows)
         self.tgt_dict = tgt_dict
@@ -285,8 +300,13 @@ class SequenceGenerator(nn.Module):
             ctc_prev = torch.zeros(bsz * beam, dtype=torch.float32, device=dev)          # log psi of each row's prefix
             ctc_known = torch.ones(bsz * beam, dtype=torch.bool, device=dev)             # row's prefix was re-scored when created
 
-        new_order = torch.arange(bsz, device=dev).view(-1, 1).repeat(1, beam).view(-1)
-        encoder_outs = self.model.reorder_encoder_out(encoder_outs, new_order)
+        slots = self.decode == "slots"
+        if slots:
+            # the encoder side stays once per sentence inside each model's slot state; encoder_outs is not replicated by beam
+            self.model.init_beam_slots(incremental_states, bsz, beam, max_len + 2, encoder_outs)
+        else:
+            new_order = torch.arange(bsz, device=dev).view(-1, 1).repeat(1, beam).view(-1)
+            encoder_outs = self.model.reorder_encoder_out(encoder_outs, new_order)
         scores = torch.zeros(bsz * beam, max_len + 1, device=dev)
         tokens = torch.full((bsz * beam, max_len + 2), self.pad, dtype=torch.long, device=dev)
         tokens[:, 0] = self.eos if bos_token is None else bos_token
@@ -308,10 +328,14 @@ class SequenceGenerator(nn.Module):
                     corr = batch_idxs - torch.arange(batch_idxs.numel(), device=dev)
                     reorder_state.view(-1, beam).add_(corr.unsqueeze(-1) * beam)
                     original_batch_idxs = original_batch_idxs[batch_idxs]
-                self.model.reorder_incremental_state(incremental_states, reorder_state)
+                if slots:
+                    self.model.reorder_beam_slots(incremental_states, reorder_state, batch_idxs)
+                else:
+                    self.model.reorder_incremental_state(incremental_states, reorder_state)
                 if lm_state is not None:
                     self.lm_model.reorder(lm_state, reorder_state)
-                encoder_outs = self.model.reorder_encoder_out(encoder_outs, reorder_state)
+                if not slots:
+                    encoder_outs = self.model.reorder_encoder_out(encoder_outs, reorder_state)
 
             lprobs, avg_attn_scores = self.model.forward_decoder(tokens[:, : step + 1], encoder_outs, incremental_states,
                                                                  self.temperature)
@@ -591,6 +615,15 @@ class EnsembleModel(nn.Module):
         if not self.has_encoder():
             return []
         return [m.encoder.reorder_encoder_out(encoder_outs[i], new_order) for i, m in enumerate(self.models)]
+
+    def init_beam_slots(self, incremental_states, n_sent, beam, max_len, encoder_outs):
+        """decode="slots": every model's own slot state (its decoder's init_beam_slots) into its incremental state."""
+        for i, m in enumerate(self.models):
+            incremental_states[i][m.decoder._BEAM_KEY] = m.decoder.init_beam_slots(n_sent, beam, max_len, encoder_outs[i])
+
+    def reorder_beam_slots(self, incremental_states, new_order, batch_idxs=None):
+        for i, m in enumerate(self.models):
+            m.decoder.reorder_beam_slots(incremental_states[i][m.decoder._BEAM_KEY], new_order, batch_idxs)
 
     def reorder_incremental_state(self, incremental_states, new_order):
         if not self.has_incremental_states():
