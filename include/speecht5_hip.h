@@ -86,6 +86,11 @@ typedef struct st5_gemm_params {
   float* asum;      /* optional fp32 [M] (batch == 1): asum[m] += sum_k A(m, k).  With A = dY^T this is the bias gradient,
                      * computed by the weight-gradient GEMM itself (one extra MFMA column in the first column of tiles)
                      * instead of a separate reduction over dY (autograd of F.linear: grad_bias = dY.sum(0)). */
+  const float* gate; /* optional LayerDrop layer gate: one float in device memory (the `keep` of st5_layernorm_gated_fwd).  When *gate == 0
+                      * every block of the launch exits before it reads or writes anything: C, Cpre and asum stay as they are (a dropped
+                      * layer's activations are never read; its weight / bias gradient accumulators would only receive exact zeros).
+                      * A split-K reduction, immediate or deferred, honours it too.  NULL or *gate != 0: no effect, bit for bit.
+                      * In st5_gemm_tn_group the gate is per problem.  Ignored by the MX-fp8 entry points. */
 } st5_gemm_params;
 
 /* Generic MFMA GEMM: C = drop(act(alpha * A.B^T + bias)) [* act'(P)] + R + beta*C.
@@ -211,6 +216,20 @@ int st5_layernorm_gated_fwd(const void* x, const float* gamma, const float* beta
 int st5_layernorm_gated_bwd(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
                             float* dgamma, float* dbeta, void* ws, int64_t rows, int32_t cols, void* dx_dropped, float drop_p,
                             uint64_t drop_seed, const float* keep, int dtype, void* stream);
+/* The LayerDrop LAYER GATE (st5_gemm_params.gate): inside a replayed step a dropped layer cannot be skipped on the host, so every launch
+ * of a gated layer carries the layer's keep float and exits at once when *gate == 0.  Rule for what a dropped launch leaves behind: DEAD
+ * outputs (read only by launches of the same layer) are not written at all; LIVE outputs (read outside the layer) get what a dropped layer
+ * gives today -- exact zeros, or an unchanged accumulator.  gate NULL or *gate != 0: the ungated call, bit for bit.
+ * st5_layernorm_fwd_gate: st5_layernorm_fwd (keep == skip == NULL) or st5_layernorm_gated_fwd (both given; pass the same pointer as gate).
+ * Dropped: a plain LayerNorm writes nothing; the gated one writes y = skip without reading x; mean / rstd stay unwritten.
+ * st5_layernorm_bwd_gate: st5_layernorm_bwd (keep NULL) or st5_layernorm_gated_bwd.  Dropped: dy, x, mean, rstd are not read, dx / dx_dropped
+ * not written, nothing is added to dgamma / dbeta (zero block partials: also through st5_layernorm_defer / _flush).
+ * Vector kernels only (cols % 4 == 0, cols <= 2048, dx given): anything else with a gate is ST5_ERR_ARG, never an ungated fall-back. */
+int st5_layernorm_fwd_gate(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int64_t rows,
+                           int32_t cols, float eps, const float* keep, const void* skip, const float* gate, int dtype, void* stream);
+int st5_layernorm_bwd_gate(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+                           float* dbeta, void* ws, int64_t rows, int32_t cols, void* dx_dropped, float drop_p, uint64_t drop_seed,
+                           const float* keep, const float* gate, int dtype, void* stream);
 int st5_layernorm_defer(int enabled, void* stream);
 int st5_layernorm_flush(void* stream);
 int64_t st5_layernorm_bwd_ws_bytes(int64_t rows, int32_t cols);
@@ -259,6 +278,13 @@ int st5_flash_attn_fwd_qp(const void* q, int64_t q_ld, const void* k, int64_t k_
                           int32_t S, int32_t head_dim, int32_t nb, int32_t maxrel, int32_t causal, int32_t lds, float scale,
                           float dropout_p, uint64_t seed, void* qp_out, int dtype, void* stream);
 
+/* st5_flash_attn_fwd_qp with the layer gate: *gate == 0 -> the table kernel and the attention kernel exit; o, lse, qp_out are not written.
+ * Second-generation kernels only (a gate with st5_flash_attn_set_impl(1), or with pe but no qp_out, is ST5_ERR_ARG). */
+int st5_flash_attn_fwd_qp_gate(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o,
+                               int64_t o_ld, float* lse, const void* pe, const uint8_t* kpm, int32_t B, int32_t H, int32_t T,
+                               int32_t S, int32_t head_dim, int32_t nb, int32_t maxrel, int32_t causal, int32_t lds, float scale,
+                               float dropout_p, uint64_t seed, void* qp_out, const float* gate, int dtype, void* stream);
+
 /* Backward of st5_flash_attn_fwd: recomputes P from (q, k, bias, lse).  Writes dq/dk/dv (dtype, same row layouts as
  * q/k/v with their own leading dimensions); dvec fp32 [B*H*T] scratch (D = rowsum(dO*O)).  With pe: qp = the relative-position table
  * [B*H, T, st5_flash_attn_qp_row(nb)] (from st5_flash_attn_fwd_qp or st5_flash_attn_qp_table) and dqp [B*H, T, nb] (plain) receives the bucket gradients
@@ -278,6 +304,17 @@ int st5_flash_attn_bwd_2s(const void* q, int64_t q_ld, const void* k, int64_t k_
                           const uint8_t* kpm, int32_t B, int32_t H, int32_t T, int32_t S, int32_t head_dim, int32_t nb,
                           int32_t maxrel, int32_t causal, int32_t lds, float scale, float dropout_p, uint64_t seed, int dtype,
                           void* stream, void* stream2);
+
+/* st5_flash_attn_bwd_2s with the layer gate: *gate == 0 -> every kernel exits; dq, dqp, dvec are not written.  dkv_live == 0: neither are
+ * dk / dv (self-attention: only the layer's own QKV backward reads them).  dkv_live != 0: dk / dv receive exact zeros in the rows and
+ * columns the kept kernel writes and nowhere else -- the decoder's cross-attention writes its column slice of the K|V gradient buffer all
+ * layers share, which is not zero-filled. */
+int st5_flash_attn_bwd_2s_gate(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o,
+                               int64_t o_ld, const void* dout, int64_t do_ld, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld,
+                               void* dv, int64_t dv_ld, const float* lse, float* dvec, const void* pe, const void* qp, void* dqp,
+                               const uint8_t* kpm, int32_t B, int32_t H, int32_t T, int32_t S, int32_t head_dim, int32_t nb,
+                               int32_t maxrel, int32_t causal, int32_t lds, float scale, float dropout_p, uint64_t seed,
+                               const float* gate, int32_t dkv_live, int dtype, void* stream, void* stream2);
 
 /* ---- speech pre-net layer 0: Conv1d(1->C,k,stride,no bias) + GroupNorm(C groups) + GELU
  *      (speech_encoder_prenet.py:300,323-324).  wav fp32 [B,S]; out channels-last [B,L,C] (dtype);
@@ -331,6 +368,10 @@ int st5_cast_to_f32(const void* src, float* dst, int64_t n, int dtype, void* str
 /* out[c] (+)= scale * sum_r x[r, c]   (bias gradients); ws >= st5_colsum_ws_bytes(rows, cols) */
 int st5_colsum_ws(const void* x, float* out, void* ws, int64_t rows, int32_t cols, int64_t ld, float scale,
                   int32_t accumulate, int dtype, void* stream);
+/* st5_colsum_ws with the layer gate (see st5_layernorm_fwd_gate): *gate == 0 -> x and the partials are not read; the overwrite form stores
+ * exact zeros (a dropped layer's relative-position gradient, read outside the layer), the accumulating form leaves `out` alone. */
+int st5_colsum_ws_gate(const void* x, float* out, void* ws, int64_t rows, int32_t cols, int64_t ld, float scale, int32_t accumulate,
+                       const float* gate, int dtype, void* stream);
 int64_t st5_colsum_ws_bytes(int64_t rows, int32_t cols);
 /* out[0] (+)= scale * sum(x^2)   (features_pen, speech_encoder_prenet.py:172) */
 int st5_sumsq(const void* x, float* out, int64_t n, float scale, int32_t accumulate, int dtype, void* stream);

@@ -182,6 +182,11 @@ __device__ __forceinline__ void mx8_quant(const float (&v)[NE], unsigned int (&q
 }
 
 // exact (erf) GELU as torch.nn.GELU() / fairseq "gelu" in fp32
+// LayerDrop layer gate: every native launch of a gated transformer layer carries the layer's `keep` float (device memory,
+// staged from the host draw before a replay).  A dropped layer's launch exits before any load, barrier or store: the test is the
+// kernel's first statement and block-uniform.  gate == nullptr or *gate != 0: the kernel runs exactly as without a gate.
+__device__ __forceinline__ bool st5_gate_dropped(const float* gate) { return gate != nullptr && *gate == 0.f; }
+
 __device__ __forceinline__ float gelu_f(float x) { return 0.5f * x * (1.0f + erff(x * 0.70710678118654752f)); }
 __device__ __forceinline__ float gelu_grad_f(float x) {
   const float cdf = 0.5f * (1.0f + erff(x * 0.70710678118654752f));

@@ -183,7 +183,9 @@ __device__ __forceinline__ void read_bias(unsigned int (&braw)[32], const char* 
 // =====================================================================================================================
 template <bool PE_LDS>
 __global__ __launch_bounds__(256) void qp_table_kernel(const bf16_t* __restrict__ qg, long long q_ld, const bf16_t* __restrict__ pe,
-                                                       bf16_t* __restrict__ qp, int H, int T, int nb, float sc2) {
+                                                       bf16_t* __restrict__ qp, int H, int T, int nb, float sc2,
+                                                       const float* __restrict__ gate) {
+  if (st5_gate_dropped(gate)) return;   // layer gate (common.h): the table of a dropped layer is read by that layer's kernels alone
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int ql = lane & 31, hi = lane >> 5;
   const int bh = blockIdx.y, b = bh / H, h = bh % H;
@@ -256,6 +258,7 @@ struct Args {
   int B, H, T, S, nb, maxrel, causal, lds;
   float scale, dropout_p;
   unsigned long long seed;
+  const float* gate;                         // layer gate or NULL (st5_flash_attn_fwd_qp_gate)
 };
 
 // scores of one tile in the log2 domain (+ masks); returns the lane's tile max.  UNI: one bias value for the whole tile.
@@ -323,6 +326,7 @@ __device__ __forceinline__ WinGeom win_geom(int qw0, int j0, int maxrel, int nb)
 // CUs; bwd_dq_kernel<true> was 7.9 k instructions with its 16-way run-time dispatch).
 template <bool BIAS, bool DROP>
 __global__ __launch_bounds__(256, 2) void fwd_kernel(const Args a) {
+  if (st5_gate_dropped(a.gate)) return;   // layer gate: o and lse of a dropped layer are never read
 #ifdef FA2_PAD256   // discriminator build (tools/r4/sbs_arms.sh): no third wave beside this kernel's wave and another big one on a SIMD
   ST5_PAD_TO_256_VGPRS();
 #endif
@@ -506,11 +510,14 @@ struct BwdArgs {
   int B, H, T, S, nb, maxrel, causal, lds;
   float scale, dropout_p;
   unsigned long long seed;
+  const float* gate;   // layer gate or NULL (st5_flash_attn_bwd_2s_gate)
+  int dkv_live;        // with a gate: dK / dV are read outside the layer -> a dropped layer stores zeros (bwd_dkv_kernel)
   int dvec_in_dq;   // 1 (dq and dkv on ONE stream): the dq kernel computes D = dO . O itself, writes dvec for the dkv kernel behind it, and clears dQP
 };
 
 __global__ __launch_bounds__(256) void dvec_kernel(const bf16_t* __restrict__ o, const bf16_t* __restrict__ dout, float* __restrict__ dvec,
-                                                   long long o_ld, long long do_ld, int H, int T, long long rows) {
+                                                   long long o_ld, long long do_ld, int H, int T, long long rows, const float* __restrict__ gate) {
+  if (st5_gate_dropped(gate)) return;
   const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
   const long long r = t >> 1;
   const int hi = (int)(t & 1);
@@ -588,6 +595,7 @@ __device__ __forceinline__ void read_bias_half(const int t, unsigned int (&braw)
 
 template <bool BIAS, bool DROP>
 __global__ __launch_bounds__(256, 2) void bwd_dq_kernel(const BwdArgs a) {
+  if (st5_gate_dropped(a.gate)) return;   // layer gate: dq, dqp and dvec of a dropped layer are never read
 #ifdef FA2_PAD256   // discriminator build (tools/r4/sbs_arms.sh): no third wave beside this kernel's wave and another big one on a SIMD
   ST5_PAD_TO_256_VGPRS();
 #endif
@@ -953,6 +961,34 @@ __device__ __forceinline__ void dkv_store_dqp(const bf16x8 (&df)[2], __amdgpu_bu
 
 template <bool BIAS, bool DROP>
 __global__ __launch_bounds__(256, 2) void bwd_dkv_kernel(const BwdArgs a) {
+  // Layer gate: a dropped layer's dK / dV are read by that layer alone (self-attention: dkv_live == 0, nothing is written) -- except the
+  // decoder's cross-attention, whose dK | dV land in a column slice of the gradient buffer all layers share and which is not zero-filled:
+  // dkv_live != 0 stores the exact zeros a dropped layer's gradient is, into this layer's columns only, with the addresses of the
+  // kernel's own final stores, and reads nothing.
+  if (st5_gate_dropped(a.gate)) {
+    if (a.dkv_live) {
+      const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
+      int xb0, bh0;
+      block_coords(xb0, bh0);
+      const int b_ = bh0 / a.H, h_ = bh0 % a.H;
+      const int ki_ = xb0 * 128 + wave_ * 32 + (lane_ & 31), hi_ = lane_ >> 5;
+      if (ki_ < a.S) {
+        bf16_t* krow = a.dk + ((long long)b_ * a.S + ki_) * a.dk_ld + h_ * HD;
+        bf16_t* vrow = a.dv + ((long long)b_ * a.S + ki_) * a.dv_ld + h_ * HD;
+        bf16x4 z;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) z[e] = (bf16_t)0.f;
+#pragma unroll
+        for (int dt = 0; dt < 2; ++dt)
+#pragma unroll
+          for (int g = 0; g < 4; ++g) {
+            *reinterpret_cast<bf16x4*>(krow + dt * 32 + 8 * g + 4 * hi_) = z;
+            *reinterpret_cast<bf16x4*>(vrow + dt * 32 + 8 * g + 4 * hi_) = z;
+          }
+      }
+    }
+    return;
+  }
 #ifdef FA2_PAD256   // discriminator build (tools/r4/sbs_arms.sh): no third wave beside this kernel's wave and another big one on a SIMD
   ST5_PAD_TO_256_VGPRS();
 #endif
@@ -1253,8 +1289,8 @@ extern "C" int st5_flash_attn_set_impl(int impl) {
 }
 extern "C" int32_t st5_flash_attn_qp_row(int32_t nb) { return g_impl == 2 ? nb + 2 * fa2::QP_PAD : nb; }
 
-extern "C" int st5_flash_attn_qp_table(const void* q, int64_t q_ld, const void* pe, void* qp_out, int32_t B, int32_t H, int32_t T,
-                                       int32_t nb, float scale, int dtype, void* stream) {
+static int qp_table(const void* q, int64_t q_ld, const void* pe, void* qp_out, int32_t B, int32_t H, int32_t T, int32_t nb, float scale,
+                    int dtype, void* stream, const float* gate) {
   if (!q || !pe || !qp_out || B <= 0 || H <= 0 || T <= 0 || nb <= 0 || nb % 8 || dtype != ST5_BF16 || q_ld % 8) return ST5_ERR_ARG;
   const size_t pe_bytes = (size_t)nb * fa2::HD * 2;
   if (pe_bytes <= 64 * 1024) {
@@ -1264,19 +1300,27 @@ extern "C" int st5_flash_attn_qp_table(const void* q, int64_t q_ld, const void* 
       attr = true;
     }
     hipLaunchKernelGGL(fa2::qp_table_kernel<true>, dim3((T + 127) / 128, B * H), dim3(256), pe_bytes, (hipStream_t)stream, (const bf16_t*)q,
-                       (long long)q_ld, (const bf16_t*)pe, (bf16_t*)qp_out, H, T, nb, scale * fa2::LOG2E);
+                       (long long)q_ld, (const bf16_t*)pe, (bf16_t*)qp_out, H, T, nb, scale * fa2::LOG2E, gate);
   } else {
     hipLaunchKernelGGL(fa2::qp_table_kernel<false>, dim3((T + 127) / 128, B * H), dim3(256), 0, (hipStream_t)stream, (const bf16_t*)q,
-                       (long long)q_ld, (const bf16_t*)pe, (bf16_t*)qp_out, H, T, nb, scale * fa2::LOG2E);
+                       (long long)q_ld, (const bf16_t*)pe, (bf16_t*)qp_out, H, T, nb, scale * fa2::LOG2E, gate);
   }
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
+extern "C" int st5_flash_attn_qp_table(const void* q, int64_t q_ld, const void* pe, void* qp_out, int32_t B, int32_t H, int32_t T,
+                                       int32_t nb, float scale, int dtype, void* stream) {
+  return qp_table(q, q_ld, pe, qp_out, B, H, T, nb, scale, dtype, stream, nullptr);
+}
 
-extern "C" int st5_flash_attn_fwd_qp(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o,
-                                     int64_t o_ld, float* lse, const void* pe, const uint8_t* kpm, int32_t B, int32_t H, int32_t T,
-                                     int32_t S, int32_t head_dim, int32_t nb, int32_t maxrel, int32_t causal, int32_t lds, float scale,
-                                     float dropout_p, uint64_t seed, void* qp_out, int dtype, void* stream) {
+/* st5_flash_attn_fwd_qp carrying the layer gate (one float in device memory, see st5_gemm_params.gate): *gate == 0 -> the table kernel and
+ * the attention kernel exit at once, o / lse / qp_out are not written.  Second-generation kernels only (a gate on the first generation,
+ * which has no gated kernels, is ST5_ERR_ARG). */
+extern "C" int st5_flash_attn_fwd_qp_gate(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o,
+                                          int64_t o_ld, float* lse, const void* pe, const uint8_t* kpm, int32_t B, int32_t H, int32_t T,
+                                          int32_t S, int32_t head_dim, int32_t nb, int32_t maxrel, int32_t causal, int32_t lds, float scale,
+                                          float dropout_p, uint64_t seed, void* qp_out, const float* gate, int dtype, void* stream) {
+  if (gate && (g_impl == 1 || (pe && !qp_out))) return ST5_ERR_ARG;
   if (g_impl == 1 || (pe && !qp_out))   // no table workspace: the first generation keeps its table in LDS
     return st5_flash1_attn_fwd_qp(q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, pe, kpm, B, H, T, S, head_dim, nb, maxrel, causal, lds, scale,
                                   dropout_p, seed, g_impl == 1 ? qp_out : nullptr, dtype, stream);
@@ -1288,10 +1332,11 @@ extern "C" int st5_flash_attn_fwd_qp(const void* q, int64_t q_ld, const void* k,
   if (set_attrs() != ST5_OK) return ST5_ERR_LAUNCH;
   hipStream_t s = (hipStream_t)stream;
   if (pe) {
-    const int rc = st5_flash_attn_qp_table(q, q_ld, pe, qp_out, B, H, T, nb, scale, dtype, stream);
+    const int rc = qp_table(q, q_ld, pe, qp_out, B, H, T, nb, scale, dtype, stream, gate);
     if (rc) return rc;
   }
   fa2::Args a;
+  a.gate = gate;
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (bf16_t*)o; a.lse = lse;
   a.qp = pe ? (const bf16_t*)qp_out : nullptr; a.kpm = kpm;
   a.q_ld = q_ld; a.k_ld = k_ld; a.v_ld = v_ld; a.o_ld = o_ld;
@@ -1308,6 +1353,14 @@ extern "C" int st5_flash_attn_fwd_qp(const void* q, int64_t q_ld, const void* k,
   return ST5_OK;
 }
 
+extern "C" int st5_flash_attn_fwd_qp(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o,
+                                     int64_t o_ld, float* lse, const void* pe, const uint8_t* kpm, int32_t B, int32_t H, int32_t T,
+                                     int32_t S, int32_t head_dim, int32_t nb, int32_t maxrel, int32_t causal, int32_t lds, float scale,
+                                     float dropout_p, uint64_t seed, void* qp_out, int dtype, void* stream) {
+  return st5_flash_attn_fwd_qp_gate(q, q_ld, k, k_ld, v, v_ld, o, o_ld, lse, pe, kpm, B, H, T, S, head_dim, nb, maxrel, causal, lds, scale,
+                                    dropout_p, seed, qp_out, nullptr, dtype, stream);
+}
+
 extern "C" int st5_flash_attn_fwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, void* o,
                                   int64_t o_ld, float* lse, const void* pe, const uint8_t* kpm, int32_t B, int32_t H, int32_t T, int32_t S,
                                   int32_t head_dim, int32_t nb, int32_t maxrel, int32_t causal, int32_t lds, float scale, float dropout_p,
@@ -1316,12 +1369,17 @@ extern "C" int st5_flash_attn_fwd(const void* q, int64_t q_ld, const void* k, in
                                dropout_p, seed, nullptr, dtype, stream);
 }
 
-extern "C" int st5_flash_attn_bwd_2s(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o,
-                                     int64_t o_ld, const void* dout, int64_t do_ld, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld,
-                                     void* dv, int64_t dv_ld, const float* lse, float* dvec, const void* pe, const void* qp, void* dqp,
-                                     const uint8_t* kpm, int32_t B, int32_t H, int32_t T, int32_t S, int32_t head_dim, int32_t nb,
-                                     int32_t maxrel, int32_t causal, int32_t lds, float scale, float dropout_p, uint64_t seed, int dtype,
-                                     void* stream, void* stream2) {
+/* st5_flash_attn_bwd_2s carrying the layer gate: *gate == 0 -> every kernel exits at once; dq, dqp and dvec are not written.  dkv_live == 0:
+ * dk / dv are not written either (self-attention: the layer's own QKV backward is their only reader); dkv_live != 0: dk / dv receive exact
+ * zeros -- the rows and columns the kept kernel writes, nothing else (the decoder's cross-attention writes a column slice of a gradient
+ * buffer shared by all layers).  Second-generation kernels only. */
+extern "C" int st5_flash_attn_bwd_2s_gate(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o,
+                                          int64_t o_ld, const void* dout, int64_t do_ld, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld,
+                                          void* dv, int64_t dv_ld, const float* lse, float* dvec, const void* pe, const void* qp, void* dqp,
+                                          const uint8_t* kpm, int32_t B, int32_t H, int32_t T, int32_t S, int32_t head_dim, int32_t nb,
+                                          int32_t maxrel, int32_t causal, int32_t lds, float scale, float dropout_p, uint64_t seed,
+                                          const float* gate, int32_t dkv_live, int dtype, void* stream, void* stream2) {
+  if (gate && g_impl == 1) return ST5_ERR_ARG;
   if (g_impl == 1)
     return st5_flash1_attn_bwd_2s(q, q_ld, k, k_ld, v, v_ld, o, o_ld, dout, do_ld, dq, dq_ld, dk, dk_ld, dv, dv_ld, lse, dvec, pe, qp, dqp,
                                   kpm, B, H, T, S, head_dim, nb, maxrel, causal, lds, scale, dropout_p, seed, dtype, stream, stream2);
@@ -1333,6 +1391,7 @@ extern "C" int st5_flash_attn_bwd_2s(const void* q, int64_t q_ld, const void* k,
   if ((long long)B * H * T * (pe ? nb + 16 : 1) >= (1ll << 31)) return ST5_ERR_ARG;
   if (set_attrs() != ST5_OK) return ST5_ERR_LAUNCH;
   fa2::BwdArgs a;
+  a.gate = gate; a.dkv_live = dkv_live;
   a.q = (const bf16_t*)q; a.k = (const bf16_t*)k; a.v = (const bf16_t*)v; a.o = (const bf16_t*)o; a.dout = (const bf16_t*)dout;
   a.dq = (bf16_t*)dq; a.dk = (bf16_t*)dk; a.dv = (bf16_t*)dv; a.lse = lse; a.dvec = dvec;
   a.qp = pe ? (const bf16_t*)qp : nullptr; a.dqp = (bf16_t*)dqp; a.kpm = kpm;
@@ -1346,7 +1405,7 @@ extern "C" int st5_flash_attn_bwd_2s(const void* q, int64_t q_ld, const void* k,
   a.dvec_in_dq = (s2 == nullptr || s2 == s) ? 1 : 0;
   if (pe && !a.dvec_in_dq && hipMemsetAsync(dqp, 0, (size_t)B * H * T * nb * 2, s) != hipSuccess) return ST5_ERR_LAUNCH;
   if (!a.dvec_in_dq)
-    hipLaunchKernelGGL(fa2::dvec_kernel, dim3((unsigned)((rows * 2 + 255) / 256)), dim3(256), 0, s, a.o, a.dout, dvec, a.o_ld, a.do_ld, H, T, rows);
+    hipLaunchKernelGGL(fa2::dvec_kernel, dim3((unsigned)((rows * 2 + 255) / 256)), dim3(256), 0, s, a.o, a.dout, dvec, a.o_ld, a.do_ld, H, T, rows, gate);
   if (s2) { if (st5_stream_fork(s, s2) != ST5_OK) return ST5_ERR_LAUNCH; } else s2 = s;
   const size_t shm_dq = (size_t)4 * fa2::TILE_B + (pe ? 4 * fa2::SCR_B : 0);
 #ifdef FA2_DKV_FAT_LDS   // discriminator build (tools/r4/sbs_arms.sh): 104+ KB per dkv block -> one per CU, and no GEMM block beside it
@@ -1371,6 +1430,17 @@ extern "C" int st5_flash_attn_bwd_2s(const void* q, int64_t q_ld, const void* k,
   HIP_CHECK_LAUNCH();
   if (s2 != s && st5_stream_fork(s2, s) != ST5_OK) return ST5_ERR_LAUNCH;
   return ST5_OK;
+}
+
+extern "C" int st5_flash_attn_bwd_2s(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o,
+                                     int64_t o_ld, const void* dout, int64_t do_ld, void* dq, int64_t dq_ld, void* dk, int64_t dk_ld,
+                                     void* dv, int64_t dv_ld, const float* lse, float* dvec, const void* pe, const void* qp, void* dqp,
+                                     const uint8_t* kpm, int32_t B, int32_t H, int32_t T, int32_t S, int32_t head_dim, int32_t nb,
+                                     int32_t maxrel, int32_t causal, int32_t lds, float scale, float dropout_p, uint64_t seed, int dtype,
+                                     void* stream, void* stream2) {
+  return st5_flash_attn_bwd_2s_gate(q, q_ld, k, k_ld, v, v_ld, o, o_ld, dout, do_ld, dq, dq_ld, dk, dk_ld, dv, dv_ld, lse, dvec, pe, qp, dqp,
+                                    kpm, B, H, T, S, head_dim, nb, maxrel, causal, lds, scale, dropout_p, seed, nullptr, 0, dtype, stream,
+                                    stream2);
 }
 
 extern "C" int st5_flash_attn_bwd(const void* q, int64_t q_ld, const void* k, int64_t k_ld, const void* v, int64_t v_ld, const void* o,

@@ -519,6 +519,7 @@ __device__ __forceinline__ void run_epilogue(const EpiArgs& ea, float* stage, co
 
 template <typename T, bool AKS, bool BKS>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
   ST5_PAD_TO_256_VGPRS();
   constexpr int BK = 128 / (int)sizeof(T);
   typedef typename Frag<T>::type frag_t;
@@ -618,7 +619,8 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const st5_gemm_params
 // C[m, n] = beta * C[m, n] + sum_s slab[s][m][n]   (slabs dense [M, N] fp32; C fp32 with row mapping)
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restrict__ slabs, float* __restrict__ C,
                                                             int nsplit, int M, int N, long long ldc, int rpb,
-                                                            long long bstride, float beta, float* __restrict__ asum) {
+                                                            long long bstride, float beta, float* __restrict__ asum, const float* gate) {
+  if (st5_gate_dropped(gate)) return;   // the producer exited too: its slabs hold nothing of this problem
   const long long nv = (long long)M * N / 4;  // N % 4 == 0 guaranteed by the host
   const long long slab = (long long)M * N;
   if (asum) {   // bias-gradient column: the splits' partial columns sit behind the slabs
@@ -653,12 +655,13 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float* __restr
 // not launched one by one; their descriptors queue up (each GEMM keeps its slabs alive in a bump arena) and
 // st5_gemm_flush_splitk() folds all of them into their outputs with ONE launch (up to MR_MAX per launch).
 constexpr int MR_MAX = 48;
-struct MrDesc { const float* slabs; float* C; float* asum; long long ldc; int nsplit, M, N; float beta; int blk0; int pad; };
+struct MrDesc { const float* slabs; float* C; float* asum; long long ldc; int nsplit, M, N; float beta; int blk0; int pad; const float* gate; };
 struct MrArgs { MrDesc d[MR_MAX]; int n; };
 __global__ __launch_bounds__(256) void splitk_multi_reduce_kernel(const MrArgs a) {
   int j = 0;
   while (j + 1 < a.n && a.d[j + 1].blk0 <= (int)blockIdx.x) ++j;
   const MrDesc d = a.d[j];
+  if (st5_gate_dropped(d.gate)) return;   // per descriptor: a skipped producer's slab is never folded in
   const int nblk = (j + 1 < a.n ? a.d[j + 1].blk0 : (int)gridDim.x) - d.blk0;
   const long long nv = (long long)d.M * d.N / 4, slab = (long long)d.M * d.N;
   if (d.asum) {
@@ -821,6 +824,7 @@ __device__ __forceinline__ F lds_read128_asm(const unsigned lds_addr) {
 #endif
 template <typename T, int NBUF, int FEAT = -1>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
   ST5_PAD_TO_256_VGPRS();
 #ifdef GEMM_TIMING
   unsigned int tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
@@ -1030,6 +1034,7 @@ constexpr int M64_A_BYTES = 64 * 128, M64_STAGE = M64_A_BYTES + TILE_BYTES;
 
 template <int FEAT>
 __global__ __launch_bounds__(NTHREADS, 3) void gemm_nt_m64_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
   typedef bf16_t T;
   constexpr int VEC = 8, BK = 64;
   typedef bf16x8 frag_t;
@@ -1165,6 +1170,7 @@ __device__ __forceinline__ int lds_off2(int row, int chunk) { return row * ROW2 
 
 template <typename T>
 __global__ __launch_bounds__(NT2) void gemm_nt256_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
 #ifdef GEMM_TIMING
   unsigned int tacc[8] = {0, 0, 0, 0, 0, 0, 0, 0};
   unsigned long long tprev = __builtin_amdgcn_s_memtime();
@@ -1357,6 +1363,7 @@ __global__ __launch_bounds__(NT2) void gemm_nt256_kernel(const st5_gemm_params p
 // ------------------------------------------------------------------------------------------------------
 template <int FEAT, bool STAGGER>
 __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
   typedef bf16_t T;
   constexpr int BK = 64;
   constexpr int HALF = TILE_BYTES;              // 16 KB: 128 rows x 128 B
@@ -1916,6 +1923,7 @@ __device__ __forceinline__ void tn_glds_body(const st5_gemm_params& p, const int
 
 template <int FEAT>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_glds_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
   ST5_PAD_TO_256_VGPRS();
   // Split-K grids (round 6): the XCD-aware placement runs over the WHOLE (tile, split) grid, split-major -- XCD x takes the x-th
   // contiguous eighth of the list, i.e. most of the tiles of one or two splits, which share their k-range of BOTH operands.  The
@@ -1951,6 +1959,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_group_kernel(const TnGrou
   while (j + 1 < g.n && (int)blockIdx.x >= g.first[j + 1]) ++j;
   const int lb = (int)blockIdx.x - g.first[j];
   if (lb >= g.tiles[j]) return;
+  if (st5_gate_dropped(g.p[j].gate)) return;   // a dropped layer's problem: C and asum stay as they are (it would add exact zeros)
   tn_glds_body<FEAT>(g.p[j], 1, lb, g.tiles[j], 0, 1, 0);
 }
 
@@ -2156,6 +2165,7 @@ __device__ __forceinline__ void tn8p_body(const st5_gemm_params& p, const int c_
 
 template <int FEAT, bool STAGGER>
 __global__ __launch_bounds__(512) void gemm_tn8p_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  if (st5_gate_dropped(p.gate)) return;
   tn8p_body<FEAT, STAGGER>(p, c_vec_ok, (int)blockIdx.x, (int)gridDim.x, (int)blockIdx.y, (int)gridDim.y);
 }
 
@@ -2170,7 +2180,7 @@ __global__ __launch_bounds__(512) void gemm_tn8p_kernel(const st5_gemm_params p,
 // (a problem as the phased body needs it -- 72 bytes instead of st5_gemm_params' 400+, so that SIXTEEN fit into the kernel arguments: a
 //  Base decoder layer has six weight gradients of 9-36 tiles, and eight problems filled only 56-77 % of a round)
 constexpr int TNG8P_MAX = 16;
-struct Tn8pProb { const void* A; const void* B; void* C; float* asum; long long lda, ldb, ldc; int M, N, K; float beta; };
+struct Tn8pProb { const void* A; const void* B; void* C; float* asum; long long lda, ldb, ldc; int M, N, K; float beta; const float* gate; };
 struct Tn8pGroupArgs { Tn8pProb p[TNG8P_MAX]; int first[TNG8P_MAX + 1]; int tiles[TNG8P_MAX]; int n; };
 template <int FEAT>
 __global__ __launch_bounds__(512) void gemm_tn8p_group_kernel(const Tn8pGroupArgs g) {
@@ -2188,6 +2198,7 @@ __global__ __launch_bounds__(512) void gemm_tn8p_group_kernel(const Tn8pGroupArg
   int j = 0;
   while (j + 1 < g.n && gidx >= g.first[j + 1]) ++j;
   const int lb = gidx - g.first[j];
+  if (st5_gate_dropped(g.p[j].gate)) return;   // per problem: a group mixes the weight gradients of two layers
   st5_gemm_params p = {};
   p.A.ptr = g.p[j].A; p.A.ld = g.p[j].lda; p.B.ptr = g.p[j].B; p.B.ld = g.p[j].ldb; p.C.ptr = g.p[j].C; p.C.ld = g.p[j].ldc;
   p.asum = g.p[j].asum; p.M = g.p[j].M; p.N = g.p[j].N; p.K = g.p[j].K; p.batch = 1; p.zdiv = 1;
@@ -2802,7 +2813,7 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
     if (rc) return rc;
     MrDesc& d = g_pending.d[g_pending.n++];
     d.slabs = slabs; d.C = reinterpret_cast<float*>(const_cast<void*>(p.C.ptr)); d.asum = p.asum; d.ldc = p.C.ld; d.nsplit = nsplit;
-    d.M = p.M; d.N = p.N; d.beta = p.beta; d.blk0 = g_pending_blocks; d.pad = 0;
+    d.M = p.M; d.N = p.N; d.beta = p.beta; d.blk0 = g_pending_blocks; d.pad = 0; d.gate = p.gate;
     long long blocks = ((long long)p.M * p.N / 4 + 255) / 256;
     if (blocks > 1024) blocks = 1024;
     g_pending_blocks += (int)blocks;
@@ -2820,7 +2831,7 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
     if (blocks > 2048) blocks = 2048;
     hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slabs,
                        reinterpret_cast<float*>(const_cast<void*>(p.C.ptr)), nsplit, p.M, p.N, (long long)p.C.ld, p.C.rpb,
-                       (long long)p.C.bstride, p.beta, p.asum);
+                       (long long)p.C.bstride, p.beta, p.asum, p.gate);
     HIP_CHECK_LAUNCH();
     return ST5_OK;
   }
@@ -2919,7 +2930,7 @@ extern "C" int st5_gemm_tn_group(const st5_gemm_params* list, int32_t n, int dty
     if (ph) {
       Tn8pProb& q = g8.p[m];
       q.A = p.A.ptr; q.B = p.B.ptr; q.C = const_cast<void*>(p.C.ptr); q.asum = p.asum; q.lda = p.A.ld; q.ldb = p.B.ld; q.ldc = p.C.ld;
-      q.M = p.M; q.N = p.N; q.K = p.K; q.beta = p.beta;
+      q.M = p.M; q.N = p.N; q.K = p.K; q.beta = p.beta; q.gate = p.gate;
       g8.tiles[m] = tiles; g8.first[m] = (int)padded;
     } else {
       g.p[m] = p; g.tiles[m] = tiles; g.first[m] = (int)padded;

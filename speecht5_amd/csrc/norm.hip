@@ -167,7 +167,26 @@ __global__ __launch_bounds__(256) void ln_fwd_vec_kernel(const T* __restrict__ x
                                                          float* __restrict__ mean, float* __restrict__ rstd,
                                                          long long rows, int cols, float eps,
                                                          const float* __restrict__ keep, const T* __restrict__ skip,
-                                                         unsigned char* __restrict__ q8 = nullptr, unsigned char* __restrict__ s8 = nullptr) {
+                                                         unsigned char* __restrict__ q8 = nullptr, unsigned char* __restrict__ s8 = nullptr,
+                                                         const float* __restrict__ gate = nullptr) {
+  // gate (layer gate, st5_layernorm_fwd_gate): *gate == 0 -> a LayerNorm inside a dropped layer exits (y, mean, rstd are read by that
+  // layer alone); the layer's LAST LayerNorm (skip given) writes y = skip without reading x, mean / rstd stay unwritten
+  if (st5_gate_dropped(gate)) {
+    if (skip == nullptr) return;
+    const int lane_ = threadIdx.x & 63;
+    const long long r0 = ((long long)blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW;
+#pragma unroll
+    for (int r = 0; r < RPW; ++r) {
+      if (r0 + r >= rows) break;
+      const long long ro = (r0 + r) * cols;
+#pragma unroll
+      for (int i = 0; i < NV; ++i) {
+        const int c = (i * 64 + lane_) * 4;
+        if (c < cols) { float o[4]; load4f<T>(skip + ro + c, o); store4f<T>(y + ro + c, o); }
+      }
+    }
+    return;
+  }
   // keep / skip (LayerDrop gate, st5_layernorm_gated_fwd): *keep == 0 -> y = skip (the layer's input) instead of LN(x)
   const bool dropped = keep != nullptr && *keep == 0.f;
   const int lane = threadIdx.x & 63;
@@ -255,7 +274,15 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const T* __restrict__ d
                                                          float* __restrict__ part, long long rows, int cols,
                                                          T* __restrict__ dxd, float drop_p, unsigned long long seed,
                                                          const float* __restrict__ keep, const float* __restrict__ beta = nullptr,
-                                                         const T* __restrict__ addend = nullptr) {
+                                                         const T* __restrict__ addend = nullptr, const float* __restrict__ gate = nullptr) {
+  // gate (layer gate, st5_layernorm_bwd_gate): *gate == 0 -> the LayerNorm belongs to a dropped layer: dy, x, mean and rstd are not read
+  // (the skipped forward never wrote them), dx / dxd are not written (only that layer's launches would read them) and the block
+  // partials are stored as zeros, so that the immediate or deferred final reduction adds nothing to dgamma / dbeta
+  if (st5_gate_dropped(gate)) {
+    if (PG)
+      for (int c = threadIdx.x; c < 2 * cols; c += 256) part[(long long)blockIdx.x * 2 * cols + c] = 0.f;
+    return;
+  }
   // addend (st5_layernorm_bwd_add, round 6): dx = LayerNorm backward + addend -- the gradient of a pre-LN block's residual connection
   // (y = x + f(LN(x))), handed over by the Linear that added the residual, so that autograd does not sum the two with a kernel of its own
   // keep (LayerDrop gate, st5_layernorm_gated_bwd): *keep == 0 -> the incoming gradient counts as zero (dx = 0, no dgamma / dbeta)
@@ -495,7 +522,8 @@ template <typename T, int MODE>
 __global__ __launch_bounds__(256) void colreduce_kernel(const T* __restrict__ x, const T* __restrict__ dy,
                                                         const float* __restrict__ mean,
                                                         const float* __restrict__ rstd, float* __restrict__ part,
-                                                        long long rows, int cols, long long ld) {
+                                                        long long rows, int cols, long long ld, const float* __restrict__ gate = nullptr) {
+  if (st5_gate_dropped(gate)) return;    // (colreduce_final_kernel then writes zeros without reading the partials)
   __shared__ float red[8][256 + 8];
   const int tx = threadIdx.x & 31, ty = threadIdx.x >> 5;
   const int c0 = blockIdx.x * 256 + tx * 8;
@@ -538,9 +566,13 @@ __global__ __launch_bounds__(256) void colreduce_kernel(const T* __restrict__ x,
   }
 }
 __global__ void colreduce_final_kernel(const float* __restrict__ part, float* __restrict__ out, int nsplit, int cols,
-                                       float scale, int accumulate) {
+                                       float scale, int accumulate, const float* __restrict__ gate = nullptr) {
   const int c = blockIdx.x * blockDim.x + threadIdx.x;
   if (c >= cols) return;
+  if (st5_gate_dropped(gate)) {          // a dropped layer's column sum is LIVE (its dPE gradient): exact zeros / an unchanged accumulator
+    if (!accumulate) out[c] = 0.f;
+    return;
+  }
   float s = 0.f;
   for (int j = 0; j < nsplit; ++j) s += part[(long long)j * cols + c];
   s *= scale;
@@ -556,15 +588,15 @@ int nsplit_for(long long rows) {
 
 template <typename T, int MODE>
 int colreduce(const void* x, const void* dy, const float* mean, const float* rstd, float* out, float* ws,
-              long long rows, int cols, long long ld, float scale, int accumulate, hipStream_t s) {
+              long long rows, int cols, long long ld, float scale, int accumulate, hipStream_t s, const float* gate = nullptr) {
   const int ns = nsplit_for(rows);
   dim3 grid((cols + 255) / 256, ns);
   // two stages in both forms (block partials -> ordered final sum; `accumulate` adds to out[] there): the single-launch
   // variant with fp32 atomics made bias gradients depend on the order in which blocks retire
   hipLaunchKernelGGL((colreduce_kernel<T, MODE>), grid, dim3(256), 0, s, (const T*)x, (const T*)dy, mean, rstd, ws,
-                     rows, cols, ld);
+                     rows, cols, ld, gate);
   hipLaunchKernelGGL(colreduce_final_kernel, dim3((cols + 255) / 256), dim3(256), 0, s, ws, out, ns, cols, scale,
-                     accumulate);
+                     accumulate, gate);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
@@ -572,9 +604,11 @@ int colreduce(const void* x, const void* dy, const float* mean, const float* rst
 }  // namespace
 
 static int layernorm_fwd(const void* x, const float* gamma, const float* beta, void* y, float* mean,
-                         float* rstd, int64_t rows, int32_t cols, float eps, int dtype, void* stream, const float* keep, const void* skip) {
+                         float* rstd, int64_t rows, int32_t cols, float eps, int dtype, void* stream, const float* keep, const void* skip,
+                         const float* gate = nullptr) {
   if (!x || !y || !gamma || !beta || rows < 0 || cols <= 0 || cols > MAXCH * 512) return ST5_ERR_ARG;
   if (keep && (!skip || cols % 4 != 0 || cols > 2048)) return ST5_ERR_ARG;    // (the gate lives in the vector kernels only)
+  if (gate && ((skip && !keep) || cols % 4 != 0 || cols > 2048)) return ST5_ERR_ARG;   // (and so does the layer gate: no ungated fall-back)
   if (rows == 0) return ST5_OK;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((rows + 3) / 4));
@@ -583,7 +617,7 @@ static int layernorm_fwd(const void* x, const float* gamma, const float* beta, v
     dim3 vgrid((unsigned)((rows + 4 * RPW - 1) / (4 * RPW)));
 #define LNV(TT, NV_)                                                                                                 \
   hipLaunchKernelGGL((ln_fwd_vec_kernel<TT, NV_>), vgrid, dim3(256), 0, s, (const TT*)x, gamma, beta, (TT*)y, mean, rstd, \
-                     (long long)rows, cols, eps, keep, (const TT*)skip)
+                     (long long)rows, cols, eps, keep, (const TT*)skip, (unsigned char*)nullptr, (unsigned char*)nullptr, gate)
 #define LNV_T(TT)                                                                                                     \
   do {                                                                                                                \
     if (cols <= 256) LNV(TT, 1); else if (cols <= 512) LNV(TT, 2); else if (cols <= 768) LNV(TT, 3);                  \
@@ -679,6 +713,14 @@ extern "C" int st5_layernorm_gated_fwd(const void* x, const float* gamma, const 
   if (!keep || !skip) return ST5_ERR_ARG;
   return layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, cols, eps, dtype, stream, keep, skip);
 }
+/* st5_layernorm_fwd (keep == skip == NULL) or st5_layernorm_gated_fwd (both given) carrying the layer gate: *gate == 0 -> a plain LayerNorm
+ * writes nothing, a gated one writes y = skip without reading x and leaves mean / rstd alone.  gate NULL or *gate != 0: the ungated call. */
+extern "C" int st5_layernorm_fwd_gate(const void* x, const float* gamma, const float* beta, void* y, float* mean, float* rstd, int64_t rows,
+                                      int32_t cols, float eps, const float* keep, const void* skip, const float* gate, int dtype,
+                                      void* stream) {
+  if ((keep == nullptr) != (skip == nullptr)) return ST5_ERR_ARG;
+  return layernorm_fwd(x, gamma, beta, y, mean, rstd, rows, cols, eps, dtype, stream, keep, skip, gate);
+}
 
 extern "C" int64_t st5_layernorm_bwd_ws_bytes(int64_t rows, int32_t cols) {
   const int64_t a = (int64_t)nsplit_for(rows) * cols * sizeof(float);
@@ -689,8 +731,9 @@ extern "C" int64_t st5_layernorm_bwd_ws_bytes(int64_t rows, int32_t cols) {
 static int layernorm_bwd(const void* dy, const void* x, const float* gamma, const float* mean,
                          const float* rstd, void* dx, float* dgamma, float* dbeta, void* ws, int64_t rows,
                          int32_t cols, void* dx_dropped, float drop_p, uint64_t drop_seed, int dtype, void* stream, const float* keep,
-                         const void* addend = nullptr) {
+                         const void* addend = nullptr, const float* gate = nullptr) {
   if (addend && (!dx || cols % 4 || cols > 2048)) return ST5_ERR_ARG;
+  if (gate && (!dx || cols % 4 || cols > 2048)) return ST5_ERR_ARG;      // (the layer gate lives in the vector kernel only)
   if (keep && (!dx || cols % 4 || cols > 2048)) return ST5_ERR_ARG;
   if (dx_dropped && (!dx || cols % 4 || cols > 2048 || drop_p <= 0.f || drop_p >= 1.f)) return ST5_ERR_ARG;
   if (!dy || !x || !gamma || !mean || !rstd || rows < 0 || cols <= 0 || cols > MAXCH * 512) return ST5_ERR_ARG;
@@ -734,10 +777,10 @@ static int layernorm_bwd(const void* dy, const void* x, const float* gamma, cons
   do {                                                                                                                  \
     if (pg) hipLaunchKernelGGL((ln_bwd_vec_kernel<TT, NV_, true>), dim3(nb), dim3(256), shm, s, (const TT*)dy, (const TT*)x, gamma, \
                                mean, rstd, (TT*)dx, (float*)ws, (long long)rows, cols, (TT*)dx_dropped, drop_p,          \
-                               (unsigned long long)drop_seed, keep, (const float*)nullptr, (const TT*)addend);          \
+                               (unsigned long long)drop_seed, keep, (const float*)nullptr, (const TT*)addend, gate);    \
     else hipLaunchKernelGGL((ln_bwd_vec_kernel<TT, NV_, false>), dim3(nb), dim3(256), 0, s, (const TT*)dy, (const TT*)x, gamma, \
                             mean, rstd, (TT*)dx, (float*)ws, (long long)rows, cols, (TT*)dx_dropped, drop_p,            \
-                            (unsigned long long)drop_seed, keep, (const float*)nullptr, (const TT*)addend);             \
+                            (unsigned long long)drop_seed, keep, (const float*)nullptr, (const TT*)addend, gate);       \
   } while (0)
 #define LBV_T(TT)                                                                                                     \
   do {                                                                                                                \
@@ -797,6 +840,14 @@ extern "C" int st5_layernorm_gated_bwd(const void* dy, const void* x, const floa
   if (!keep) return ST5_ERR_ARG;
   return layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, rows, cols, dx_dropped, drop_p, drop_seed, dtype, stream, keep);
 }
+/* st5_layernorm_bwd (keep NULL) or st5_layernorm_gated_bwd carrying the layer gate: *gate == 0 -> no operand is read, dx / dx_dropped are not
+ * written and nothing is added to dgamma / dbeta, with the immediate and with the deferred reduction (the block partials are zeros). */
+extern "C" int st5_layernorm_bwd_gate(const void* dy, const void* x, const float* gamma, const float* mean, const float* rstd, void* dx,
+                                      float* dgamma, float* dbeta, void* ws, int64_t rows, int32_t cols, void* dx_dropped, float drop_p,
+                                      uint64_t drop_seed, const float* keep, const float* gate, int dtype, void* stream) {
+  return layernorm_bwd(dy, x, gamma, mean, rstd, dx, dgamma, dbeta, ws, rows, cols, dx_dropped, drop_p, drop_seed, dtype, stream, keep,
+                       nullptr, gate);
+}
 
 #undef g_ln_pending
 #undef g_ln_blocks
@@ -828,6 +879,17 @@ extern "C" int st5_colsum_ws(const void* x, float* out, void* ws, int64_t rows, 
     return colreduce<bf16_t, 0>(x, nullptr, nullptr, nullptr, out, (float*)ws, rows, cols, ld, scale, accumulate, s);
   if (dtype == ST5_F32)
     return colreduce<float, 0>(x, nullptr, nullptr, nullptr, out, (float*)ws, rows, cols, ld, scale, accumulate, s);
+  return ST5_ERR_ARG;
+}
+/* st5_colsum_ws carrying the layer gate: *gate == 0 -> x and the partials are not read; out = exact zeros (overwrite form) or unchanged. */
+extern "C" int st5_colsum_ws_gate(const void* x, float* out, void* ws, int64_t rows, int32_t cols, int64_t ld, float scale,
+                                  int32_t accumulate, const float* gate, int dtype, void* stream) {
+  if (!x || !out || !ws || rows < 0 || cols <= 0) return ST5_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == ST5_BF16)
+    return colreduce<bf16_t, 0>(x, nullptr, nullptr, nullptr, out, (float*)ws, rows, cols, ld, scale, accumulate, s, gate);
+  if (dtype == ST5_F32)
+    return colreduce<float, 0>(x, nullptr, nullptr, nullptr, out, (float*)ws, rows, cols, ld, scale, accumulate, s, gate);
   return ST5_ERR_ARG;
 }
 extern "C" int64_t st5_colsum_ws_bytes(int64_t rows, int32_t cols) {

@@ -757,6 +757,83 @@ def as_float(x):
 
 
 # -------------------------------------------------------------------------------------------------
+# LayerDrop layer gate.  Inside a step recorded for replay a dropped layer cannot be skipped on the host, but its kernels
+# can exit: every native launch of a GATED layer carries the layer's `keep` float (the one its last LayerNorm selects on) and returns
+# before its first load when the layer is dropped.  layer_gate_scope makes the gate ambient for the layer's forward_rows; the autograd
+# Functions launched inside remember it (ctx.lgate) and re-install it around their backward.  A layer is gated as a whole or not at all
+# (layer_exit_ok): every launch inside must have a gate-capable entry.
+# -------------------------------------------------------------------------------------------------
+LAYER_EXIT = os.environ.get("ST5_LAYER_EXIT", "1") != "0"    # A/B switch: 0 = select only (a dropped layer runs in full)
+_LG = SimpleNamespace(keep=None, nan_fill=False)
+
+
+def set_layer_exit(on):
+    """A/B switch of the exit form (tests): False = select only."""
+    global LAYER_EXIT
+    LAYER_EXIT = bool(on)
+
+
+def set_layer_exit_nan_fill(on):
+    """TEST ONLY: allocate every output of a gated launch NaN-filled instead of uninitialised, so that stale memory cannot hide a read
+    of a dropped layer's dead buffer, nor a kept kernel that does not write all of its output."""
+    _LG.nan_fill = bool(on)
+
+
+def layer_exit_ok(dtype, head_dim, want_probs=False, shared_kv=True):
+    """Can every launch of a post-LN transformer layer carry the gate?  bf16 on the fused attention kernels, no attention probabilities
+    wanted, fp8 mode off, and (decoder) the cross-attention keys / values taken from the all-layer projection (KVShare): a per-layer
+    K|V projection would hand a dropped layer's unwritten data gradient to the encoder output."""
+    return LAYER_EXIT and _can_flash(dtype, head_dim, want_probs) and not _FP8.enabled and shared_kv
+
+
+class layer_gate_scope:
+    """with layer_gate_scope(gate): the layer's launches carry gate.keep (gate None or not gate.exit: no effect)."""
+
+    def __init__(self, gate):
+        self.keep = gate.keep if (gate is not None and gate.exit) else None
+
+    def __enter__(self):
+        self.prev = _lgate_set(self.keep)
+
+    def __exit__(self, *exc):
+        _lgate_set(self.prev)
+        return False
+
+
+def _lgate_set(keep):
+    prev, _LG.keep = _LG.keep, keep
+    hip.set_gate(0 if keep is None else keep.data_ptr())
+    return prev
+
+
+def _lg_fwd(fn):
+    """forward of an autograd Function launched inside gated layers: remember the ambient gate for the backward."""
+    def forward(ctx, *args):
+        ctx.lgate = _LG.keep
+        return fn(ctx, *args)
+    forward.__doc__ = fn.__doc__
+    return forward
+
+
+def _lg_bwd(fn):
+    """backward: its launches carry the gate the forward ran under."""
+    def backward(ctx, *grads):
+        prev = _lgate_set(ctx.lgate)
+        try:
+            return fn(ctx, *grads)
+        finally:
+            _lgate_set(prev)
+    return backward
+
+
+def _gout(t):
+    """An output buffer of a (possibly gated) launch; see set_layer_exit_nan_fill."""
+    if _LG.nan_fill and _LG.keep is not None and t is not None and t.is_floating_point():
+        t.fill_(float("nan"))
+    return t
+
+
+# -------------------------------------------------------------------------------------------------
 # raw kernel wrappers (no autograd)
 # -------------------------------------------------------------------------------------------------
 def _colsum_into(x2d, ld, cols, out, col_off=0, scale=1.0):
@@ -764,6 +841,10 @@ def _colsum_into(x2d, ld, cols, out, col_off=0, scale=1.0):
     rows = x2d.shape[0]
     L = hip.lib()
     ws = hip.workspace(L.st5_colsum_ws_bytes(rows, cols), x2d.device)
+    if hip.gate():      # (a dropped layer adds nothing)
+        hip.check(L.st5_colsum_ws_gate(x2d.data_ptr() + col_off * x2d.element_size(), out.data_ptr(), ws.data_ptr(), rows, cols,
+                                       ld, scale, 1, hip.gate(), _dt(x2d), hip.stream()), "st5_colsum_ws_gate")
+        return
     hip.check(L.st5_colsum_ws(x2d.data_ptr() + col_off * x2d.element_size(), out.data_ptr(), ws.data_ptr(), rows, cols,
                               ld, scale, 1, _dt(x2d), hip.stream()), "st5_colsum_ws")
 
@@ -980,7 +1061,7 @@ def _wgrad_queue(A, B, C, M, N, K, dt, flags, asum, keep):
         ent = None
     if ent is None:
         ent = q[st] = [[], [], 0, dt, phased]
-    ent[0].append((A, B, C, M, N, K, flags, 1.0, asum))
+    ent[0].append((A, B, C, M, N, K, flags, 1.0, asum, hip.gate()))      # (the layer gate travels with the problem)
     ent[1].append(keep)
     ent[2] += tiles
     if ent[2] >= flush_at:
@@ -1073,6 +1154,7 @@ class LinearFunction(torch.autograd.Function):
     speech_decoder_postnet.py:61-63, text_decoder_postnet.py:59-65, speech_encoder_postnet.py:88."""
 
     @staticmethod
+    @_lg_fwd
     def forward(ctx, x, residual, act, dropout_p, nw, *wb):
         relay_in = None
         if isinstance(nw, tuple):
@@ -1088,9 +1170,9 @@ class LinearFunction(torch.autograd.Function):
         ldn = _ceil8(N)
         Wc = fused_weight(weights, dtype)
         bc = fused_bias(biases)
-        y = torch.empty(M, ldn, dtype=dtype, device=x.device)
+        y = _gout(torch.empty(M, ldn, dtype=dtype, device=x.device))
         need_pre = act != ACT_NONE and any(ctx.needs_input_grad)
-        pre = torch.empty(M, ldn, dtype=dtype, device=x.device) if need_pre else None
+        pre = _gout(torch.empty(M, ldn, dtype=dtype, device=x.device)) if need_pre else None
         seed = next_seed() if dropout_p > 0 else 0
         if dropout_p > 0:
             assert ldn == N, "dropout epilogue requires an 8-aligned output width"
@@ -1112,6 +1194,7 @@ class LinearFunction(torch.autograd.Function):
         return out.reshape(x.shape[:-1] + (N,))
 
     @staticmethod
+    @_lg_bwd
     def backward(ctx, dy):
         x2, pre, Wc = ctx.saved_tensors
         weights, biases, act, p, seed, M, N, K, ldn, xshape, has_res = ctx.meta
@@ -1130,13 +1213,14 @@ class LinearFunction(torch.autograd.Function):
         if p > 0:
             g = _dropped_grad(g, p, seed)
         if act != ACT_NONE:
+            assert not hip.gate(), "a Linear with an activation inside a gated layer: st5_act_bwd carries no layer gate"
             g2 = torch.empty_like(g)
             hip.check(hip.lib().st5_act_bwd(g.data_ptr(), pre.data_ptr(), g2.data_ptr(), g.numel(), act, _dt(g),
                                             hip.stream()), "st5_act_bwd")
             g = g2
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty(M, K, dtype=dtype, device=x2.device)
+            dx = _gout(torch.empty(M, K, dtype=dtype, device=x2.device))
             if N % 8 == 0:
                 # dX = G . W as an NT GEMM against the cached transposed weights W^T [K, N]
                 _nt_gemm(g, weights, True, hip.operand(dx, K), M, K, N, dtype,
@@ -1219,15 +1303,16 @@ class _RelayedResidual:
 # -------------------------------------------------------------------------------------------------
 class FFNFunction(torch.autograd.Function):
     @staticmethod
+    @_lg_fwd
     def forward(ctx, x, residual, w1, b1, w2, b2, act, p_act, p_out, relay_out=None):
         dtype = x.dtype
         x2 = _rows(x)
         M, d = x2.shape
         Fd = w1.shape[0]
         W1, W2 = fused_weight([w1], dtype), fused_weight([w2], dtype)
-        h = torch.empty(M, Fd, dtype=dtype, device=x.device)
-        hpre = torch.empty(M, Fd, dtype=dtype, device=x.device)
-        y = torch.empty(M, w2.shape[0], dtype=dtype, device=x.device)
+        h = _gout(torch.empty(M, Fd, dtype=dtype, device=x.device))
+        hpre = _gout(torch.empty(M, Fd, dtype=dtype, device=x.device))
+        y = _gout(torch.empty(M, w2.shape[0], dtype=dtype, device=x.device))
         s1 = next_seed() if p_act > 0 else 0
         s2 = next_seed() if p_out > 0 else 0
         # residual == "x": the block input itself is the residual (post-LN layers).  Its gradient dY is then added in the
@@ -1246,6 +1331,7 @@ class FFNFunction(torch.autograd.Function):
         return y.view(x.shape[:-1] + (w2.shape[0],))
 
     @staticmethod
+    @_lg_bwd
     def backward(ctx, dy):
         x2, h, hpre, W1, W2 = ctx.saved_tensors
         w1, b1, w2, b2, act, p_act, p_out, s1, s2, xshape, has_res, res_is_x = ctx.meta
@@ -1261,13 +1347,13 @@ class FFNFunction(torch.autograd.Function):
         if p_out > 0:
             g = _dropped_grad(g, p_out, s2)
         # dHpre = (G . W2) * act'(Hpre) [* activation-dropout mask]   (fused epilogue)
-        dh = torch.empty(M, Fd, dtype=dtype, device=x2.device)
+        dh = _gout(torch.empty(M, Fd, dtype=dtype, device=x2.device))
         _nt_gemm(g, [w2], True, hip.operand(dh, Fd), M, Fd, dout, dtype,     # (B operand: W2^T [Fd, dout])
                  quant_out=dh if ctx.needs_input_grad[0] else None,
                  P=hip.operand(hpre, Fd), act=act, flags=hip.DACT, dropout_p=p_act, seed=s1)
         dx = None
         if ctx.needs_input_grad[0]:
-            dx = torch.empty(M, d, dtype=dtype, device=x2.device)
+            dx = _gout(torch.empty(M, d, dtype=dtype, device=x2.device))
             _nt_gemm(dh, [w1], True, hip.operand(dx, d), M, d, Fd, dtype,     # (B operand: W1^T [d, Fd])
                      R=hip.operand(g_in, d) if res_is_x else None)
             dx = dx.view(xshape)
@@ -1478,12 +1564,14 @@ def guided_attention_loss(att, ilens, olens, sigma, alpha):
 # -------------------------------------------------------------------------------------------------
 class LayerNormFunction(torch.autograd.Function):
     @staticmethod
+    @_lg_fwd
     def forward(ctx, x, weight, bias, eps, gate=None, q8=False, relay=None):
         x2 = _rows(x)
         rows, cols = x2.shape
-        y = torch.empty_like(x2)
-        mean = torch.empty(rows, dtype=torch.float32, device=x.device)
-        rstd = torch.empty(rows, dtype=torch.float32, device=x.device)
+        y = _gout(torch.empty_like(x2))
+        mean = _gout(torch.empty(rows, dtype=torch.float32, device=x.device))
+        rstd = _gout(torch.empty(rows, dtype=torch.float32, device=x.device))
+        lg = hip.gate()
         if q8 and gate is None and _FP8.enabled and (_FP8.fuse & 1) and x2.dtype == torch.bfloat16 and cols % 128 == 0 and cols <= 2048 and \
                 rows >= _FP8.min_rows:
             # fp8 mode: the consumer of a pre-LN layer's LayerNorm is an fp8 GEMM (QKV / fc1) -- its operand image comes out of this pass
@@ -1492,6 +1580,12 @@ class LayerNormFunction(torch.autograd.Function):
                                                      rstd.data_ptr(), q.data_ptr(), sc.data_ptr(), rows, cols, eps, hip.stream()),
                       "st5_layernorm_fwd_q8")
             _q8_tag(y, q, sc, rows, cols)
+        elif lg:    # inside a gated layer: a dropped layer's LayerNorm exits; its LAST one (gate given) writes the layer's input instead
+            skip = gate.skip if gate is not None else None
+            assert gate is None or (gate.keep.data_ptr() == lg and skip.shape == x2.shape and skip.dtype == x2.dtype and skip.is_contiguous())
+            hip.check(hip.lib().st5_layernorm_fwd_gate(x2.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
+                                                       rstd.data_ptr(), rows, cols, eps, lg if gate is not None else None, hip.ptr(skip), lg,
+                                                       _dt(x), hip.stream()), "st5_layernorm_fwd_gate")
         elif gate is None:
             hip.check(hip.lib().st5_layernorm_fwd(x2.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), mean.data_ptr(),
                                                   rstd.data_ptr(), rows, cols, eps, _dt(x), hip.stream()), "st5_layernorm_fwd")
@@ -1511,16 +1605,18 @@ class LayerNormFunction(torch.autograd.Function):
         return y.view(x.shape)
 
     @staticmethod
+    @_lg_bwd
     def backward(ctx, dy):
         x2, mean, rstd = ctx.saved_tensors
         weight, bias, xshape, tag = ctx.meta
         rows, cols = x2.shape
         g = dy.contiguous().view(rows, cols)
         L = hip.lib()
-        dx = torch.empty_like(x2) if ctx.needs_input_grad[0] else None
+        lg = hip.gate()
+        dx = _gout(torch.empty_like(x2)) if ctx.needs_input_grad[0] else None
         dxd = None
         if tag is not None and dx is not None:
-            dxd = torch.empty_like(x2)
+            dxd = _gout(torch.empty_like(x2))
             if len(_drop_grads) > 64:
                 _drop_grads.clear()
             _drop_grads[dx.data_ptr()] = (tag[0], tag[1], rows, cols, dxd)
@@ -1532,7 +1628,15 @@ class LayerNormFunction(torch.autograd.Function):
         if relay is not None and relay.grad is not None:
             # a pre-LN block's residual gradient (handed over by the Linear / FFN that added the residual, earlier in this backward pass)
             addend, relay.grad = relay.grad, None
-        if addend is not None and gate is None and dx is not None and dxd is None:
+        if lg:      # inside a gated layer (both uses): a dropped layer reads nothing, adds nothing to dgamma / dbeta, leaves dx unwritten
+            assert dx is not None and addend is None
+            if gate is not None:
+                gate.g_out = g
+            hip.check(L.st5_layernorm_bwd_gate(g.data_ptr(), x2.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(),
+                                               hip.ptr(dx), hip.ptr(gw), hip.ptr(gb), ws.data_ptr(), rows, cols, hip.ptr(dxd),
+                                               tag[0] if dxd is not None else 0.0, tag[1] if dxd is not None else 0,
+                                               lg if gate is not None else None, lg, _dt(x2), hip.stream()), "st5_layernorm_bwd_gate")
+        elif addend is not None and gate is None and dx is not None and dxd is None:
             assert addend.shape == (rows, cols) and addend.dtype == x2.dtype and addend.is_contiguous()
             hip.check(L.st5_layernorm_bwd_add(g.data_ptr(), x2.data_ptr(), weight.data_ptr(), mean.data_ptr(), rstd.data_ptr(), dx.data_ptr(),
                                               hip.ptr(gw), hip.ptr(gb), ws.data_ptr(), rows, cols, addend.data_ptr(), _dt(x2), hip.stream()),
@@ -1749,11 +1853,17 @@ def _flash_fwd(q, k, v, B, H, T, S, hd, pe, maxrel, kpm, causal, p_drop, seed, s
     encoder layer at cfg 2) for the backward instead of recomputing it there with a batched GEMM."""
     dev = q[0].device
     d = H * hd
-    ctx = torch.empty(B * T, d, dtype=torch.bfloat16, device=dev)
-    lse = torch.empty(B * H, T, dtype=torch.float32, device=dev)
+    ctx = _gout(torch.empty(B * T, d, dtype=torch.bfloat16, device=dev))
+    lse = _gout(torch.empty(B * H, T, dtype=torch.float32, device=dev))
     nb = pe.shape[0] if pe is not None else 0
     # relative-position table workspace ([.., 8 | nb | 8] rows for the second-generation kernels); kept for the backward
-    qp = torch.empty(B * H, T, hip.lib().st5_flash_attn_qp_row(nb), dtype=torch.bfloat16, device=dev) if pe is not None else None
+    qp = _gout(torch.empty(B * H, T, hip.lib().st5_flash_attn_qp_row(nb), dtype=torch.bfloat16, device=dev)) if pe is not None else None
+    if hip.gate():
+        hip.check(hip.lib().st5_flash_attn_fwd_qp_gate(_eptr(q), q[1], _eptr(k), k[1], _eptr(v), v[1], ctx.data_ptr(), d, lse.data_ptr(),
+                                                       hip.ptr(pe), hip.ptr(kpm), B, H, T, S, hd, nb, maxrel, 1 if causal else 0, _ceil8(S),
+                                                       hd ** -0.5, p_drop, seed, hip.ptr(qp), hip.gate(), hip.BF16, hip.stream()),
+                  "st5_flash_attn_fwd_qp_gate")
+        return ctx, lse, (qp if save_qp else None)
     hip.check(hip.lib().st5_flash_attn_fwd_qp(_eptr(q), q[1], _eptr(k), k[1], _eptr(v), v[1], ctx.data_ptr(), d, lse.data_ptr(),
                                               hip.ptr(pe), hip.ptr(kpm), B, H, T, S, hd, nb, maxrel, 1 if causal else 0, _ceil8(S),
                                               hd ** -0.5, p_drop, seed, hip.ptr(qp), hip.BF16, hip.stream()), "st5_flash_attn_fwd_qp")
@@ -1782,29 +1892,39 @@ def _attn_side_raw():
 
 
 def _flash_bwd(dctx, ctx, lse, q, k, v, dq, dk, dv, B, H, T, S, hd, pe, want_dpe, maxrel, kpm, causal, p_drop, seed, qp=None,
-               pe_t=None):
-    """Writes dq/dk/dv slices; returns dPE (fp32) or None."""
+               pe_t=None, dkv_live=False):
+    """Writes dq/dk/dv slices; returns dPE (fp32) or None.  dkv_live (inside a gated layer): dk / dv are read outside the layer (the shared
+    cross-attention gradient buffer), so a dropped layer stores zeros there; everything else it leaves unwritten -- except dPE, zeros."""
+    lg = hip.gate()
     dev = dctx.device
     dtype = torch.bfloat16
     d = H * hd
     BH = B * H
     alpha = hd ** -0.5
-    dvec = torch.empty(BH * T, dtype=torch.float32, device=dev)
+    dvec = _gout(torch.empty(BH * T, dtype=torch.float32, device=dev))
     dqp = None
     nb = 0
     qt, qld, qoff = q
     if pe is not None:
         nb = pe.shape[0]
+        assert qp is not None or not lg, "a gated layer keeps the forward's relative-position table (st5_flash_attn_qp_table carries no gate)"
         if qp is None:   # the kernels work in the log2 domain: qp = scale * log2(e) * q.pe^T (+ replicated end chunks)
             qp = torch.empty(BH, T, hip.lib().st5_flash_attn_qp_row(nb), dtype=dtype, device=dev)
             hip.check(hip.lib().st5_flash_attn_qp_table(_eptr(q), q[1], pe.data_ptr(), qp.data_ptr(), B, H, T, nb, alpha, hip.BF16,
                                                         hip.stream()), "st5_flash_attn_qp_table")
-        dqp = torch.empty(BH, T, nb, dtype=dtype, device=dev)
-    hip.check(hip.lib().st5_flash_attn_bwd_2s(_eptr(q), q[1], _eptr(k), k[1], _eptr(v), v[1], ctx.data_ptr(), d, dctx.data_ptr(), d,
-                                              _eptr(dq), dq[1], _eptr(dk), dk[1], _eptr(dv), dv[1], lse.data_ptr(), dvec.data_ptr(),
-                                              hip.ptr(pe), hip.ptr(qp), hip.ptr(dqp), hip.ptr(kpm), B, H, T, S, hd, nb, maxrel,
-                                              1 if causal else 0, _ceil8(S), alpha, p_drop, seed, hip.BF16, hip.stream(),
-                                              _attn_side_raw()), "st5_flash_attn_bwd_2s")
+        dqp = _gout(torch.empty(BH, T, nb, dtype=dtype, device=dev))
+    if lg:
+        hip.check(hip.lib().st5_flash_attn_bwd_2s_gate(_eptr(q), q[1], _eptr(k), k[1], _eptr(v), v[1], ctx.data_ptr(), d, dctx.data_ptr(), d,
+                                                       _eptr(dq), dq[1], _eptr(dk), dk[1], _eptr(dv), dv[1], lse.data_ptr(), dvec.data_ptr(),
+                                                       hip.ptr(pe), hip.ptr(qp), hip.ptr(dqp), hip.ptr(kpm), B, H, T, S, hd, nb, maxrel,
+                                                       1 if causal else 0, _ceil8(S), alpha, p_drop, seed, lg, 1 if dkv_live else 0, hip.BF16,
+                                                       hip.stream(), _attn_side_raw()), "st5_flash_attn_bwd_2s_gate")
+    else:
+        hip.check(hip.lib().st5_flash_attn_bwd_2s(_eptr(q), q[1], _eptr(k), k[1], _eptr(v), v[1], ctx.data_ptr(), d, dctx.data_ptr(), d,
+                                                  _eptr(dq), dq[1], _eptr(dk), dk[1], _eptr(dv), dv[1], lse.data_ptr(), dvec.data_ptr(),
+                                                  hip.ptr(pe), hip.ptr(qp), hip.ptr(dqp), hip.ptr(kpm), B, H, T, S, hd, nb, maxrel,
+                                                  1 if causal else 0, _ceil8(S), alpha, p_drop, seed, hip.BF16, hip.stream(),
+                                                  _attn_side_raw()), "st5_flash_attn_bwd_2s")
     if pe is None:
         return None
     dqt, dqld, dqoff = dq
@@ -1818,13 +1938,17 @@ def _flash_bwd(dctx, ctx, lse, q, k, v, dq, dk, dv, B, H, T, S, hd, pe, want_dpe
                  flags=hip.B_KSTRIDED, alpha=alpha, beta=1.0)
     if not want_dpe:
         return None
-    part = torch.empty(BH, nb, hd, dtype=torch.float32, device=dev)
+    part = _gout(torch.empty(BH, nb, hd, dtype=torch.float32, device=dev))
     hip.gemm(hip.operand(dqp, nb, zs0=H * T * nb, zs1=T * nb), hip.operand(qt, qld, off=qoff, zs0=T * qld, zs1=hd),
              hip.operand(part, hd, zs0=H * nb * hd, zs1=nb * hd), nb, hd, T, hip.BF16, batch=BH, zdiv=H,
              flags=hip.A_KSTRIDED | hip.B_KSTRIDED | hip.OUT_F32, alpha=alpha)
-    g = torch.empty(nb, hd, dtype=torch.float32, device=dev)
+    g = _gout(torch.empty(nb, hd, dtype=torch.float32, device=dev))
     L = hip.lib()
     ws = hip.workspace(L.st5_colsum_ws_bytes(BH, nb * hd), dev)
+    if lg:      # the layer's dPE gradient is LIVE (the cast and the sum over layers behind it read it): a dropped layer's is exact zeros
+        hip.check(L.st5_colsum_ws_gate(part.data_ptr(), g.data_ptr(), ws.data_ptr(), BH, nb * hd, nb * hd, 1.0, 0, lg, hip.F32, hip.stream()),
+                  "st5_colsum_ws_gate")
+        return g
     hip.check(L.st5_colsum_ws(part.data_ptr(), g.data_ptr(), ws.data_ptr(), BH, nb * hd, nb * hd, 1.0, 0, hip.F32, hip.stream()),
               "st5_colsum_ws")   # (overwrite form: two-stage, no zero fill, fixed summation order)
     return g
@@ -1835,10 +1959,12 @@ class SelfAttentionFunction(torch.autograd.Function):
     table [2*maxrel, hd] in the compute dtype (a differentiable cast / norm_k of the parameter) or None."""
 
     @staticmethod
+    @_lg_fwd
     def forward(ctx_, qkv, pe, kpm, cfg):
         B, H, T, hd, maxrel, causal, p_drop = cfg[:7]
         d = H * hd
         seed = next_seed() if p_drop > 0 else 0
+        assert _LG.keep is None or _can_flash(qkv.dtype, hd, False), "gated layer without the fused attention kernels"
         if _can_flash(qkv.dtype, hd, False):
             ctx, lse, qp = _flash_fwd((qkv, 3 * d, 0), (qkv, 3 * d, d), (qkv, 3 * d, 2 * d), B, H, T, T, hd, pe, maxrel, kpm, causal,
                                       p_drop, seed, save_qp=any(ctx_.needs_input_grad))
@@ -1852,6 +1978,7 @@ class SelfAttentionFunction(torch.autograd.Function):
         return ctx
 
     @staticmethod
+    @_lg_bwd
     def backward(ctx_, dctx):
         cfg, seed, flash = ctx_.meta
         B, H, T, hd, maxrel, causal, p_drop = cfg[:7]
@@ -1859,7 +1986,7 @@ class SelfAttentionFunction(torch.autograd.Function):
         d = H * hd
         if flash:
             qkv, ctx, lse, pe, kpm, qp = ctx_.saved_tensors
-            dqkv = torch.empty_like(qkv)
+            dqkv = _gout(torch.empty_like(qkv))
             dpe = _flash_bwd(dctx.contiguous(), ctx, lse, (qkv, 3 * d, 0), (qkv, 3 * d, d), (qkv, 3 * d, 2 * d), (dqkv, 3 * d, 0),
                              (dqkv, 3 * d, d), (dqkv, 3 * d, 2 * d), B, H, T, T, hd, pe, pe is not None and ctx_.needs_input_grad[1],
                              maxrel, kpm, causal, p_drop, seed, qp=qp, pe_t=pe_t)
@@ -1900,6 +2027,7 @@ class CrossAttentionFunction(torch.autograd.Function):
     the all-layer projection [B*S, kv_ld] and this layer's keys / values start at column kv_off (KVShare)."""
 
     @staticmethod
+    @_lg_fwd
     def forward(ctx_, q, kv, kpm, cfg):
         B, H, T, S, hd, p_drop, want_probs = cfg[:7]
         d = H * hd
@@ -1907,6 +2035,8 @@ class CrossAttentionFunction(torch.autograd.Function):
         if share is not None and share.first is None:
             share.first = id(ctx_)
         seed = next_seed() if p_drop > 0 else 0
+        assert _LG.keep is None or (share is not None and _can_flash(q.dtype, hd, want_probs)), \
+            "gated layer: the cross-attention needs the fused kernels and the shared K|V projection"
         if _can_flash(q.dtype, hd, want_probs):
             ctx, lse, _ = _flash_fwd((q, d, 0), (kv, kld, koff), (kv, kld, koff + d), B, H, T, S, hd, None, 0, kpm, False, p_drop, seed)
             ctx_.save_for_backward(q, kv, ctx, lse, kpm)
@@ -1921,18 +2051,19 @@ class CrossAttentionFunction(torch.autograd.Function):
         return ctx, None
 
     @staticmethod
+    @_lg_bwd
     def backward(ctx_, dctx, dprobs):
         cfg, seed, flash = ctx_.meta
         B, H, T, S, hd, p_drop, _ = cfg[:7]
         d = H * hd
         kld, koff, share = cfg[7:10] if len(cfg) > 7 else (2 * d, 0, None)
         kv = ctx_.saved_tensors[1]
-        dq = torch.empty_like(ctx_.saved_tensors[0])
+        dq = _gout(torch.empty_like(ctx_.saved_tensors[0]))
         dkv = share.grad_buffer(kv) if share is not None else torch.empty_like(kv)
         if flash:
             q, kv, ctx, lse, kpm = ctx_.saved_tensors
             _flash_bwd(dctx.contiguous(), ctx, lse, (q, d, 0), (kv, kld, koff), (kv, kld, koff + d), (dq, d, 0), (dkv, kld, koff),
-                       (dkv, kld, koff + d), B, H, T, S, hd, None, False, 0, kpm, False, p_drop, seed)
+                       (dkv, kld, koff + d), B, H, T, S, hd, None, False, 0, kpm, False, p_drop, seed, dkv_live=True)
         else:
             q, kv, probs, pdrop = ctx_.saved_tensors
             extra = None
@@ -2028,8 +2159,9 @@ class LayerDropGate:
     (st5_skip_grad: a kept layer, 19 of 20, costs one early-exit launch instead of a select and an autograd accumulation).
     Usage (modules/encoder.py, modules/decoder.py):  gate, x = layerdrop_gate(x, keep);  y = layer.forward_rows(x, ..., gate=gate)."""
 
-    def __init__(self, keep, skip):
+    def __init__(self, keep, skip, exit=False):
         self.keep, self.skip = keep, skip      # one device float; the layer's input rows (detached, contiguous)
+        self.exit = exit                       # the layer's launches carry `keep` as their layer gate (layer_gate_scope): dropped = exit
         self.g_out = None                      # the gradient of the gated LayerNorm's output, set by its backward
         self.used = False
 
@@ -2059,10 +2191,11 @@ class LayerDropEnterFunction(torch.autograd.Function):
 LAYERDROP_GATE = os.environ.get("ST5_LAYERDROP_GATE", "1") != "0"    # A/B switch: 0 = the stand-alone select kernels everywhere
 
 
-def layerdrop_gate(x, keep):
-    """(gate, x') for a layer whose last operation is a LayerNorm that accepts `gate=`; x' aliases x."""
+def layerdrop_gate(x, keep, exit=False):
+    """(gate, x') for a layer whose last operation is a LayerNorm that accepts `gate=`; x' aliases x.  exit: every launch of the layer
+    can carry the gate (layer_exit_ok, decided by the caller for the layer as a whole)."""
     x = x.contiguous()
-    gate = LayerDropGate(keep, _rows(x.detach()))
+    gate = LayerDropGate(keep, _rows(x.detach()), exit)
     y = LayerDropEnterFunction.apply(x, gate)
     b = getattr(x, "_st5_boundary", None)
     if b is not None:

@@ -36,7 +36,8 @@ class GemmParams(Structure):
                 ("bias", c_void_p), ("bias_zs", c_int64),
                 ("M", c_int32), ("N", c_int32), ("K", c_int32), ("batch", c_int32), ("zdiv", c_int32),
                 ("act", c_int32), ("flags", c_int32),
-                ("alpha", c_float), ("beta", c_float), ("dropout_p", c_float), ("seed", c_uint64), ("asum", c_void_p)]
+                ("alpha", c_float), ("beta", c_float), ("dropout_p", c_float), ("seed", c_uint64), ("asum", c_void_p),
+                ("gate", c_void_p)]      # LayerDrop layer gate: device address of the layer's `keep` float, or NULL
 
 
 _SIGS = {
@@ -64,6 +65,19 @@ _SIGS = {
                                         c_float, c_void_p, c_void_p, c_int, c_void_p]),
     "st5_layernorm_gated_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                         c_int64, c_int32, c_void_p, c_float, c_uint64, c_void_p, c_int, c_void_p]),
+    "st5_layernorm_fwd_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "st5_layernorm_bwd_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_int64, c_int32, c_void_p, c_float, c_uint64, c_void_p, c_void_p, c_int, c_void_p]),
+    "st5_colsum_ws_gate": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_float, c_int32, c_void_p, c_int,
+                                   c_void_p]),
+    "st5_flash_attn_fwd_qp_gate": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p,
+                                           c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_float, c_float, c_uint64, c_void_p, c_void_p, c_int, c_void_p]),
+    "st5_flash_attn_bwd_2s_gate": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                           c_int32, c_float, c_float, c_uint64, c_void_p, c_int32, c_int, c_void_p, c_void_p]),
     "st5_layernorm_defer": (c_int, [c_int, c_void_p]),
     "st5_layernorm_flush": (c_int, [c_void_p]),
     "st5_layernorm_bwd_ws_bytes": (c_int64, [c_int64, c_int32]),
@@ -384,6 +398,22 @@ class GemmProfiler:
 
 profiler = GemmProfiler()
 
+# The ambient LayerDrop layer gate: device address of the `keep` float of the gated transformer layer whose launches are being issued
+# (functional.layer_gate_scope sets it for the layer's forward, the autograd Functions restore it in their backward), or 0.  Every
+# st5_gemm launched meanwhile carries it (st5_gemm_params.gate): a dropped layer's launches exit at once.
+_gate = 0
+
+
+def set_gate(addr):
+    """Install the ambient layer gate (0 / None = none); returns the previous one."""
+    global _gate
+    prev, _gate = _gate, int(addr or 0)
+    return prev
+
+
+def gate():
+    return _gate
+
 
 def gemm(A, B, C, M, N, K, dtype, *, R=None, P=None, Cpre=None, bias=None, bias_zs=0, batch=1, zdiv=1, act=ACT_NONE,
          flags=0, alpha=1.0, beta=0.0, dropout_p=0.0, seed=0, asum=None, on=None):
@@ -399,6 +429,7 @@ def gemm(A, B, C, M, N, K, dtype, *, R=None, P=None, Cpre=None, bias=None, bias_
     p.act, p.flags = act, flags
     p.alpha, p.beta, p.dropout_p, p.seed = alpha, beta, dropout_p, seed
     p.asum = ptr(asum)
+    p.gate = _gate or None
     if profiler.enabled:
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         e0.record(on)
@@ -411,14 +442,17 @@ def gemm(A, B, C, M, N, K, dtype, *, R=None, P=None, Cpre=None, bias=None, bias_
 
 
 def gemm_tn_group(problems, dtype, on=None):
-    """problems: [(A, B, C, M, N, K, flags, beta, asum)] weight-gradient GEMMs -> ONE launch without split-K (st5_gemm_tn_group;
+    """problems: [(A, B, C, M, N, K, flags, beta, asum[, gate])] weight-gradient GEMMs (gate: the layer gate's device address the problem
+    was queued under, per problem -- a group mixes the problems of two layers) -> ONE launch without split-K (st5_gemm_tn_group;
     the library falls back to one st5_gemm per problem when the group does not qualify).  The caller keeps the operands alive until
     the call returns (the launch is enqueued on the current stream by then).  on: torch.cuda.Stream to launch on instead of the
     current one (the caller orders it behind the producers: st5_stream_fork, and keeps the operands alive until the streams join)."""
     n = len(problems)
     arr = (GemmParams * n)()
     flops = 0.0
-    for p, (A, B, C, M, N, K, flags, beta, asum) in zip(arr, problems):
+    for p, prob in zip(arr, problems):
+        A, B, C, M, N, K, flags, beta, asum = prob[:9]
+        p.gate = (prob[9] if len(prob) > 9 else 0) or None
         p.A, p.B, p.C = A, B, C
         p.R = p.P = p.Cpre = _NULL_OP
         p.bias, p.bias_zs = None, 0

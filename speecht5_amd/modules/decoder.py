@@ -124,8 +124,10 @@ class TransformerDecoder(FairseqIncrementalDecoder):
             kva = (kv_all, idx * 2 * C, share) if kv_all is not None else None
             if keep_dev is not None and torch.is_grad_enabled() and Fn.LAYERDROP_GATE and layer.gate_ok():
                 # post-LN layer: the select rides on its last LayerNorm and its gradient on the layer's input (Fn.LayerDropGate)
-                gate, xg = Fn.layerdrop_gate(x, keep_dev[idx:idx + 1])
-                x, layer_attn = layer.forward_rows(xg, B, T, enc_rows, S, enc_pad, tgt_mask, causal, want, kv_all=kva, gate=gate)
+                # ... and, where every launch of the layer can carry it, the same flag makes a dropped layer's kernels exit
+                gate, xg = Fn.layerdrop_gate(x, keep_dev[idx:idx + 1], exit=layer.exit_ok(x.dtype, want, enc_rows is not None, kva is not None))
+                with Fn.layer_gate_scope(gate):
+                    x, layer_attn = layer.forward_rows(xg, B, T, enc_rows, S, enc_pad, tgt_mask, causal, want, kv_all=kva, gate=gate)
                 assert gate.used
             else:
                 y, layer_attn = layer.forward_rows(x, B, T, enc_rows, S, enc_pad, tgt_mask, causal, want, kv_all=kva)

@@ -133,8 +133,10 @@ class TransformerEncoder(FairseqEncoder):
                     pb = self.pos_emb.for_layer(pos_k) if pos_k is not None else None
                     if i != self.unb_enc_layer and not frozen and torch.is_grad_enabled() and Fn.LAYERDROP_GATE and layer.gate_ok():
                         # post-LN layer: the select rides on its last LayerNorm and its gradient on the layer's input (Fn.LayerDropGate)
-                        gate, xg = Fn.layerdrop_gate(x, keep_dev[i:i + 1])
-                        x = layer.forward_rows(xg, B, T, padding_mask=encoder_padding_mask, pos_bias=pb, gate=gate)
+                        # ... and, where every launch of the layer can carry it, the same flag makes a dropped layer's kernels exit
+                        gate, xg = Fn.layerdrop_gate(x, keep_dev[i:i + 1], exit=layer.exit_ok(x.dtype))
+                        with Fn.layer_gate_scope(gate):
+                            x = layer.forward_rows(xg, B, T, padding_mask=encoder_padding_mask, pos_bias=pb, gate=gate)
                         assert gate.used
                     else:
                         y = layer.forward_rows(x, B, T, padding_mask=encoder_padding_mask, pos_bias=pb)

@@ -44,6 +44,10 @@ class TransformerSentenceEncoderLayer(nn.Module):
         """A LayerDrop gate (functional.LayerDropGate) can ride on this layer: its last operation is a LayerNorm."""
         return not self.layer_norm_first
 
+    def exit_ok(self, dtype):
+        """Every launch of this (gate_ok) layer can carry the layer gate, so that a dropped layer's kernels exit (functional.layer_exit_ok)."""
+        return self.gate_ok() and Fn.layer_exit_ok(dtype, self.self_attn.head_dim)
+
     def forward_rows(self, x, B, T, padding_mask=None, pos_bias=None, gate=None):
         """x rows [B*T, C] -> rows.  Post-LN (:112-132) or pre-LN (:90-111).  gate: LayerDrop select folded into the last LayerNorm."""
         assert gate is None or self.gate_ok()
@@ -113,6 +117,13 @@ class TransformerDecoderLayer(nn.Module):
     def gate_ok(self):
         """A LayerDrop gate can ride on this layer: post-LN (the last operation is final_layer_norm) and nothing frozen."""
         return (not self.normalize_before) and self.freeze_decoder_updates <= self.num_updates
+
+    def exit_ok(self, dtype, need_attn, has_encoder, shared_kv):
+        """Every launch of this (gate_ok) layer can carry the layer gate (functional.layer_exit_ok): no attention probabilities wanted,
+        and the cross-attention, when there is one, reads the all-layer K|V projection."""
+        cross = self.encoder_attn is not None and has_encoder
+        return self.gate_ok() and Fn.layer_exit_ok(dtype, self.self_attn.head_dim, want_probs=bool(need_attn) and cross,
+                                                   shared_kv=shared_kv or not cross)
 
     def forward_rows(self, x, B, T, enc_rows, S, enc_padding_mask, self_padding_mask, causal, need_attn, kv_all=None, gate=None):
         """transformer_layer.py:262-404 without incremental state.  Returns (rows, cross-attn probs [B,H,T,S] or None).
