@@ -774,6 +774,33 @@ int st5_tts_step_tail_dev(const float* y, int64_t y_ld, int32_t B, int32_t r, in
 int st5_tts_pe_add_step(const void* x, int64_t x_ld, const float* table, int32_t table_rows, const float* alpha, const int32_t* step,
                         void* y, int64_t y_ld, int32_t B, int32_t C, int dtype, void* stream);
 
+/* ---- validation UER / WER of the ASR criterion (speech_to_text_loss.py:232-297), csrc/asr_metrics.hip ----
+ * All arrays on the device; rows are int32 [B, L] with int32 lengths [B] unless said otherwise.  Every length is clamped to its row
+ * inside the kernels; token VALUES are compared or range-checked, never trusted as indices.
+ * st5_ctc_greedy_rows: lprobs [T, B, V] fp32 (st5_ctc_loss_fwd's layout), input_lengths [B] int64.  Per frame t < clamp(len_b, 0, T)
+ *   the argmax over V by torch's CPU rule (lowest index among equal maxima; a NaN beats every number, the first NaN wins), then
+ *   unique_consecutive, then blanks dropped: frame t is kept iff best[t] != blank and (t == 0 or best[t] != best[t - 1]).
+ *   pred [B, T] (-1 behind pred_len[b]), pred_len [B]; best_ws [B, T] int32 workspace.
+ * st5_tokens_to_words: the sentence's bytes = concatenation of the table's byte strings of its tokens (table_offsets [V + 1] into
+ *   table_bytes [table_nbytes], no string longer than max_symbol_bytes), written to bytes [B, cap], cap = L * max_symbol_bytes;
+ *   a word is a maximal run of bytes other than 0x20: word_start / word_len [B, word_cap], word_cap = (cap + 1) / 2, n_words [B].
+ *   A token outside [0, V) contributes no bytes and sets err_flag[0] = 1 (the caller zeroes it).
+ * st5_word_ids: p_ids [B, p_word_cap], t_ids [B, t_word_cap] with id(predicted word) == id(target word) iff their bytes are equal
+ *   (lengths compared first), id(target word) == id(target word) iff their bytes are equal.
+ * st5_edit_distance_rows: dist[b] = unit-cost Levenshtein distance of a[b][:a_len[b]] and b[b][:b_len[b]]; anti-diagonals, three
+ *   rotating diagonals of min(La, Lb) + 1 ints in LDS.  min(La, Lb) > 4095 is refused (ST5_ERR_ARG, nothing launched). */
+int st5_ctc_greedy_rows(const float* lprobs, const int64_t* input_lengths, int32_t T, int32_t B, int32_t V, int32_t blank,
+                        int32_t* best_ws, int32_t* pred, int32_t* pred_len, void* stream);
+int st5_tokens_to_words(const int32_t* tokens, const int32_t* len, int32_t B, int32_t L, const int32_t* table_offsets,
+                        const uint8_t* table_bytes, int32_t V, int32_t table_nbytes, int32_t max_symbol_bytes, int32_t cap,
+                        int32_t word_cap, uint8_t* bytes, int32_t* word_start, int32_t* word_len, int32_t* n_words, int32_t* err_flag,
+                        void* stream);
+int st5_word_ids(const uint8_t* p_bytes, const int32_t* p_start, const int32_t* p_len, const int32_t* p_n, int32_t p_cap,
+                 int32_t p_word_cap, const uint8_t* t_bytes, const int32_t* t_start, const int32_t* t_len, const int32_t* t_n,
+                 int32_t t_cap, int32_t t_word_cap, int32_t B, int32_t* p_ids, int32_t* t_ids, void* stream);
+int st5_edit_distance_rows(const int32_t* a, const int32_t* a_len, int32_t La, const int32_t* b, const int32_t* b_len, int32_t Lb,
+                           int32_t B, int32_t* dist, void* stream);
+
 const char* st5_version(void);
 
 #ifdef __cplusplus

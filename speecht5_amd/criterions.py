@@ -298,7 +298,12 @@ def label_smoothed_nll_loss(lprobs, target, epsilon, ignore_index=None, reduce=T
 
 
 class SpeechtoTextLoss(nn.Module):
-    """speech_to_text_loss.py:113-337 (CE + CTC; the WER/KenLM validation extras are not part of the hot path)."""
+    """speech_to_text_loss.py:113-337: CE + CTC, and in eval mode with ctc_weight > 0 the validation error counts of :232-297 --
+    c_errors / c_total (units) and w_errors / wv_errors / w_total (words of `cfg.post_process`, default "sentencepiece") of the greedy
+    CTC decoding against `sample["target_label"]` (else `sample["target"]`) without pad and eos, counted on the device
+    (asr_metrics.py, csrc/asr_metrics.hip) and summed by `SpeechT5Criterion.reduce_metrics` into uer / wer / raw_wer.  Under
+    `sync_logging=False` they stay int64 device scalars like the other entries.  There is no KenLM / lexicon decoder: w_errors equals
+    wv_errors, and a set `wer_kenlm_model` is ignored with a one-time warning."""
 
     def __init__(self, cfg, task, sentence_avg=True, label_smoothing=0.1, ignore_prefix_size=0, report_accuracy=False,
                  ce_weight=1.0, ctc_weight=0.0, sync_logging=True):
@@ -314,6 +319,13 @@ class SpeechtoTextLoss(nn.Module):
         self.zero_infinity = getattr(cfg, "zero_infinity", True)
         self.report_accuracy = report_accuracy
         self.sync_logging = sync_logging
+        self.post_process = getattr(cfg, "post_process", "sentencepiece")
+        self._byte_tables = {}     # asr_metrics.byte_table's cache: the dictionary's byte table on the device, built once
+        self.metric_flag = None    # int32 [1] on the device: 1 once a validation step met a token id outside the dictionary
+        if getattr(cfg, "wer_kenlm_model", None) is not None or getattr(cfg, "wer_args", None) is not None:
+            from . import asr_metrics
+            asr_metrics._warn_once("kenlm", "wer_kenlm_model / wer_args: there is no KenLM / lexicon decoder here; w_errors is counted "
+                                   "on the greedy CTC decoding (= wv_errors)")
 
     def forward(self, model, sample, reduce=True):
         s = self.sync_logging
@@ -332,7 +344,8 @@ class SpeechtoTextLoss(nn.Module):
                 loss_ce, nll = label_smoothed_nll_loss(lprobs.view(-1, lprobs.size(-1)), sample["target"].view(-1), self.eps,
                                                        ignore_index=self.padding_idx, reduce=reduce)
         if self.ctc_weight > 0:
-            loss_ctc = self.compute_loss_ctc(model, net_output, sample)
+            ctc_inputs = self._ctc_inputs(model, net_output)
+            loss_ctc = self.compute_loss_ctc(model, net_output, sample, ctc_inputs)
         if self.ce_weight > 0 and self.ctc_weight > 0:
             loss = self.ce_weight * loss_ce + self.ctc_weight * loss_ctc
         else:
@@ -346,6 +359,17 @@ class SpeechtoTextLoss(nn.Module):
             n_correct, total = self.compute_accuracy(model, net_output_decoder, sample)
             log["n_correct"] = _item(n_correct, s)
             log["total"] = _item(total, s)
+        if self.ctc_weight > 0 and not model.training:
+            from . import asr_metrics
+            with torch.no_grad():
+                counts, self.metric_flag = asr_metrics.count_errors(
+                    ctc_inputs[0], ctc_inputs[1], sample["target_label"] if "target_label" in sample else sample["target"],
+                    self.task.target_dictionary, self.blank_idx, self.post_process, self._byte_tables)
+            for k in asr_metrics.KEYS:
+                log[k] = _item(counts[k], s)
+            if s and int(self.metric_flag):
+                asr_metrics._warn_once("ids", "validation word counts: a token id outside the target dictionary was met (a CTC class "
+                                       "or a target beyond len(dictionary)); it contributes no bytes to the words")
         return loss, sample_size, log
 
     def compute_accuracy(self, model, net_output, sample):
@@ -360,12 +384,17 @@ class SpeechtoTextLoss(nn.Module):
             total = mask.sum()
         return n_correct, total
 
-    def compute_loss_ctc(self, model, net_output, sample):
+    def _ctc_inputs(self, model, net_output):
+        """The CTC posterior [T, B, V] and the sentences' frame counts [B]: read by the loss and by the validation counts."""
         lprobs = model.get_normalized_probs_for_ctc(net_output, log_probs=True).contiguous()
         if net_output["encoder_padding_mask"] is not None:
             input_lengths = (~net_output["encoder_padding_mask"][0]).long().sum(-1)
         else:
             input_lengths = lprobs.new_full((lprobs.size(1),), lprobs.size(0), dtype=torch.long)
+        return lprobs, input_lengths
+
+    def compute_loss_ctc(self, model, net_output, sample, ctc_inputs=None):
+        lprobs, input_lengths = ctc_inputs if ctc_inputs is not None else self._ctc_inputs(model, net_output)
         pad_mask = (sample["target"] != self.pad_idx) & (sample["target"] != self.eos_idx)
         targets_flat = sample["target"].masked_select(pad_mask)
         target_lengths = sample["target_lengths"] if "target_lengths" in sample else pad_mask.sum(-1)

@@ -1560,6 +1560,97 @@ def guided_attention_loss(att, ilens, olens, sigma, alpha):
 
 
 # -------------------------------------------------------------------------------------------------
+# validation UER / WER (csrc/asr_metrics.hip): greedy CTC decoding, words, word ids, edit distance
+# -------------------------------------------------------------------------------------------------
+EDIT_DISTANCE_MAX_SHORT = 4095   # (AM_ED_MAX_SHORT of csrc/asr_metrics_index.h)
+
+
+def _i32_rows(x, lens, what):
+    if not (x.is_cuda and x.dim() == 2 and x.dtype == torch.int32):
+        raise TypeError(f"{what}: expected int32 rows [B, L] on the GPU, got {x.dtype} {tuple(x.shape)} on {x.device}")
+    if not (lens.is_cuda and lens.dtype == torch.int32 and lens.shape == (x.size(0),)):
+        raise TypeError(f"{what}: expected int32 lengths [{x.size(0)}] on the GPU, got {lens.dtype} {tuple(lens.shape)} on {lens.device}")
+    return x.contiguous(), lens.contiguous()
+
+
+def ctc_greedy_rows(lprobs, input_lengths, blank):
+    """Greedy CTC decoding of lprobs [T, B, V] fp32 (the layout ctc_loss_sum takes): per frame t < clamp(input_lengths[b], 0, T) the
+    argmax over V by torch's CPU rule (lowest index among equal maxima, the first NaN beats every number), unique_consecutive, blanks
+    dropped.  -> pred int32 [B, T] (-1 behind the length), pred_len int32 [B]."""
+    if not (lprobs.is_cuda and lprobs.dtype == torch.float32 and lprobs.dim() == 3):
+        raise TypeError(f"ctc_greedy_rows: expected fp32 [T, B, V] on the GPU, got {lprobs.dtype} {tuple(lprobs.shape)} on {lprobs.device}")
+    T, B, V = lprobs.shape
+    if V < 1:
+        raise ValueError("ctc_greedy_rows: V must be at least 1")
+    lprobs = lprobs.contiguous()
+    dev = lprobs.device
+    in_len = input_lengths.to(device=dev, dtype=torch.int64).contiguous()
+    if in_len.shape != (B,):
+        raise ValueError(f"ctc_greedy_rows: input_lengths {tuple(in_len.shape)} for B = {B}")
+    best = torch.empty(B, T, dtype=torch.int32, device=dev)
+    pred = torch.empty(B, T, dtype=torch.int32, device=dev)
+    pred_len = torch.empty(B, dtype=torch.int32, device=dev)
+    hip.check(hip.lib().st5_ctc_greedy_rows(lprobs.data_ptr(), in_len.data_ptr(), T, B, V, int(blank), best.data_ptr(), pred.data_ptr(),
+                                            pred_len.data_ptr(), hip.stream()), "st5_ctc_greedy_rows")
+    return pred, pred_len
+
+
+def tokens_to_words(tokens, lens, table_offsets, table_bytes, max_symbol_bytes, err_flag=None):
+    """tokens int32 [B, L] / lens int32 [B] -> the sentences' bytes through the per-symbol byte table (table_offsets int32 [V + 1] into
+    table_bytes uint8) and their words (maximal runs of bytes other than 0x20).  Returns a namespace: bytes uint8 [B, cap] with
+    cap = L * max_symbol_bytes, start / len int32 [B, word_cap], n int32 [B], err int32 [1] (1 once a token was outside [0, V))."""
+    tokens, lens = _i32_rows(tokens, lens, "tokens_to_words")
+    B, L = tokens.shape
+    dev = tokens.device
+    V = table_offsets.numel() - 1
+    if V < 0 or table_offsets.dtype != torch.int32 or table_bytes.dtype != torch.uint8 or table_offsets.device != dev or table_bytes.device != dev:
+        raise TypeError("tokens_to_words: the table is int32 offsets [V + 1] and uint8 bytes on the tokens' device")
+    msb = int(max_symbol_bytes)
+    cap = L * msb
+    if msb < 0 or cap >= 2 ** 31:
+        raise ValueError(f"tokens_to_words: L * max_symbol_bytes = {cap} does not fit the int32 offsets")
+    wcap = (cap + 1) // 2
+    out = SimpleNamespace(bytes=torch.empty(B, cap, dtype=torch.uint8, device=dev), start=torch.empty(B, wcap, dtype=torch.int32, device=dev),
+                          len=torch.empty(B, wcap, dtype=torch.int32, device=dev), n=torch.empty(B, dtype=torch.int32, device=dev),
+                          err=err_flag if err_flag is not None else torch.zeros(1, dtype=torch.int32, device=dev), cap=cap, word_cap=wcap)
+    hip.check(hip.lib().st5_tokens_to_words(tokens.data_ptr(), lens.data_ptr(), B, L, table_offsets.data_ptr(), table_bytes.data_ptr(), V,
+                                            table_bytes.numel(), msb, cap, wcap, out.bytes.data_ptr(), out.start.data_ptr(),
+                                            out.len.data_ptr(), out.n.data_ptr(), out.err.data_ptr(), hip.stream()), "st5_tokens_to_words")
+    return out
+
+
+def word_ids(pred_words, target_words):
+    """Int32 ids of the words of two tokens_to_words results over the same sentences: a predicted and a target word share an id iff
+    their bytes are equal, two target words share an id iff their bytes are equal.  -> (p_ids [B, p_word_cap], t_ids [B, t_word_cap])."""
+    P, Tg = pred_words, target_words
+    B = P.n.numel()
+    if Tg.n.numel() != B:
+        raise ValueError("word_ids: the two sides hold different numbers of sentences")
+    p_ids = torch.empty(B, P.word_cap, dtype=torch.int32, device=P.n.device)
+    t_ids = torch.empty(B, Tg.word_cap, dtype=torch.int32, device=P.n.device)
+    hip.check(hip.lib().st5_word_ids(P.bytes.data_ptr(), P.start.data_ptr(), P.len.data_ptr(), P.n.data_ptr(), P.cap, P.word_cap,
+                                     Tg.bytes.data_ptr(), Tg.start.data_ptr(), Tg.len.data_ptr(), Tg.n.data_ptr(), Tg.cap, Tg.word_cap, B,
+                                     p_ids.data_ptr(), t_ids.data_ptr(), hip.stream()), "st5_word_ids")
+    return p_ids, t_ids
+
+
+def edit_distance_rows(a, a_len, b, b_len):
+    """Unit-cost Levenshtein distance (editdistance.eval) of a[i][:a_len[i]] and b[i][:b_len[i]], int32 rows on the GPU -> int32 [B].
+    Lengths are clamped to the rows.  The shorter side's row may hold at most 4095 entries (ValueError, nothing is launched)."""
+    a, a_len = _i32_rows(a, a_len, "edit_distance_rows")
+    b, b_len = _i32_rows(b, b_len, "edit_distance_rows")
+    if a.size(0) != b.size(0) or a.device != b.device:
+        raise ValueError("edit_distance_rows: the two sides hold different numbers of rows or live on different devices")
+    if min(a.size(1), b.size(1)) > EDIT_DISTANCE_MAX_SHORT:
+        raise ValueError(f"edit_distance_rows: min(La, Lb) = {min(a.size(1), b.size(1))} > {EDIT_DISTANCE_MAX_SHORT} "
+                         "(three diagonals of the shorter side live in LDS)")
+    dist = torch.empty(a.size(0), dtype=torch.int32, device=a.device)
+    hip.check(hip.lib().st5_edit_distance_rows(a.data_ptr(), a_len.data_ptr(), a.size(1), b.data_ptr(), b_len.data_ptr(), b.size(1),
+                                               a.size(0), dist.data_ptr(), hip.stream()), "st5_edit_distance_rows")
+    return dist
+
+
+# -------------------------------------------------------------------------------------------------
 # LayerNorm
 # -------------------------------------------------------------------------------------------------
 class LayerNormFunction(torch.autograd.Function):

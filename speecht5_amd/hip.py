@@ -255,6 +255,12 @@ _SIGS = {
                                       c_int64, c_int64, c_int32, c_int, c_void_p]),
     "st5_batchnorm_act_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float,
                                       c_uint64, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_int32, c_int, c_void_p]),
+    "st5_ctc_greedy_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "st5_tokens_to_words": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
+                                    c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "st5_word_ids": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                             c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
+    "st5_edit_distance_rows": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
     "st5_version": (c_char_p, []),
 }
 
