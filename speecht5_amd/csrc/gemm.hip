@@ -356,6 +356,32 @@ __device__ __forceinline__ void epilogue_rows(const EpiArgs& ea, const float* st
 }
 
 
+// A lane's 8 consecutive elements of a side operand as they come from memory (16 B of bf16, 32 B of fp32): held raw between the
+// early load and the row pass that uses them (epilogue_fast, FEAT >= 0), converted at the use exactly as load8f converts.
+template <typename U> struct Raw8;
+template <> struct Raw8<float> {
+  f32x4 a, b;
+  __device__ __forceinline__ void load(const float* p) {
+    a = *reinterpret_cast<const f32x4*>(p);
+    b = *reinterpret_cast<const f32x4*>(p + 4);
+  }
+  __device__ __forceinline__ void to_f(float (&v)[8]) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) { v[i] = a[i]; v[4 + i] = b[i]; }
+  }
+};
+template <> struct Raw8<bf16_t> {
+  u32x4 a;
+  __device__ __forceinline__ void load(const bf16_t* p) { a = *reinterpret_cast<const u32x4*>(p); }
+  __device__ __forceinline__ void to_f(float (&v)[8]) const {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      v[2 * i] = __uint_as_float(a[i] << 16);
+      v[2 * i + 1] = __uint_as_float(a[i] & 0xffff0000u);
+    }
+  }
+};
+
 // Fast epilogue of a wave's 64x64 tile for the common layout (every C-class operand 16-byte
 // aligned, N % 8 == 0 so a lane's 8 columns are all valid or all out of range).  Both 32-row halves are staged through the
 // wave-private LDS slab; the per-lane constants (bias, column offsets) are loaded once, the uniform feature tests are
@@ -417,13 +443,60 @@ __device__ __forceinline__ void epilogue_fast(const EpiArgs& ea, float* stage, c
   unsigned long long ctr0 = drop ? ea.ctr_base + (unsigned long long)row0 * (unsigned long long)ea.N + (unsigned long long)gn : 0ull;
   // (opaque to the optimiser: hipcc otherwise re-associates co0 + rr * ld back into (row0 + rr) * ld -- one register less, the multiplies back)
   asm volatile("" : "+v"(co0), "+v"(ro0), "+v"(po0), "+v"(qo0), "+v"(ctr0));
+  // C-class operand offsets of the wave tile's row rr (+ rsub per lane), global row gm
+  auto row_offs = [&](const int rr, const int gm, long long& c_off, long long& r_off, long long& p_off, long long& q_off) {
+    if (split) {
+      // row -> (block q, row rm inside the block) when the C-class operands are split every `rpb` rows
+      // (convolution layouts: per-utterance halo rows); every operand has its own row / block stride
+      const long long q = gm / ea.rpb, rm = gm - q * ea.rpb;
+      c_off = q * ea.c_bs + rm * ea.c_ld; r_off = q * ea.r_bs + rm * ea.r_ld;
+      p_off = q * ea.p_bs + rm * ea.p_ld; q_off = q * ea.q_bs + rm * ea.q_ld;
+    } else {
+      c_off = co0 + (long long)rr * ea.c_ld; r_off = ro0 + (long long)rr * ea.r_ld;
+      p_off = po0 + (long long)rr * ea.p_ld; q_off = qo0 + (long long)rr * ea.q_ld;
+    }
+  };
+  // Side operands ahead of the tile's stores (feature-specialised form only).  Loads and stores share one counter on this target
+  // and return in order, so a row pass that loads its R / P / old C row, uses it and stores the row makes the NEXT row's wait for its
+  // operand also a wait for this row's store to be acknowledged: eight dependent round trips per wave tile with two waves per SIMD
+  // to cover them.  Every address is known here, so all rows of the tile a lane owns are requested before the first LDS staging
+  // write and held raw (4 VGPRs per bf16 row, 8 per fp32 row: 32 / 64 per operand); the row passes consume registers, are fully
+  // unrolled (static register indices) and wait for nothing that a store precedes.  Predicates and addresses are the row passes'
+  // own; an operand aliasing C (F_BETA reads C itself) is read and written element-wise by the same lane, the read first.
+  // The run-time form keeps the row-by-row order: it is the fallback and the reference of tests/test_gemm_epilogue_loads_gpu.py.
+  // (not the F_Q8 twins: their row passes carry the MX quantisation, eight unrolled copies took gemm_nt8p_mx8_kernel<F_Q8 | F_DACT>
+  //  from 28.8 to 55.4 KB of a 64 KB instruction cache that two CUs share, and the benched bf16 update does not run them)
+  constexpr bool EARLY = !RT && (FEAT & (F_RES | F_DACT | F_BETA)) != 0 && (FEAT & F_Q8) == 0;
+  constexpr int NROWS = HALVES * 4;
+  Raw8<OUT> res_raw[EARLY && (FEAT & F_RES) != 0 ? NROWS : 1], old_raw[EARLY && (FEAT & F_BETA) != 0 ? NROWS : 1];
+  Raw8<T> pre_raw[EARLY && (FEAT & F_DACT) != 0 ? NROWS : 1];
+  if constexpr (EARLY) {
+#pragma unroll
+    for (int j = 0; j < NROWS; ++j) {
+      const int rr = j * 8;
+      const int gm = mbase + rr + rsub;
+      if (gm < ea.M && col_ok) {
+        long long c_off, r_off, p_off, q_off;
+        row_offs(rr, gm, c_off, r_off, p_off, q_off);
+        if constexpr ((FEAT & F_RES) != 0) res_raw[j].load(Rb + r_off);
+        if constexpr ((FEAT & F_DACT) != 0) pre_raw[j].load(Pb + p_off);
+        if constexpr ((FEAT & F_BETA) != 0) old_raw[j].load(Cb + c_off);
+      }
+    }
+  }
 #pragma unroll
   for (int h = 0; h < HALVES; ++h) {
     if (h == 0) stage_write(stage, acc00, acc01, lane);
     else stage_write(stage, acc10, acc11, lane);
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll 1
-    for (int pp = 0; pp < 2; ++pp) {   // two row passes at a time (keeps the register footprint of the epilogue small)
+    // One wait for all early loads, ahead of the first store (vmcnt(0), the other counters left alone; the builtin, not inline
+    // assembly: the compiler's wait insertion has to see it).  The row passes sit in predicated blocks, and without this the
+    // compiler, unable to count what the blocks in between issued, puts a vmcnt(0) in front of every row's first use -- behind the
+    // previous row's store again.  The loads were issued a whole LDS staging pass ago and return together.
+    if constexpr (EARLY) { if (h == 0) __builtin_amdgcn_s_waitcnt(0x0F70); }
+    // two row passes at a time (keeps the register footprint of the epilogue small); rolled unless the passes index early-loaded rows
+#pragma unroll EARLY ? 2 : 1
+    for (int pp = 0; pp < 2; ++pp) {
       float v[2][8];
 #pragma unroll
       for (int k = 0; k < 2; ++k) {
@@ -439,20 +512,18 @@ __device__ __forceinline__ void epilogue_fast(const EpiArgs& ea, float* stage, c
         const int gm = mbase + rr + rsub;
         if (gm < ea.M && col_ok) {
           long long c_off, r_off, p_off, q_off;
-          if (split) {
-            // row -> (block q, row rm inside the block) when the C-class operands are split every `rpb` rows
-            // (convolution layouts: per-utterance halo rows); every operand has its own row / block stride
-            const long long q = gm / ea.rpb, rm = gm - q * ea.rpb;
-            c_off = q * ea.c_bs + rm * ea.c_ld; r_off = q * ea.r_bs + rm * ea.r_ld;
-            p_off = q * ea.p_bs + rm * ea.p_ld; q_off = q * ea.q_bs + rm * ea.q_ld;
-          } else {
-            c_off = co0 + (long long)rr * ea.c_ld; r_off = ro0 + (long long)rr * ea.r_ld;
-            p_off = po0 + (long long)rr * ea.p_ld; q_off = qo0 + (long long)rr * ea.q_ld;
-          }
+          row_offs(rr, gm, c_off, r_off, p_off, q_off);
           float rv[8], pv[8], ov[8];
-          if (has_res) load8f<OUT>(Rb + r_off, rv);
-          if (dact) load8f<T>(Pb + p_off, pv);
-          if (has_beta) load8f<OUT>(Cb + c_off, ov);
+          if constexpr (EARLY) {
+            const int j = h * 4 + pp * 2 + k;
+            if constexpr ((FEAT & F_RES) != 0) res_raw[j].to_f(rv);
+            if constexpr ((FEAT & F_DACT) != 0) pre_raw[j].to_f(pv);
+            if constexpr ((FEAT & F_BETA) != 0) old_raw[j].to_f(ov);
+          } else {
+            if (has_res) load8f<OUT>(Rb + r_off, rv);
+            if (dact) load8f<T>(Pb + p_off, pv);
+            if (has_beta) load8f<OUT>(Cb + c_off, ov);
+          }
           float x[8];
 #pragma unroll
           for (int e = 0; e < 8; ++e) x[e] = fmaf(v[k][e], ea.alpha, bias8[e]);
