@@ -46,6 +46,13 @@ __device__ __forceinline__ int lds_off(int row, int chunk) {
   return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
 }
 
+// XCD-aware renumbering of the nwg blocks of a grid (block b runs on XCD b % 8): every XCD gets a contiguous range of the new numbers,
+// so that neighbouring tiles (sharing an A row panel) hit the same L2.  Bijective for any nwg.
+__device__ __forceinline__ int xcd_remap(const int bid, const int nwg) {
+  const int xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
+  return (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
+}
+
 // Linear block number (after the XCD remap: every XCD walks a contiguous range of them, ~32 x blocks-per-CU at a time) -> tile
 // coordinates.  Row-major order makes the blocks that run together on an XCD cover few rows and ALL columns of tiles (64 blocks on
 // 24 columns: 3 A panels + 24 B panels stream through that XCD's L2 at once); walking column groups GEMM_GROUP_N wide instead (the
@@ -602,11 +609,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_kernel(const st5_gemm_params
   const int tiles_n = (p.N + BN - 1) / BN;
   // XCD-aware remap (block b runs on XCD b % 8): give each XCD a contiguous range of tiles so that
   // neighbouring tiles (sharing an A row panel) hit the same L2.  Bijective for any grid size.
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
@@ -764,6 +767,37 @@ struct DeferState {
   int pending_blocks;
   float* arena;              // slab arena for deferred reductions (grown between flushes only)
   size_t arena_bytes, arena_used;
+
+  // folds everything queued into its outputs with one launch on the state's stream
+  int flush() {
+    if (pending.n == 0) return ST5_OK;
+    hipLaunchKernelGGL(splitk_multi_reduce_kernel, dim3((unsigned)pending_blocks), dim3(256), 0, stream, pending);
+    pending.n = 0; pending_blocks = 0; arena_used = 0;
+    HIP_CHECK_LAUNCH();
+    return ST5_OK;
+  }
+  // slab space for one deferred GEMM, or nullptr when the arena is too full for it
+  float* take(size_t bytes) {
+    bytes = (bytes + 255) & ~(size_t)255;
+    if (arena_used + bytes > arena_bytes) return nullptr;
+    float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(arena) + arena_used);
+    arena_used += bytes;
+    return p;
+  }
+  // the same; a full arena is emptied by a flush first and grown when it is too small altogether.  nullptr: the flush or the allocation failed
+  float* take_or_grow(size_t bytes) {
+    float* slabs = take(bytes);
+    if (slabs) return slabs;
+    if (flush() != ST5_OK) return nullptr;
+    if (bytes > arena_bytes || arena_bytes == 0) {
+      if (arena) (void)hipFree(arena);   // synchronises with in-flight users
+      size_t want = arena_bytes ? arena_bytes * 2 : (size_t(1) << 30);
+      while (want < bytes * 4) want *= 2;
+      if (st5_dev_malloc(&arena, want) != hipSuccess) { arena = nullptr; arena_bytes = 0; return nullptr; }
+      arena_bytes = want;
+    }
+    return take(bytes);
+  }
 };
 constexpr int DEFER_STREAMS = 32;
 DeferState g_dstates[DEFER_STREAMS] = {};
@@ -786,27 +820,9 @@ DeferState* defer_state(hipStream_t s, bool create) {
   d->stream = s; d->pending.n = 0; d->pending_blocks = 0; d->arena_used = 0;
   return d;
 }
-#define g_pending (ds->pending)
-#define g_pending_blocks (ds->pending_blocks)
-#define g_arena (ds->arena)
-#define g_arena_bytes (ds->arena_bytes)
-#define g_arena_used (ds->arena_used)
-
-int flush_state(DeferState* ds) {
-  if (!ds || g_pending.n == 0) return ST5_OK;
-  hipLaunchKernelGGL(splitk_multi_reduce_kernel, dim3((unsigned)g_pending_blocks), dim3(256), 0, ds->stream, g_pending);
-  g_pending.n = 0; g_pending_blocks = 0; g_arena_used = 0;
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
-int flush_pending(hipStream_t s) { return flush_state(defer_state(s, false)); }
-// slab space for one deferred GEMM, or nullptr when the arena must grow (caller flushes, grows, retries)
-float* arena_take(DeferState* ds, size_t bytes) {
-  bytes = (bytes + 255) & ~(size_t)255;
-  if (g_arena_used + bytes > g_arena_bytes) return nullptr;
-  float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(g_arena) + g_arena_used);
-  g_arena_used += bytes;
-  return p;
+int flush_pending(hipStream_t s) {
+  DeferState* ds = defer_state(s, false);
+  return ds ? ds->flush() : (int)ST5_OK;
 }
 
 // split-K slab workspace, one per stream (the weight-gradient stream runs split-K GEMMs beside the main stream's)
@@ -855,6 +871,161 @@ int launch(const st5_gemm_params& p, int c_vec_ok, int nsplit, hipStream_t s) {
 }
 
 
+// ------------------------------------------------------------------------------------------------------
+// Knobs: the A/B switches of the launch choices below, each with its setter (C ABI: include/speecht5_hip.h) and the measurements behind
+// its default.  Process-wide; the tests and bench.py's environment hooks set them between launches.
+// ------------------------------------------------------------------------------------------------------
+bool g_use_glds = true;      // the LDS-DMA kernels (NT and TN fast paths) at all
+int g_splitk_target = 384;   // blocks a split-K weight-gradient GEMM aims for (st5_gemm_set_splitk_target)
+int g_nt_tile = 0;   // 0 = choose per problem, 1 = always 128^2, 2 = always 256^2 (A/B switch, st5_gemm_set_nt_tile); 3 / 4 = always the phased
+                     // 256^2 kernel with / without the half-phase stagger of the two m-halves, 5 = always the 64 x 128 kernel (bf16)
+// Ring depth of the 128^2 NT kernel (template parameter NBUF).  2 stages (64 KB LDS) let two blocks share a CU and cover each
+// other's LDS-DMA landing latency (~1 us per k-step against 0.25 us of MFMAs): the right shape for grids of several blocks
+// per CU.  A grid of <= 256 blocks has the CU to itself; there a deeper ring (loads two or three k-steps ahead) helps a little:
+// measured on the pre-training update with the micro-batches in turn 48.24 -> 47.33 ms (4 stages), 47.41 (3 stages); deep rings
+// for EVERY grid were 10-25 % slower (round 1).  With the two micro-batches side by side (ddp.accumulate_overlapped) the
+// other stream's blocks are the latency cover and 128 KB blocks keep them off the CU: 37.70 -> 38.27 ms, so that mode turns
+// the deep ring off (st5_gemm_set_deep_ring(0, 2)).
+int g_deep_blocks = 256, g_deep_nbuf = 4;
+int g_nt_slots5 = 1;   // grids of more than g_deep_blocks blocks on five operand slots (80 KB, 2.5 k-steps of loads in flight) instead of two
+                       // stages (64 KB); st5_gemm_set_nt_slots.  Per shape the difference is inside the noise (-4 % .. +3 %,
+                       // profiles/r4_gemm_nt_slots.txt); on the whole update it was -0.4 .. -0.9 % in three same-box pairs on two boxes
+                       // (profiles/r4_knob_ab.txt), so it is the default.  Results are bit-identical either way.
+// Which NT launches take the half-height tiles: bf16, and at most g_m64_max_tiles tiles of 128^2 (st5_gemm_set_m64_max_tiles; 0 = never)
+int g_m64_max_tiles = 0;      // (default: never -- every isolated gain below was a LOSS inside the update, see DESIGN.md round 6)
+// (A/B knob, round 6, st5_gemm_set_nt_longk: problems of at least `g_nt_longk_tiles` tiles of 256^2 with a reduction of at least
+//  `g_nt_longk_nk` k-tiles also take the phased kernel (nt256_pays) -- the N = 768, K = 2304 / 3072 shapes at 8192 rows are 96 tiles: one
+//  block on 96 CUs for 36-48 k-tiles instead of 384 tiles of 128^2 on every CU.  0 = off, the default.)
+int g_nt_longk_tiles = 0, g_nt_longk_nk = 36;
+int g_tn8p = 0;   // st5_gemm_set_tn_phased: 0 (default) = always the 128^2 kernel; 1 / 2 = eligible weight-gradient GEMMs on the phased 256^2 kernel (staggered / not).
+                  // Measured (profiles/r4_gemm_tn_phased.txt): the phased kernel wins only on very long reductions over few tiles (512 x 1536 x 128k:
+                  // 335 vs 343 us); on the transformer weight gradients its 256^2 tiles need 2x the split-K slabs and lose 20-35 %.
+int g_tn_group_tile = 0;   // st5_gemm_set_tn_group_tile: 0 = per problem (phased 256^2 when M, N are multiples of 256 and K >= 512), 1 = 128^2 always
+int g_mx8_tile = 0;   // 0 = choose per problem, 1 = always 128^2, 2 = always the phased 256^2 kernel (st5_gemm_set_mx8_tile)
+int g_mx8_heavy_nk = 16;   // k-tiles an epilogue-heavy fp8 GEMM needs before it takes the phased 256^2 kernel (mx8_256_pays has the measurement)
+
+}  // namespace
+/* A/B switch for the LDS-DMA NT kernel (tools/bench_kernels.py uses it for within-process comparisons). */
+extern "C" int st5_gemm_set_glds(int enabled) { g_use_glds = enabled != 0; return ST5_OK; }
+/* Block count the split-K choice of the fp32-output (weight-gradient) GEMMs aims for (default 384 = 1.5 per CU). */
+extern "C" int st5_gemm_set_splitk_target(int blocks) { if (blocks < 1 || blocks > 4096) return ST5_ERR_ARG; g_splitk_target = blocks; return ST5_OK; }
+/* NT block tile: 0 = per-problem choice (default), 1 = 128x128 always, 2 = 256x256 always, 3 / 4 = phased 256x256 always (staggered / not),
+ * 5 = 64x128 always (A/B measurements). */
+extern "C" int st5_gemm_set_nt_tile(int mode) { if (mode < 0 || mode > 5) return ST5_ERR_ARG; g_nt_tile = mode; return ST5_OK; }
+/* 128^2 NT kernel, grids of more than one block per CU: 5 = ring of five 16 KB operand slots (default), 4 = two whole stages. */
+extern "C" int st5_gemm_set_nt_slots(int slots) {
+  if (slots != 4 && slots != 5) return ST5_ERR_ARG;
+  g_nt_slots5 = slots == 5; return ST5_OK;
+}
+/* 128^2 NT kernel: grids of at most `max_blocks` blocks run with an `nbuf`-stage operand ring (2 = off, 3, 4). */
+extern "C" int st5_gemm_set_deep_ring(int max_blocks, int nbuf) {
+  if (max_blocks < 0 || nbuf < 2 || nbuf > 4) return ST5_ERR_ARG;
+  g_deep_blocks = max_blocks; g_deep_nbuf = nbuf; return ST5_OK;
+}
+extern "C" int st5_gemm_set_m64_max_tiles(int tiles) { if (tiles < 0) return ST5_ERR_ARG; g_m64_max_tiles = tiles; return ST5_OK; }
+extern "C" int st5_gemm_set_nt_longk(int tiles, int nk) { if (tiles < 0 || nk < 1) return ST5_ERR_ARG; g_nt_longk_tiles = tiles; g_nt_longk_nk = nk; return ST5_OK; }
+/* Weight-gradient (TN) GEMMs without row split / segments: 0 (default) = always the 128^2 LDS-DMA kernel; 1 = phased 256^2 kernel,
+ * 2 = the same without the stagger of the two m-halves (A/B measurements; the header documents the same default). */
+extern "C" int st5_gemm_set_tn_phased(int mode) { if (mode < 0 || mode > 2) return ST5_ERR_ARG; g_tn8p = mode; return ST5_OK; }
+/* Block tile of the grouped weight-gradient launch: 0 (default) = per problem -- the phased 256x256 kernel when M and N are multiples of
+ * 256 and K >= 512 (every Linear of the transformer), else 128x128; 1 = 128x128 always (A/B measurements, tests). */
+extern "C" int st5_gemm_set_tn_group_tile(int mode) { if (mode < 0 || mode > 1) return ST5_ERR_ARG; g_tn_group_tile = mode; return ST5_OK; }
+/* MX-fp8 NT block tile: 0 = per-problem choice (default), 1 = 128x128 always, 2 = phased 256x256 always (A/B measurements, tests). */
+extern "C" int st5_gemm_set_mx8_tile(int mode) { if (mode < 0 || mode > 2) return ST5_ERR_ARG; g_mx8_tile = mode; return ST5_OK; }
+/* (A/B) k-tiles of 128 an epilogue-heavy fp8 GEMM needs before the per-problem choice takes the phased 256x256 kernel; default 16, 0 = always. */
+extern "C" int st5_gemm_set_mx8_heavy_nk(int nk) { if (nk < 0) return ST5_ERR_ARG; g_mx8_heavy_nk = nk; return ST5_OK; }
+namespace {
+
+// ------------------------------------------------------------------------------------------------------
+// What the launchers and the entry points share.
+// ------------------------------------------------------------------------------------------------------
+bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
+
+// What every entry point does with a problem first: sizes and operands present, batch / zdiv defaults.  ST5_OK or ST5_ERR_ARG.
+int normalise_and_check(st5_gemm_params& p) {
+  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return ST5_ERR_ARG;
+  if (!p.A.ptr || !p.B.ptr || !p.C.ptr) return ST5_ERR_ARG;
+  if (p.batch <= 0) p.batch = 1;
+  if (p.zdiv <= 0) p.zdiv = 1;
+  if ((p.flags & ST5_GEMM_DACT) && !p.P.ptr) return ST5_ERR_ARG;
+  return ST5_OK;
+}
+// The kernels' c_vec_ok: every C-class operand that is present (C, R, P, Cpre) is 16-byte aligned with strides that are multiples of 8
+// elements, so the epilogue may read and write it as 8-element vectors.
+// batched = false: the entry point takes one batch only and does not look at the operands' batch strides (st5_gemm_mxfp8).
+int c_class_vec_ok(const st5_gemm_params& p, const bool batched) {
+  auto ok = [&](const st5_operand& o) {
+    if (!o.ptr) return true;
+    if (batched && (o.zs0 % 8 || o.zs1 % 8)) return false;
+    return aligned(o.ptr, 16) && o.ld % 8 == 0 && o.bstride % 8 == 0;
+  };
+  return ok(p.C) && ok(p.R) && ok(p.P) && ok(p.Cpre);
+}
+
+// Launch of a kernel whose dynamic LDS may exceed 64 KB: the limit is raised once per kernel (this template is instantiated per
+// kernel, and so is its flag), not on every launch.
+template <auto KERNEL, typename... Args>
+int launch_lds(const dim3 grid, const dim3 block, const size_t lds_bytes, hipStream_t s, const Args&... args) {
+  static bool attr = false;
+  if (!attr) {
+    if (hipFuncSetAttribute((const void*)KERNEL, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ST5_ERR_LAUNCH;
+    attr = true;
+  }
+  hipLaunchKernelGGL(KERNEL, grid, block, lds_bytes, s, args...);
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+
+// ST5_GEMM_RT_EPILOGUE=1 (A/B switch, read once): the 128^2 bf16 NT and TN kernels run the run-time form of the epilogue only.
+bool rt_epilogue_only() {
+  static const bool on = getenv("ST5_GEMM_RT_EPILOGUE") && getenv("ST5_GEMM_RT_EPILOGUE")[0] == '1';
+  return on;
+}
+
+// The feature mask of a launch when one of the specialised instantiations covers it exactly, else -1 (run-time form).
+// The hot combinations of the training step (transformer_layer.py / multihead_attention.py call sites through functional.py):
+//   0                plain / bias          (QKV and cross-attention projections, plain data gradients)
+//   F_GELU | F_PRE   fc1 forward           (bias, GELU, pre-activation kept for the backward)
+//   F_DROP | F_RES   fc2 / output projection forward (bias, dropout, residual)
+//   F_DACT           data gradient through the GELU (x act'(pre))
+//   F_BETA           accumulating data gradient (dX += ...)
+//   F_RES            data gradient of a post-LN block whose input is also its residual (dX = dH W + dY: 78 of the 87 launches of an
+//                    update that still ran the run-time form in round 5, ST5_GEMM_FEAT_LOG=1)
+int nt_feat_of(const st5_gemm_params& p, int c_vec_ok) {
+  // ST5_GEMM_FEAT_LOG=1: one stderr line per launch that falls back to the run-time form (which combinations deserve a kernel?)
+  static const bool log_rt = getenv("ST5_GEMM_FEAT_LOG") && getenv("ST5_GEMM_FEAT_LOG")[0] == '1';
+  const bool dact = (p.flags & ST5_GEMM_DACT) != 0;
+  if (!c_vec_ok || p.N % 8 != 0 || (p.flags & ST5_GEMM_OUT_F32) || (p.act != ACT_NONE && p.act != ACT_GELU) || (dact && p.act != ACT_GELU)) {
+    if (log_rt) fprintf(stderr, "st5_gemm rt-epilogue layout vec=%d f32=%d act=%d dact=%d M=%d N=%d K=%d batch=%d\n", c_vec_ok,
+                        (int)((p.flags & ST5_GEMM_OUT_F32) != 0), p.act, (int)dact, p.M, p.N, p.K, p.batch);
+    return -1;
+  }
+  int f = 0;
+  if (dact) f |= F_DACT;
+  else if (p.act == ACT_GELU) f |= F_GELU;
+  if (p.dropout_p > 0.f) f |= F_DROP;
+  if (p.R.ptr) f |= F_RES;
+  if (p.Cpre.ptr) f |= F_PRE;
+  if (p.beta != 0.f) f |= F_BETA;
+  switch (f) {
+    case 0: case F_GELU | F_PRE: case F_DROP | F_RES: case F_DACT: case F_BETA: case F_RES: return f;
+    default: break;
+  }
+  if (log_rt) fprintf(stderr, "st5_gemm rt-epilogue feat=%d act=%d M=%d N=%d K=%d batch=%d\n", f, p.act, p.M, p.N, p.K, p.batch);
+  return -1;
+}
+
+// Run-time feature mask -> compile-time constant: fn(std::integral_constant<int, F>()) with F = feat when feat is one of FS... (the masks
+// the caller's kernel family is instantiated for), else with F = -1, the run-time form.  A family instantiates exactly FS... and -1.
+template <int... FS> struct FeatSet {};
+typedef FeatSet<0, F_GELU | F_PRE, F_DROP | F_RES, F_DACT, F_BETA, F_RES> NtFeats;   // nt_feat_of's hot combinations: the bf16 NT families
+typedef FeatSet<0, F_BETA> TnFeats;                                                  // weight gradients: store or accumulate
+template <int... FS, typename Fn>
+int with_feat(const int feat, FeatSet<FS...>, Fn&& fn) {
+  int rc = ST5_OK;
+  const bool hit = ((feat == FS && (rc = fn(std::integral_constant<int, FS>()), true)) || ...);
+  return hit ? rc : fn(std::integral_constant<int, -1>());
+}
 // ------------------------------------------------------------------------------------------------------
 // NT fast path: both operands K-major, K a multiple of the k-tile, no K segmentation.  Same tiling, MFMA
 // fragments, swizzled LDS image and epilogue as gemm_kernel, but the operand tiles go HBM -> LDS directly
@@ -910,11 +1081,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gem
   const int wr = wave >> 1, wc = wave & 1;
   const int z = blockIdx.z;
   const int tiles_n = (p.N + BN - 1) / BN;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
@@ -1115,11 +1282,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_nt_m64_kernel(const st5_gemm
   const int wr = wave >> 1, wc = wave & 1;
   const int z = blockIdx.z;
   const int tiles_n = (p.N + BN - 1) / BN;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * 64, n0 = tn * BN;
@@ -1255,11 +1418,7 @@ __global__ __launch_bounds__(NT2) void gemm_nt256_kernel(const st5_gemm_params p
   const int wr = wave >> 2, wc = wave & 3;
   const int z = blockIdx.z;
   const int tiles_n = (p.N + BN2 - 1) / BN2;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * BM2, n0 = tn * BN2;
@@ -1445,11 +1604,7 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
   const int wr = wave >> 2, wc = wave & 3;
   const int z = blockIdx.z;
   const int tiles_n = (p.N + 255) / 256;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * 256, n0 = tn * 256;
@@ -1586,53 +1741,23 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
   run_epilogue<T, FEAT>(ea, stg, acc[2][0], acc[2][1], acc[3][0], acc[3][1], m0 + wr * 128 + 64, n0 + wc * 64, lane);
 }
 
-int g_p8_stagger = 1;     // st5_gemm_set_nt_tile(3 / 4): phased 256^2 kernel with / without the half-phase stagger of the two m-halves
-template <int FEAT>
-int launch_nt8p_as(const st5_gemm_params& p, int c_vec_ok, dim3 grid, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_nt8p_kernel<FEAT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemm_nt8p_kernel<FEAT, false>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return ST5_ERR_LAUNCH;
-    attr = true;
-  }
-  if (g_p8_stagger) hipLaunchKernelGGL((gemm_nt8p_kernel<FEAT, true>), grid, dim3(512), (size_t)8 * TILE_BYTES, s, p, c_vec_ok);
-  else hipLaunchKernelGGL((gemm_nt8p_kernel<FEAT, false>), grid, dim3(512), (size_t)8 * TILE_BYTES, s, p, c_vec_ok);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
-int nt_feat_of(const st5_gemm_params& p, int c_vec_ok);
-int launch_nt8p(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
+// (stagger: the two m-halves half a phase apart; st5_gemm_set_nt_tile(4) turns it off)
+int launch_nt8p(const st5_gemm_params& p, int c_vec_ok, bool stagger, hipStream_t s) {
   const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  dim3 grid(tiles, 1, p.batch);
-  switch (nt_feat_of(p, c_vec_ok)) {
-    case 0: return launch_nt8p_as<0>(p, c_vec_ok, grid, s);
-    case F_GELU | F_PRE: return launch_nt8p_as<F_GELU | F_PRE>(p, c_vec_ok, grid, s);
-    case F_DROP | F_RES: return launch_nt8p_as<F_DROP | F_RES>(p, c_vec_ok, grid, s);
-    case F_DACT: return launch_nt8p_as<F_DACT>(p, c_vec_ok, grid, s);
-    case F_BETA: return launch_nt8p_as<F_BETA>(p, c_vec_ok, grid, s);
-    case F_RES: return launch_nt8p_as<F_RES>(p, c_vec_ok, grid, s);
-    default: return launch_nt8p_as<-1>(p, c_vec_ok, grid, s);
-  }
+  const dim3 grid(tiles, 1, p.batch), block(512);
+  const size_t lds = (size_t)8 * TILE_BYTES;
+  return with_feat(nt_feat_of(p, c_vec_ok), NtFeats(), [&](auto f) -> int {
+    constexpr int F = decltype(f)::value;
+    return stagger ? launch_lds<gemm_nt8p_kernel<F, true>>(grid, block, lds, s, p, c_vec_ok)
+                   : launch_lds<gemm_nt8p_kernel<F, false>>(grid, block, lds, s, p, c_vec_ok);
+  });
 }
 
 template <typename T>
 int launch_nt256(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
   const int tiles = ((p.M + BM2 - 1) / BM2) * ((p.N + BN2 - 1) / BN2);
-  dim3 grid(tiles, 1, p.batch), block(NT2);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_nt256_kernel<bf16_t>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemm_nt256_kernel<float>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return ST5_ERR_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_nt256_kernel<T>), grid, block, (size_t)NSTAGE2 * STAGE2_BYTES, s, p, c_vec_ok);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
+  return launch_lds<gemm_nt256_kernel<T>>(dim3(tiles, 1, p.batch), dim3(NT2), (size_t)NSTAGE2 * STAGE2_BYTES, s, p, c_vec_ok);
 }
-int g_splitk_target = 384;   // blocks a split-K weight-gradient GEMM aims for (st5_gemm_set_splitk_target)
-int g_nt_tile = 0;   // 0 = choose per problem, 1 = always 128^2, 2 = always 256^2 (A/B switch, st5_gemm_set_nt_tile)
 
 #ifdef GEMM_TIMING
 }  // namespace
@@ -1645,109 +1770,24 @@ namespace {
 #endif
 
 
-// Ring depth of the 128^2 NT kernel (template parameter NBUF).  2 stages (64 KB LDS) let two blocks share a CU and cover each
-// other's LDS-DMA landing latency (~1 us per k-step against 0.25 us of MFMAs): the right shape for grids of several blocks
-// per CU.  A grid of <= 256 blocks has the CU to itself; there a deeper ring (loads two or three k-steps ahead) helps a little:
-// measured on the pre-training update with the micro-batches in turn 48.24 -> 47.33 ms (4 stages), 47.41 (3 stages); deep rings
-// for EVERY grid were 10-25 % slower (round 1).  With the two micro-batches side by side (ddp.accumulate_overlapped) the
-// other stream's blocks are the latency cover and 128 KB blocks keep them off the CU: 37.70 -> 38.27 ms, so that mode turns
-// the deep ring off (st5_gemm_set_deep_ring(0, 2)).
-int g_deep_blocks = 256, g_deep_nbuf = 4;
-int g_nt_slots5 = 1;   // grids of more than g_deep_blocks blocks on five operand slots (80 KB, 2.5 k-steps of loads in flight) instead of two
-                       // stages (64 KB); st5_gemm_set_nt_slots.  Per shape the difference is inside the noise (-4 % .. +3 %,
-                       // profiles/r4_gemm_nt_slots.txt); on the whole update it was -0.4 .. -0.9 % in three same-box pairs on two boxes
-                       // (profiles/r4_knob_ab.txt), so it is the default.  Results are bit-identical either way.
-
-// The feature mask of a launch when one of the specialised instantiations covers it exactly, else -1 (run-time form).
-// The hot combinations of the training step (transformer_layer.py / multihead_attention.py call sites through functional.py):
-//   0                plain / bias          (QKV and cross-attention projections, plain data gradients)
-//   F_GELU | F_PRE   fc1 forward           (bias, GELU, pre-activation kept for the backward)
-//   F_DROP | F_RES   fc2 / output projection forward (bias, dropout, residual)
-//   F_DACT           data gradient through the GELU (x act'(pre))
-//   F_BETA           accumulating data gradient (dX += ...)
-//   F_RES            data gradient of a post-LN block whose input is also its residual (dX = dH W + dY: 78 of the 87 launches of an
-//                    update that still ran the run-time form in round 5, ST5_GEMM_FEAT_LOG=1)
-int nt_feat_of(const st5_gemm_params& p, int c_vec_ok) {
-  // ST5_GEMM_FEAT_LOG=1: one stderr line per launch that falls back to the run-time form (which combinations deserve a kernel?)
-  static const bool log_rt = getenv("ST5_GEMM_FEAT_LOG") && getenv("ST5_GEMM_FEAT_LOG")[0] == '1';
-  const bool dact = (p.flags & ST5_GEMM_DACT) != 0;
-  if (!c_vec_ok || p.N % 8 != 0 || (p.flags & ST5_GEMM_OUT_F32) || (p.act != ACT_NONE && p.act != ACT_GELU) || (dact && p.act != ACT_GELU)) {
-    if (log_rt) fprintf(stderr, "st5_gemm rt-epilogue layout vec=%d f32=%d act=%d dact=%d M=%d N=%d K=%d batch=%d\n", c_vec_ok,
-                        (int)((p.flags & ST5_GEMM_OUT_F32) != 0), p.act, (int)dact, p.M, p.N, p.K, p.batch);
-    return -1;
-  }
-  int f = 0;
-  if (dact) f |= F_DACT;
-  else if (p.act == ACT_GELU) f |= F_GELU;
-  if (p.dropout_p > 0.f) f |= F_DROP;
-  if (p.R.ptr) f |= F_RES;
-  if (p.Cpre.ptr) f |= F_PRE;
-  if (p.beta != 0.f) f |= F_BETA;
-  switch (f) {
-    case 0: case F_GELU | F_PRE: case F_DROP | F_RES: case F_DACT: case F_BETA: case F_RES: return f;
-    default: break;
-  }
-  if (log_rt) fprintf(stderr, "st5_gemm rt-epilogue feat=%d act=%d M=%d N=%d K=%d batch=%d\n", f, p.act, p.M, p.N, p.K, p.batch);
-  return -1;
-}
-
-template <typename T, int NBUF, int FEAT>
-int launch_glds_as(const st5_gemm_params& p, int c_vec_ok, dim3 grid, hipStream_t s) {
-  static bool attr = false;      // (one flag per instantiation)
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_glds_kernel<T, NBUF, FEAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return ST5_ERR_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_glds_kernel<T, NBUF, FEAT>), grid, dim3(NTHREADS), (size_t)(NBUF == 5 ? 5 : NBUF * 2) * TILE_BYTES, s, p, c_vec_ok);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
-
 template <typename T, int NBUF>
 int launch_glds_feat(const st5_gemm_params& p, int c_vec_ok, dim3 grid, hipStream_t s) {
-  if constexpr (sizeof(T) == 2) {      // (bf16: the training step; the fp32 parity mode keeps the one run-time form)
-    static const bool rt_only = getenv("ST5_GEMM_RT_EPILOGUE") && getenv("ST5_GEMM_RT_EPILOGUE")[0] == '1';   // A/B switch
-    switch (rt_only ? -1 : nt_feat_of(p, c_vec_ok)) {
-      case 0: return launch_glds_as<T, NBUF, 0>(p, c_vec_ok, grid, s);
-      case F_GELU | F_PRE: return launch_glds_as<T, NBUF, F_GELU | F_PRE>(p, c_vec_ok, grid, s);
-      case F_DROP | F_RES: return launch_glds_as<T, NBUF, F_DROP | F_RES>(p, c_vec_ok, grid, s);
-      case F_DACT: return launch_glds_as<T, NBUF, F_DACT>(p, c_vec_ok, grid, s);
-      case F_BETA: return launch_glds_as<T, NBUF, F_BETA>(p, c_vec_ok, grid, s);
-      case F_RES: return launch_glds_as<T, NBUF, F_RES>(p, c_vec_ok, grid, s);
-      default: break;
-    }
-  }
-  return launch_glds_as<T, NBUF, -1>(p, c_vec_ok, grid, s);
+  auto go = [&](auto f) -> int {
+    return launch_lds<gemm_nt_glds_kernel<T, NBUF, decltype(f)::value>>(grid, dim3(NTHREADS), (size_t)(NBUF == 5 ? 5 : NBUF * 2) * TILE_BYTES, s, p, c_vec_ok);
+  };
+  // (bf16: the training step; the fp32 parity mode keeps the one run-time form)
+  if constexpr (sizeof(T) == 2) return with_feat(rt_epilogue_only() ? -1 : nt_feat_of(p, c_vec_ok), NtFeats(), go);
+  else return go(std::integral_constant<int, -1>());
 }
 
-template <int FEAT>
-int launch_m64_as(const st5_gemm_params& p, int c_vec_ok, dim3 grid, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_m64_kernel<FEAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return ST5_ERR_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_m64_kernel<FEAT>), grid, dim3(NTHREADS), (size_t)2 * M64_STAGE, s, p, c_vec_ok);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
 int launch_m64(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
   const int tiles = ((p.M + 63) / 64) * ((p.N + BN - 1) / BN);
-  dim3 grid(tiles, 1, p.batch);
-  switch (nt_feat_of(p, c_vec_ok)) {
-    case 0: return launch_m64_as<0>(p, c_vec_ok, grid, s);
-    case F_GELU | F_PRE: return launch_m64_as<F_GELU | F_PRE>(p, c_vec_ok, grid, s);
-    case F_DROP | F_RES: return launch_m64_as<F_DROP | F_RES>(p, c_vec_ok, grid, s);
-    case F_DACT: return launch_m64_as<F_DACT>(p, c_vec_ok, grid, s);
-    case F_BETA: return launch_m64_as<F_BETA>(p, c_vec_ok, grid, s);
-    case F_RES: return launch_m64_as<F_RES>(p, c_vec_ok, grid, s);
-    default: return launch_m64_as<-1>(p, c_vec_ok, grid, s);
-  }
+  const dim3 grid(tiles, 1, p.batch);
+  return with_feat(nt_feat_of(p, c_vec_ok), NtFeats(), [&](auto f) -> int {
+    return launch_lds<gemm_nt_m64_kernel<decltype(f)::value>>(grid, dim3(NTHREADS), (size_t)2 * M64_STAGE, s, p, c_vec_ok);
+  });
 }
 // Which NT launches take the half-height tiles: bf16, and at most g_m64_max_tiles tiles of 128^2 (st5_gemm_set_m64_max_tiles; 0 = never)
-int g_m64_max_tiles = 0;      // (default: never -- every isolated gain below was a LOSS inside the update, see DESIGN.md round 6)
 bool nt_m64_pays(const st5_gemm_params& p) {
   static const int env = getenv("ST5_M64_MAX_TILES") ? atoi(getenv("ST5_M64_MAX_TILES")) : -1;   // (A/B switch for whole-step measurements)
   const int lim = env >= 0 ? env : g_m64_max_tiles;
@@ -1768,10 +1808,6 @@ int launch_glds(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
   }
   return launch_glds_feat<T, 2>(p, c_vec_ok, grid, s);
 }
-
-bool g_use_glds = true;
-
-bool aligned(const void* p, size_t a) { return (reinterpret_cast<uintptr_t>(p) % a) == 0; }
 
 // ------------------------------------------------------------------------------------------------------
 // TN fast path (weight gradients: C[M,N] = A^T B with A = dY [K, M], B = X [K, N], the reduction index is the slow
@@ -1821,11 +1857,8 @@ __device__ __forceinline__ void tn_glds_body(const st5_gemm_params& p, const int
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int tiles_n = (p.N + BN - 1) / BN;
-  int bid = bx;
-  if (remap) {     // (remap == false: the caller has placed this block with the XCDs in mind already, see gemm_tn_glds_kernel)
-    const int nwg = nwg_, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  // (remap == false: the caller has placed this block with the XCDs in mind already, see gemm_tn_glds_kernel)
+  const int bid = remap ? xcd_remap(bx, nwg_) : bx;
   int tm, tn;
   tile_of(bid, tiles_n, nwg_, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
@@ -2006,8 +2039,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_tn_glds_kernel(const st5_gem
   const bool placed = ny > 1 && gridDim.z == 1;
   if (placed) {
     const int total = nx * ny, lin = by * nx + bx;
-    const int xcd = lin & 7, q = total >> 3, rmd = total & 7;
-    const int pidx = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (lin >> 3);
+    const int pidx = xcd_remap(lin, total);
     by = pidx / nx;
     bx = pidx - by * nx;
   }
@@ -2058,11 +2090,8 @@ __device__ __forceinline__ void tn8p_body(const st5_gemm_params& p, const int c_
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   const int tiles_n = (p.N + 255) / 256;
-  int bid = bx;
-  if (REMAP) {     // (the grouped launch remaps over ALL its tiles and passes the problem-local tile number)
-    const int nwg = nwg_, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  // (REMAP == false: the grouped launch remaps over ALL its tiles and passes the problem-local tile number)
+  const int bid = REMAP ? xcd_remap(bx, nwg_) : bx;
   int tm, tn;
   tile_of(bid, tiles_n, nwg_, tm, tn);
   const int m0 = tm * 256, n0 = tn * 256;
@@ -2261,11 +2290,7 @@ __global__ __launch_bounds__(512) void gemm_tn8p_group_kernel(const Tn8pGroupArg
   // tiles per problem every XCD held 1-5 tiles of EACH of the launch's eight problems -- ~35 panels for the same 27 tiles -- and the
   // counters showed it: 921 MB through the fabric per launch (2.1x the algorithmic bytes) at 4 TB/s, the bound of the kernel.
   const int T = g.first[g.n];
-  int gidx;
-  {
-    const int b = (int)blockIdx.x, xcd = b & 7, q = T >> 3, rmd = T & 7;
-    gidx = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (b >> 3);
-  }
+  const int gidx = xcd_remap((int)blockIdx.x, T);
   int j = 0;
   while (j + 1 < g.n && gidx >= g.first[j + 1]) ++j;
   const int lb = gidx - g.first[j];
@@ -2278,9 +2303,6 @@ __global__ __launch_bounds__(512) void gemm_tn8p_group_kernel(const Tn8pGroupArg
   tn8p_body<FEAT, true, false>(p, 1, lb, g.tiles[j], 0, 1);
 }
 
-int g_tn8p = 0;   // st5_gemm_set_tn_phased: 0 (default) = always the 128^2 kernel; 1 / 2 = eligible weight-gradient GEMMs on the phased 256^2 kernel (staggered / not).
-                  // Measured (profiles/r4_gemm_tn_phased.txt): the phased kernel wins only on very long reductions over few tiles (512 x 1536 x 128k:
-                  // 335 vs 343 us); on the transformer weight gradients its 256^2 tiles need 2x the split-K slabs and lose 20-35 %.
 bool tn8p_ok(const st5_gemm_params& p, int c_vec_ok) {
   if (!g_tn8p || p.batch != 1 || p.A.rpb || p.B.rpb || p.A.seg || p.B.seg) return false;
   if (!c_vec_ok || p.N % 8 || !(p.flags & ST5_GEMM_OUT_F32) || (p.flags & ST5_GEMM_DACT) || p.act != ACT_NONE || p.dropout_p != 0.f ||
@@ -2300,40 +2322,28 @@ int tn8p_splits(const st5_gemm_params& p) {
   return (nk + per - 1) / per;
 }
 int launch_tn8p(const st5_gemm_params& p, int c_vec_ok, int nsplit, hipStream_t s) {
-  static bool attr = false;
-  if (!attr) {
-    const void* fns[] = {(const void*)gemm_tn8p_kernel<0, true>, (const void*)gemm_tn8p_kernel<F_BETA, true>,
-                         (const void*)gemm_tn8p_kernel<0, false>, (const void*)gemm_tn8p_kernel<F_BETA, false>};
-    for (const void* f : fns)
-      if (hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ST5_ERR_LAUNCH;
-    attr = true;
-  }
   const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  dim3 grid(tiles, nsplit, 1), block(512);
-  const size_t shm = (size_t)8 * TILE_BYTES;
-  if (p.beta == 0.f) {
-    if (g_tn8p == 2) hipLaunchKernelGGL((gemm_tn8p_kernel<0, false>), grid, block, shm, s, p, c_vec_ok);
-    else hipLaunchKernelGGL((gemm_tn8p_kernel<0, true>), grid, block, shm, s, p, c_vec_ok);
-  } else {
-    if (g_tn8p == 2) hipLaunchKernelGGL((gemm_tn8p_kernel<F_BETA, false>), grid, block, shm, s, p, c_vec_ok);
-    else hipLaunchKernelGGL((gemm_tn8p_kernel<F_BETA, true>), grid, block, shm, s, p, c_vec_ok);
-  }
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
+  const dim3 grid(tiles, nsplit, 1), block(512);
+  const size_t lds = (size_t)8 * TILE_BYTES;
+  return with_feat(p.beta == 0.f ? 0 : F_BETA, TnFeats(), [&](auto f) -> int {
+    constexpr int F = decltype(f)::value;
+    if constexpr (F < 0) return ST5_ERR_ARG;   // (tn8p_ok admits plain launches only: this family has no run-time form)
+    else return g_tn8p == 2 ? launch_lds<gemm_tn8p_kernel<F, false>>(grid, block, lds, s, p, c_vec_ok)
+                            : launch_lds<gemm_tn8p_kernel<F, true>>(grid, block, lds, s, p, c_vec_ok);
+  });
 }
 
 int launch_tn_glds(const st5_gemm_params& p, int c_vec_ok, int nsplit, hipStream_t s) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  dim3 grid(tiles, nsplit, p.batch), block(NTHREADS);
+  const dim3 grid(tiles, nsplit, p.batch), block(NTHREADS);
   // weight gradients: fp32 output, plain store (split-K slabs / first contribution) or accumulate -- own instantiations
-  static const bool rt_only = getenv("ST5_GEMM_RT_EPILOGUE") && getenv("ST5_GEMM_RT_EPILOGUE")[0] == '1';   // A/B switch
-  const bool plain = !rt_only && c_vec_ok && p.N % 8 == 0 && (p.flags & ST5_GEMM_OUT_F32) && !(p.flags & ST5_GEMM_DACT) && p.act == ACT_NONE &&
+  const bool plain = !rt_epilogue_only() && c_vec_ok && p.N % 8 == 0 && (p.flags & ST5_GEMM_OUT_F32) && !(p.flags & ST5_GEMM_DACT) && p.act == ACT_NONE &&
                      p.dropout_p == 0.f && !p.R.ptr && !p.Cpre.ptr;
-  if (plain && p.beta == 0.f) hipLaunchKernelGGL(gemm_tn_glds_kernel<0>, grid, block, (size_t)4 * TILE_BYTES, s, p, c_vec_ok);
-  else if (plain) hipLaunchKernelGGL(gemm_tn_glds_kernel<F_BETA>, grid, block, (size_t)4 * TILE_BYTES, s, p, c_vec_ok);
-  else hipLaunchKernelGGL(gemm_tn_glds_kernel<-1>, grid, block, (size_t)4 * TILE_BYTES, s, p, c_vec_ok);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
+  return with_feat(!plain ? -1 : p.beta == 0.f ? 0 : F_BETA, TnFeats(), [&](auto f) -> int {
+    hipLaunchKernelGGL(gemm_tn_glds_kernel<decltype(f)::value>, grid, block, (size_t)4 * TILE_BYTES, s, p, c_vec_ok);   // (64 KB: inside the default limit)
+    HIP_CHECK_LAUNCH();
+    return ST5_OK;
+  });
 }
 
 // operands the TN LDS-DMA kernel can take: bf16, both k-strided (row split allowed, no k segments), 16-byte
@@ -2354,10 +2364,7 @@ bool tn_glds_ok(const st5_gemm_params& p, int dtype) {
 // problems (8192^3: 1.20 against 0.89) -- or when ONE round of 256^2 tiles nearly fills the chip with a short reduction (3992 x 3072 x
 // 768: 192 tiles, 27.8 against 30.6 us).  Everything else of the transformer (96-384 tiles in 1.1-2 rounds, or long K on few tiles)
 // stays on 128^2, two blocks per CU.
-// (A/B knob, round 6, st5_gemm_set_nt_longk: problems of at least `g_nt_longk_tiles` tiles of 256^2 with a reduction of at least
-//  `g_nt_longk_nk` k-tiles also take the phased kernel -- the N = 768, K = 2304 / 3072 shapes at 8192 rows are 96 tiles: one block on 96
-//  CUs for 36-48 k-tiles instead of 384 tiles of 128^2 on every CU.  0 = off, the default.)
-int g_nt_longk_tiles = 0, g_nt_longk_nk = 36;
+// (and, st5_gemm_set_nt_longk: long reductions over fewer tiles -- see g_nt_longk_tiles)
 bool nt256_pays(int M, int N, int nk64, int batch) {
   const long long t256 = (long long)((M + 255) / 256) * ((N + 255) / 256) * batch;
   if (t256 >= 448) return true;
@@ -2403,11 +2410,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_mx8_kernel(const st5_gemm
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int wr = wave >> 1, wc = wave & 1;
   const int tiles_n = (p.N + BN - 1) / BN;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * BM, n0 = tn * BN;
@@ -2513,19 +2516,6 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_mx8_kernel(const st5_gemm
   run_epilogue<T, FEAT>(ea, stage, acc00, acc01, acc10, acc11, m0 + wr * 64, n0 + wc * 64, lane);
 }
 
-template <int FEAT>
-int launch_mx8_as(const st5_gemm_params& p, int c_vec_ok, const unsigned char* sa, long long sa_ld, const unsigned char* sb, long long sb_ld,
-                  dim3 grid, hipStream_t s, const MxOut mo = MxOut{nullptr, 0, nullptr, 0}) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_nt_mx8_kernel<FEAT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess) return ST5_ERR_LAUNCH;
-    attr = true;
-  }
-  hipLaunchKernelGGL((gemm_nt_mx8_kernel<FEAT>), grid, dim3(NTHREADS), (size_t)4 * TILE_BYTES, s, p, c_vec_ok, sa, sa_ld, sb, sb_ld, mo);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
-
 // ------------------------------------------------------------------------------------------------------
 // MX-fp8 NT path, 256 x 256 block tile, PHASED schedule (round 6): gemm_nt8p_kernel's program on fp8 bytes.  An LDS row is still 128
 // bytes, now 128 k-elements, so staging, swizzle, the four fragment offsets and the phase structure are the bf16 kernel's byte for
@@ -2550,11 +2540,7 @@ __global__ __launch_bounds__(512) void gemm_nt8p_mx8_kernel(const st5_gemm_param
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   const int tiles_n = (p.N + 255) / 256;
-  int bid = blockIdx.x;
-  {
-    const int nwg = gridDim.x, xcd = bid & 7, q = nwg >> 3, rmd = nwg & 7;
-    bid = (xcd < rmd ? xcd * (q + 1) : rmd * (q + 1) + (xcd - rmd) * q) + (bid >> 3);
-  }
+  const int bid = xcd_remap((int)blockIdx.x, (int)gridDim.x);
   int tm, tn;
   tile_of(bid, tiles_n, (int)gridDim.x, tm, tn);
   const int m0 = tm * 256, n0 = tn * 256;
@@ -2744,29 +2730,12 @@ __global__ __launch_bounds__(512) void gemm_nt8p_mx8_kernel(const st5_gemm_param
 // VALU slots per element) is NOT hidden in a one-block-per-CU kernel; behind a short reduction it costs more than the phased schedule
 // gains (measured inside the Large update, B = 32: fc1 forward N = 4096, K = 1024 with GELU + copy + fp8 image 147 us phased against
 // 113 us + quantiser on 128^2 tiles, while the plain N = 3072 / 4096 launches gain 20-25 %): such launches need >= g_mx8_heavy_nk k-tiles.
-int g_mx8_heavy_nk = 16;
 bool mx8_256_pays(int M, int N, int nk, int feat) {
   const long long t256 = (long long)((M + 255) / 256) * ((N + 255) / 256);
   if (!(t256 >= 448 || (t256 >= 176 && t256 <= 256))) return false;
   const bool heavy = feat < 0 || (feat & (F_GELU | F_DACT | F_PRE | F_DROP | F_Q8)) != 0;
   return !heavy || nk >= g_mx8_heavy_nk;
 }
-int g_mx8_tile = 0;   // 0 = choose per problem, 1 = always 128^2, 2 = always the phased 256^2 kernel (st5_gemm_set_mx8_tile)
-template <int FEAT>
-int launch_mx8p_as(const st5_gemm_params& p, int c_vec_ok, const unsigned char* sa, long long sa_ld, const unsigned char* sb, long long sb_ld,
-                   hipStream_t s, const MxOut mo = MxOut{nullptr, 0, nullptr, 0}) {
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_nt8p_mx8_kernel<FEAT, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return ST5_ERR_LAUNCH;
-    attr = true;
-  }
-  const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
-  hipLaunchKernelGGL((gemm_nt8p_mx8_kernel<FEAT, true>), dim3(tiles, 1, 1), dim3(512), (size_t)8 * TILE_BYTES, s, p, c_vec_ok, sa, sa_ld, sb, sb_ld, mo);
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
-
 // MX quantisation of a row-major bf16 matrix along its rows: per 32 consecutive elements one e8m0 scale byte
 // E = floor(log2(amax)) - 8 + 127 (the OCP MX rule for e4m3, whose largest binade is 2^8) and 32 e4m3 bytes of x * 2^(127 - E),
 // round-to-nearest-even, saturating FINITE values at +-448 (NaN / Inf propagate: see the kernel).  Four lanes per block, 8 elements each: coalesced 16-byte loads and 8-byte stores
@@ -2804,16 +2773,31 @@ __global__ __launch_bounds__(256) void multi_quant_mx8_kernel(const QuantJob* __
   mx8_quant8(v, j.q + i, j.s + (i >> 5), (i & 31) == 0);
 }
 
+// The kernels that take k-strided operands, an asum column or split-K (nsplit > 1: every split stores its own slab): the phased TN
+// kernel where st5_gemm chose it (use8p), the 128^2 TN kernel where the operands allow, else the register-staged general kernel.
+int launch_general(const st5_gemm_params& p, int dtype, bool use8p, int c_vec_ok, int nsplit, hipStream_t s) {
+  if (use8p) return launch_tn8p(p, c_vec_ok, nsplit, s);
+  if (g_use_glds && tn_glds_ok(p, dtype)) return launch_tn_glds(p, c_vec_ok, nsplit, s);
+  return dtype == ST5_BF16 ? launch<bf16_t>(p, c_vec_ok, nsplit, s) : launch<float>(p, c_vec_ok, nsplit, s);
+}
+// The partial products of a split-K GEMM: problem p with its output rewritten to the dense fp32 slabs [nsplit][M][N] (+ [nsplit][M] asum columns)
+int launch_splitk_partials(const st5_gemm_params& p, int dtype, bool use8p, int nsplit, float* slabs, hipStream_t s) {
+  st5_gemm_params q = p;
+  q.C.ptr = slabs; q.C.ld = p.N; q.C.rpb = 0; q.C.bstride = 0; q.C.zs0 = q.C.zs1 = 0; q.beta = 0.f;
+  return launch_general(q, dtype, use8p, 1, nsplit, s);
+}
+// blocks of 256 threads that fold the slabs of an M x N output, four elements per thread
+int reduce_blocks(int M, int N, int cap) {
+  const long long blocks = ((long long)M * N / 4 + 255) / 256;
+  return (int)(blocks > cap ? cap : blocks);
+}
+
 }  // namespace
 
 extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
   if (!pp) return ST5_ERR_ARG;
   st5_gemm_params p = *pp;
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0) return ST5_ERR_ARG;
-  if (!p.A.ptr || !p.B.ptr || !p.C.ptr) return ST5_ERR_ARG;
-  if (p.batch <= 0) p.batch = 1;
-  if (p.zdiv <= 0) p.zdiv = 1;
-  if ((p.flags & ST5_GEMM_DACT) && !p.P.ptr) return ST5_ERR_ARG;
+  if (const int rc = normalise_and_check(p)) return rc;
   if (p.asum && p.batch > 1) return ST5_ERR_ARG;
   if (dtype != ST5_BF16 && dtype != ST5_F32) return ST5_ERR_ARG;
   const int es = dtype == ST5_BF16 ? 2 : 4;
@@ -2828,11 +2812,7 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
   };
   if (!op_ok(p.A, p.flags & ST5_GEMM_A_KSTRIDED)) return ST5_ERR_ALIGN;
   if (!op_ok(p.B, p.flags & ST5_GEMM_B_KSTRIDED)) return ST5_ERR_ALIGN;
-  auto c_ok = [&](const st5_operand& o) {
-    if (!o.ptr) return true;
-    return aligned(o.ptr, 16) && o.ld % 8 == 0 && o.bstride % 8 == 0 && o.zs0 % 8 == 0 && o.zs1 % 8 == 0;
-  };
-  const int c_vec_ok = c_ok(p.C) && c_ok(p.R) && c_ok(p.P) && c_ok(p.Cpre);
+  const int c_vec_ok = c_class_vec_ok(p, true);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   // split-K for fp32 outputs (weight gradients: small M x N, very long K): raise the block count towards ~1.5 per
   // CU; every split writes its own dense fp32 slab (plain 16-byte stores), a second kernel sums the slabs into C.
@@ -2855,54 +2835,33 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
   // weight gradients without row split / segments: the phased 256^2 kernel with its own split count (about one block per CU)
   const bool use8p = dtype == ST5_BF16 && g_use_glds && tn_glds_ok(p, dtype) && tn8p_ok(p, c_vec_ok) && p.C.ld % 4 == 0;
   if (use8p) nsplit = tn8p_splits(p);
-  if (nsplit > 1 && g_defer && (p.flags & ST5_GEMM_DEFERRABLE) && !p.C.rpb && p.C.ld % 4 == 0) {
-    const size_t need = ((size_t)nsplit * p.M * p.N + (p.asum ? (size_t)nsplit * p.M : 0)) * sizeof(float);
-    // the same output twice in one batch (tied weights) would race inside the batched reduction: fold what is pending first
-    DeferState* ds = defer_state(s, true);
-    if (!ds) return ST5_ERR_LAUNCH;
-    for (int j = 0; j < g_pending.n; ++j)
-      if (g_pending.d[j].C == p.C.ptr) { const int rc = flush_pending(s); if (rc) return rc; break; }
-    if (g_pending.n == MR_MAX) { const int rc = flush_pending(s); if (rc) return rc; }
-    float* slabs = arena_take(ds, need);
-    if (!slabs) {
-      const int rc = flush_pending(s);
-      if (rc) return rc;
-      if (need > g_arena_bytes || g_arena_bytes == 0) {
-        if (g_arena) (void)hipFree(g_arena);   // synchronises with in-flight users
-        size_t want = g_arena_bytes ? g_arena_bytes * 2 : (size_t(1) << 30);
-        while (want < need * 4) want *= 2;
-        if (st5_dev_malloc(&g_arena, want) != hipSuccess) { g_arena = nullptr; g_arena_bytes = 0; return ST5_ERR_LAUNCH; }
-        g_arena_bytes = want;
-      }
-      slabs = arena_take(ds, need);
-      if (!slabs) return ST5_ERR_LAUNCH;
-    }
-    st5_gemm_params q = p;
-    q.C.ptr = slabs; q.C.ld = p.N; q.C.rpb = 0; q.C.bstride = 0; q.C.zs0 = q.C.zs1 = 0; q.beta = 0.f;
-    const int rc = use8p ? launch_tn8p(q, 1, nsplit, s) : (g_use_glds && tn_glds_ok(q, dtype)) ? launch_tn_glds(q, 1, nsplit, s)
-                   : dtype == ST5_BF16 ? launch<bf16_t>(q, 1, nsplit, s) : launch<float>(q, 1, nsplit, s);
-    if (rc) return rc;
-    MrDesc& d = g_pending.d[g_pending.n++];
-    d.slabs = slabs; d.C = reinterpret_cast<float*>(const_cast<void*>(p.C.ptr)); d.asum = p.asum; d.ldc = p.C.ld; d.nsplit = nsplit;
-    d.M = p.M; d.N = p.N; d.beta = p.beta; d.blk0 = g_pending_blocks; d.pad = 0; d.gate = p.gate;
-    long long blocks = ((long long)p.M * p.N / 4 + 255) / 256;
-    if (blocks > 1024) blocks = 1024;
-    g_pending_blocks += (int)blocks;
-    return ST5_OK;
-  }
   if (nsplit > 1) {
-    float* slabs = slab_workspace(((size_t)nsplit * p.M * p.N + (p.asum ? (size_t)nsplit * p.M : 0)) * sizeof(float), s);
+    const size_t need = ((size_t)nsplit * p.M * p.N + (p.asum ? (size_t)nsplit * p.M : 0)) * sizeof(float);
+    float* const C = reinterpret_cast<float*>(const_cast<void*>(p.C.ptr));
+    if (g_defer && (p.flags & ST5_GEMM_DEFERRABLE) && !p.C.rpb && p.C.ld % 4 == 0) {
+      // deferred: the slabs stay in the stream's arena, the reduction is queued for st5_gemm_flush_splitk
+      DeferState* ds = defer_state(s, true);
+      if (!ds) return ST5_ERR_LAUNCH;
+      // the same output twice in one batch (tied weights) would race inside the batched reduction: fold what is pending first
+      for (int j = 0; j < ds->pending.n; ++j)
+        if (ds->pending.d[j].C == p.C.ptr) { const int rc = ds->flush(); if (rc) return rc; break; }
+      if (ds->pending.n == MR_MAX) { const int rc = ds->flush(); if (rc) return rc; }
+      float* slabs = ds->take_or_grow(need);
+      if (!slabs) return ST5_ERR_LAUNCH;
+      const int rc = launch_splitk_partials(p, dtype, use8p, nsplit, slabs, s);
+      if (rc) return rc;
+      MrDesc& d = ds->pending.d[ds->pending.n++];
+      d.slabs = slabs; d.C = C; d.asum = p.asum; d.ldc = p.C.ld; d.nsplit = nsplit;
+      d.M = p.M; d.N = p.N; d.beta = p.beta; d.blk0 = ds->pending_blocks; d.pad = 0; d.gate = p.gate;
+      ds->pending_blocks += reduce_blocks(p.M, p.N, 1024);
+      return ST5_OK;
+    }
+    float* slabs = slab_workspace(need, s);
     if (!slabs) return ST5_ERR_LAUNCH;
-    st5_gemm_params q = p;
-    q.C.ptr = slabs; q.C.ld = p.N; q.C.rpb = 0; q.C.bstride = 0; q.C.zs0 = q.C.zs1 = 0; q.beta = 0.f;
-    const int rc = use8p ? launch_tn8p(q, 1, nsplit, s) : (g_use_glds && tn_glds_ok(q, dtype)) ? launch_tn_glds(q, 1, nsplit, s)
-                   : dtype == ST5_BF16 ? launch<bf16_t>(q, 1, nsplit, s) : launch<float>(q, 1, nsplit, s);
+    const int rc = launch_splitk_partials(p, dtype, use8p, nsplit, slabs, s);
     if (rc) return rc;
-    long long blocks = ((long long)p.M * p.N / 4 + 255) / 256;
-    if (blocks > 2048) blocks = 2048;
-    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, s, slabs,
-                       reinterpret_cast<float*>(const_cast<void*>(p.C.ptr)), nsplit, p.M, p.N, (long long)p.C.ld, p.C.rpb,
-                       (long long)p.C.bstride, p.beta, p.asum, p.gate);
+    hipLaunchKernelGGL(splitk_reduce_kernel, dim3((unsigned)reduce_blocks(p.M, p.N, 2048)), dim3(256), 0, s, slabs, C, nsplit, p.M, p.N,
+                       (long long)p.C.ld, p.C.rpb, (long long)p.C.bstride, p.beta, p.asum, p.gate);
     HIP_CHECK_LAUNCH();
     return ST5_OK;
   }
@@ -2911,66 +2870,61 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
   const int bk = 128 / es;
   if (g_use_glds && !p.asum && !(p.flags & (ST5_GEMM_A_KSTRIDED | ST5_GEMM_B_KSTRIDED)) && p.K % bk == 0 && p.K >= 2 * bk && !p.A.seg && !p.B.seg)
   {
-    if ((g_nt_tile == 3 || g_nt_tile == 4) && dtype == ST5_BF16 && p.K % 64 == 0) {
-      g_p8_stagger = g_nt_tile == 3;
-      return launch_nt8p(p, c_vec_ok, s);
-    }
+    if ((g_nt_tile == 3 || g_nt_tile == 4) && dtype == ST5_BF16 && p.K % 64 == 0) return launch_nt8p(p, c_vec_ok, g_nt_tile == 3, s);
     if (g_nt_tile == 2) return dtype == ST5_BF16 ? launch_nt256<bf16_t>(p, c_vec_ok, s) : launch_nt256<float>(p, c_vec_ok, s);
     if (g_nt_tile == 5 && dtype == ST5_BF16) return launch_m64(p, c_vec_ok, s);
     if (g_nt_tile == 0 && dtype == ST5_BF16 && nt_m64_pays(p) && !nt256_pays(p.M, p.N, p.K / 64, p.batch)) return launch_m64(p, c_vec_ok, s);
     if (g_nt_tile == 0 && nt256_pays(p.M, p.N, p.K / 64, p.batch)) {
       // bf16: the phased kernel (round 4); fp32 parity mode: the first 256^2 kernel (4-stage ring)
-      if (dtype == ST5_BF16 && p.K % 64 == 0) { g_p8_stagger = 1; return launch_nt8p(p, c_vec_ok, s); }
+      if (dtype == ST5_BF16 && p.K % 64 == 0) return launch_nt8p(p, c_vec_ok, true, s);
       if (dtype != ST5_BF16) return launch_nt256<float>(p, c_vec_ok, s);
     }
     return dtype == ST5_BF16 ? launch_glds<bf16_t>(p, c_vec_ok, s) : launch_glds<float>(p, c_vec_ok, s);
   }
-  if (use8p) return launch_tn8p(p, c_vec_ok, nsplit, s);
-  if (g_use_glds && tn_glds_ok(p, dtype)) return launch_tn_glds(p, c_vec_ok, nsplit, s);
-  if (dtype == ST5_BF16) return launch<bf16_t>(p, c_vec_ok, nsplit, s);
-  return launch<float>(p, c_vec_ok, nsplit, s);
+  return launch_general(p, dtype, use8p, c_vec_ok, nsplit, s);
 }
 
 /* Several weight-gradient GEMMs (C_j [M_j x N_j] (+)= A_j^T B_j: both operands k-strided bf16, fp32 output, no epilogue beyond beta and the
  * bias-gradient column) as ONE launch without split-K (gemm_tn_group_kernel).  A problem's result does not depend on the rest of the
  * group (every tile runs its own whole reduction).  Falls back to one st5_gemm call per problem when a problem does not have that form
  * or two problems write the same output. */
-int g_tn_group_tile = 0;   // st5_gemm_set_tn_group_tile: 0 = per problem (phased 256^2 when M, N are multiples of 256 and K >= 512), 1 = 128^2 always
-// Does this (group-eligible) problem run on the phased 256 x 256 grouped kernel?  A function of the problem alone.
+namespace {
+// Does this (group-eligible) problem run on the phased 256 x 256 grouped kernel?  A function of the problem alone: the shape rule (what
+// st5_gemm_tn_group_is_phased answers) and operands without row split / segments.
+bool tn_group_phased_shape(int M, int N, int K) { return g_tn_group_tile == 0 && M % 256 == 0 && N % 256 == 0 && K >= 512; }
 bool tn_group_phased(const st5_gemm_params& p) {
-  return g_tn_group_tile == 0 && p.M % 256 == 0 && p.N % 256 == 0 && p.K >= 512 && p.C.ld % 4 == 0 && !p.A.rpb && !p.B.rpb && !p.A.seg && !p.B.seg;
+  return tn_group_phased_shape(p.M, p.N, p.K) && p.C.ld % 4 == 0 && !p.A.rpb && !p.B.rpb && !p.A.seg && !p.B.seg;
 }
+}  // namespace
 extern "C" int st5_gemm_tn_group(const st5_gemm_params* list, int32_t n, int dtype, void* stream) {
   if (!list || n < 0) return ST5_ERR_ARG;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  static bool attr = false;
-  if (!attr) {
-    if (hipFuncSetAttribute((const void*)gemm_tn8p_group_kernel<0>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess ||
-        hipFuncSetAttribute((const void*)gemm_tn8p_group_kernel<F_BETA>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
-      return ST5_ERR_LAUNCH;
-    attr = true;
-  }
   TnGroupArgs g;          // 128 x 128 class: up to TNG_MAX problems
   Tn8pGroupArgs g8;       // phased 256 x 256 class: up to TNG8P_MAX
   int m = 0;             // problems in the open group
   long long padded = 0;
   bool accum = false, phased = false;
-  auto launch = [&]() {
-    if (m == 0) return (int)ST5_OK;
+  auto launch_group = [&]() -> int {     // the open group as one launch
+    if (m == 0) return ST5_OK;
     if (phased) {      // (first[]: cumulative tile counts, no padding -- the kernel remaps over the whole launch)
       g8.first[m] = (int)padded; g8.n = m;
       for (int i = m; i < TNG8P_MAX; ++i) { g8.tiles[i] = 0; g8.first[i + 1] = (int)padded; }
-      if (accum) hipLaunchKernelGGL(gemm_tn8p_group_kernel<F_BETA>, dim3((unsigned)padded), dim3(512), (size_t)8 * TILE_BYTES, s, g8);
-      else hipLaunchKernelGGL(gemm_tn8p_group_kernel<0>, dim3((unsigned)padded), dim3(512), (size_t)8 * TILE_BYTES, s, g8);
     } else {
       g.first[m] = (int)padded; g.n = m;
       for (int i = m; i < TNG_MAX; ++i) { g.tiles[i] = 0; g.first[i + 1] = (int)padded; }
-      if (accum) hipLaunchKernelGGL(gemm_tn_group_kernel<F_BETA>, dim3((unsigned)padded), dim3(NTHREADS), (size_t)4 * TILE_BYTES, s, g);
-      else hipLaunchKernelGGL(gemm_tn_group_kernel<0>, dim3((unsigned)padded), dim3(NTHREADS), (size_t)4 * TILE_BYTES, s, g);
     }
+    const dim3 grid((unsigned)padded);
     m = 0; padded = 0;
-    HIP_CHECK_LAUNCH();
-    return (int)ST5_OK;
+    return with_feat(accum ? F_BETA : 0, TnFeats(), [&](auto f) -> int {
+      constexpr int F = decltype(f)::value;
+      if constexpr (F < 0) return ST5_ERR_ARG;   // (a group holds plain problems only: these families have no run-time form)
+      else {
+        if (phased) return launch_lds<gemm_tn8p_group_kernel<F>>(grid, dim3(512), (size_t)8 * TILE_BYTES, s, g8);
+        hipLaunchKernelGGL(gemm_tn_group_kernel<F>, grid, dim3(NTHREADS), (size_t)4 * TILE_BYTES, s, g);   // (64 KB: inside the default limit)
+        HIP_CHECK_LAUNCH();
+        return ST5_OK;
+      }
+    });
   };
   // Whether a problem runs here (whole reduction per tile) or through st5_gemm (split-K), and on which block tile, is decided by the
   // problem ALONE, never by what it is queued with: a replayed update and an eager one, or two micro-batch schedules, form different
@@ -2978,9 +2932,7 @@ extern "C" int st5_gemm_tn_group(const st5_gemm_params* list, int32_t n, int dty
   // the end of a backward pass.)
   for (int i = 0; i < n; ++i) {
     st5_gemm_params p = list[i];
-    if (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.A.ptr || !p.B.ptr || !p.C.ptr) return ST5_ERR_ARG;
-    if (p.batch <= 0) p.batch = 1;
-    if (p.zdiv <= 0) p.zdiv = 1;
+    if (const int rc = normalise_and_check(p)) return rc;
     const int want = ST5_GEMM_A_KSTRIDED | ST5_GEMM_B_KSTRIDED | ST5_GEMM_OUT_F32;
     const bool plain = !p.bias && !p.R.ptr && !p.P.ptr && !p.Cpre.ptr && p.act == ST5_ACT_NONE && p.dropout_p == 0.f && !(p.flags & ST5_GEMM_DACT);
     const bool c_ok = aligned(p.C.ptr, 16) && p.C.ld % 8 == 0 && !p.C.rpb && p.C.zs0 == 0 && p.C.zs1 == 0;
@@ -2995,7 +2947,7 @@ extern "C" int st5_gemm_tn_group(const st5_gemm_params* list, int32_t n, int dty
     bool clash = (m > 0 && m == (phased ? TNG8P_MAX : TNG_MAX)) || (m > 0 && ((p.beta != 0.f) != accum || ph != phased));
     for (int j = 0; j < m && !clash; ++j)
       clash = phased ? (g8.p[j].C == p.C.ptr || (p.asum && g8.p[j].asum == p.asum)) : (g.p[j].C.ptr == p.C.ptr || (p.asum && g.p[j].asum == p.asum));
-    if (clash) { const int rc = launch(); if (rc) return rc; }      // (same output twice, mixed beta or block tile: in order, one launch each)
+    if (clash) { const int rc = launch_group(); if (rc) return rc; }      // (same output twice, mixed beta or block tile: in order, one launch each)
     if (m == 0) { accum = p.beta != 0.f; phased = ph; }
     const int tiles = ph ? (p.M / 256) * (p.N / 256) : ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
     if (ph) {
@@ -3009,14 +2961,11 @@ extern "C" int st5_gemm_tn_group(const st5_gemm_params* list, int32_t n, int dty
     padded += ph ? tiles : (tiles + 7) / 8 * 8;
     ++m;
   }
-  return launch();
+  return launch_group();
 }
-/* Block tile of the grouped weight-gradient launch: 0 (default) = per problem -- the phased 256x256 kernel when M and N are multiples of
- * 256 and K >= 512 (every Linear of the transformer), else 128x128; 1 = 128x128 always (A/B measurements, tests). */
-extern "C" int st5_gemm_set_tn_group_tile(int mode) { if (mode < 0 || mode > 1) return ST5_ERR_ARG; g_tn_group_tile = mode; return ST5_OK; }
 /* 1 when st5_gemm_tn_group would run a weight gradient of this shape on the phased 256x256 kernel (host-side tile accounting). */
 extern "C" int st5_gemm_tn_group_is_phased(int32_t M, int32_t N, int32_t K) {
-  return g_tn_group_tile == 0 && M % 256 == 0 && N % 256 == 0 && K >= 512;
+  return tn_group_phased_shape(M, N, K);
 }
 
 /* MX-fp8 GEMM (see gemm_nt_mx8_kernel): p describes fp8 operands A [M x K], B [N x K] (ld in BYTES = elements, K-major, no row
@@ -3026,18 +2975,13 @@ int gemm_mxfp8_impl(const st5_gemm_params* pp, const uint8_t* a_scale, int64_t a
                     const MxOut mo, void* stream) {
   if (!pp || !a_scale || !b_scale) return ST5_ERR_ARG;
   st5_gemm_params p = *pp;
-  if (p.M <= 0 || p.N <= 0 || p.K <= 0 || !p.A.ptr || !p.B.ptr || !p.C.ptr) return ST5_ERR_ARG;
+  if (const int rc = normalise_and_check(p)) return rc;
   if (p.K % 128 || (p.batch > 1) || p.asum || (p.flags & (ST5_GEMM_A_KSTRIDED | ST5_GEMM_B_KSTRIDED | ST5_GEMM_OUT_F32))) return ST5_ERR_ARG;
   if (p.A.rpb || p.B.rpb || p.A.seg || p.B.seg) return ST5_ERR_ARG;
-  if ((p.flags & ST5_GEMM_DACT) && !p.P.ptr) return ST5_ERR_ARG;
   if (!aligned(p.A.ptr, 16) || !aligned(p.B.ptr, 16) || p.A.ld % 16 || p.B.ld % 16) return ST5_ERR_ALIGN;
   if (!aligned(a_scale, 4) || !aligned(b_scale, 4) || a_scale_ld % 4 || b_scale_ld % 4) return ST5_ERR_ALIGN;
-  p.batch = 1; p.zdiv = 1;
-  auto c_ok = [&](const st5_operand& o) {
-    if (!o.ptr) return true;
-    return aligned(o.ptr, 16) && o.ld % 8 == 0 && o.bstride % 8 == 0;
-  };
-  const int c_vec_ok = c_ok(p.C) && c_ok(p.R) && c_ok(p.P) && c_ok(p.Cpre);
+  p.zdiv = 1;   // (one batch, checked above: nothing here or in the kernels looks at the batch strides)
+  const int c_vec_ok = c_class_vec_ok(p, false);
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
   const long long al = a_scale_ld, bl = b_scale_ld;
   int feat = nt_feat_of(p, c_vec_ok);
@@ -3052,31 +2996,22 @@ int gemm_mxfp8_impl(const st5_gemm_params* pp, const uint8_t* a_scale, int64_t a
   // (the phased kernel addresses operands and scales through buffer resources: 32-bit byte offsets)
   const long long lim = 1ll << 31;
   const bool small_images = (long long)p.M * p.A.ld < lim && (long long)p.N * p.B.ld < lim && (long long)p.M * al < lim && (long long)p.N * bl < lim;
+  // The masks with a kernel of their own: nt_feat_of's, and the two F_Q8 producers.  (The 128^2 family has none for F_RES: such a launch runs
+  // its run-time form.  Adding one is a change to measure, not to make in passing.)
+  typedef FeatSet<0, F_GELU | F_PRE, F_DROP | F_RES, F_DACT, F_BETA, F_RES, F_GELU | F_PRE | F_Q8, F_DACT | F_Q8> Mx8pFeats;
+  typedef FeatSet<0, F_GELU | F_PRE, F_DROP | F_RES, F_DACT, F_BETA, F_GELU | F_PRE | F_Q8, F_DACT | F_Q8> Mx8Feats;
   if (small_images && (g_mx8_tile == 2 || (g_mx8_tile == 0 && mx8_256_pays(p.M, p.N, p.K / 128, feat)))) {
-    switch (feat) {
-      case F_GELU | F_PRE | F_Q8: return launch_mx8p_as<F_GELU | F_PRE | F_Q8>(p, c_vec_ok, a_scale, al, b_scale, bl, s, mo);
-      case F_DACT | F_Q8: return launch_mx8p_as<F_DACT | F_Q8>(p, c_vec_ok, a_scale, al, b_scale, bl, s, mo);
-      case 0: return launch_mx8p_as<0>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-      case F_GELU | F_PRE: return launch_mx8p_as<F_GELU | F_PRE>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-      case F_DROP | F_RES: return launch_mx8p_as<F_DROP | F_RES>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-      case F_DACT: return launch_mx8p_as<F_DACT>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-      case F_BETA: return launch_mx8p_as<F_BETA>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-      case F_RES: return launch_mx8p_as<F_RES>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-      default: return launch_mx8p_as<-1>(p, c_vec_ok, a_scale, al, b_scale, bl, s);
-    }
+    const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
+    return with_feat(feat, Mx8pFeats(), [&](auto f) -> int {
+      return launch_lds<gemm_nt8p_mx8_kernel<decltype(f)::value, true>>(dim3(tiles, 1, 1), dim3(512), (size_t)8 * TILE_BYTES, s, p, c_vec_ok, a_scale, al,
+                                                                         b_scale, bl, mo);
+    });
   }
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
-  dim3 grid(tiles, 1, 1);
-  switch (feat) {
-    case F_GELU | F_PRE | F_Q8: return launch_mx8_as<F_GELU | F_PRE | F_Q8>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s, mo);
-    case F_DACT | F_Q8: return launch_mx8_as<F_DACT | F_Q8>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s, mo);
-    case 0: return launch_mx8_as<0>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s);
-    case F_GELU | F_PRE: return launch_mx8_as<F_GELU | F_PRE>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s);
-    case F_DROP | F_RES: return launch_mx8_as<F_DROP | F_RES>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s);
-    case F_DACT: return launch_mx8_as<F_DACT>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s);
-    case F_BETA: return launch_mx8_as<F_BETA>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s);
-    default: return launch_mx8_as<-1>(p, c_vec_ok, a_scale, al, b_scale, bl, grid, s);
-  }
+  return with_feat(feat, Mx8Feats(), [&](auto f) -> int {
+    return launch_lds<gemm_nt_mx8_kernel<decltype(f)::value>>(dim3(tiles, 1, 1), dim3(NTHREADS), (size_t)4 * TILE_BYTES, s, p, c_vec_ok, a_scale, al, b_scale,
+                                                               bl, mo);
+  });
 }
 }  // namespace
 extern "C" int st5_gemm_mxfp8(const st5_gemm_params* pp, const uint8_t* a_scale, int64_t a_scale_ld, const uint8_t* b_scale,
@@ -3120,46 +3055,14 @@ extern "C" int st5_multi_quant_mxfp8(const void* jobs, int32_t njobs, int32_t nb
   return ST5_OK;
 }
 
-#undef g_pending
-#undef g_pending_blocks
-#undef g_arena
-#undef g_arena_bytes
-#undef g_arena_used
-
 /* Deferred split-K reductions (see splitk_multi_reduce_kernel).  While enabled, outputs of split-K GEMMs are complete only
  * after st5_gemm_flush_splitk(); disabling flushes. */
 extern "C" int st5_gemm_defer_splitk(int enabled, void* stream) {
   (void)stream;
   if (!enabled && g_defer) {   // fold whatever is queued, every state on its own stream
-    for (int i = 0; i < g_ndstates; ++i) { const int rc = flush_state(&g_dstates[i]); if (rc) return rc; }
+    for (int i = 0; i < g_ndstates; ++i) { const int rc = g_dstates[i].flush(); if (rc) return rc; }
   }
   g_defer = enabled != 0;
   return ST5_OK;
 }
 extern "C" int st5_gemm_flush_splitk(void* stream) { return flush_pending(reinterpret_cast<hipStream_t>(stream)); }
-
-/* A/B switch for the LDS-DMA NT kernel (tools/bench_kernels.py uses it for within-process comparisons). */
-extern "C" int st5_gemm_set_glds(int enabled) { g_use_glds = enabled != 0; return ST5_OK; }
-/* NT block tile: 0 = per-problem choice (default), 1 = 128x128 always, 2 = 256x256 always (A/B measurements). */
-/* Block count the split-K choice of the fp32-output (weight-gradient) GEMMs aims for (default 384 = 1.5 per CU). */
-extern "C" int st5_gemm_set_splitk_target(int blocks) { if (blocks < 1 || blocks > 4096) return ST5_ERR_ARG; g_splitk_target = blocks; return ST5_OK; }
-/* 128^2 NT kernel, grids of more than one block per CU: 5 = ring of five 16 KB operand slots (default), 4 = two whole stages. */
-extern "C" int st5_gemm_set_nt_slots(int slots) {
-  if (slots != 4 && slots != 5) return ST5_ERR_ARG;
-  g_nt_slots5 = slots == 5; return ST5_OK;
-}
-/* 128^2 NT kernel: grids of at most `max_blocks` blocks run with an `nbuf`-stage operand ring (2 = off, 3, 4). */
-extern "C" int st5_gemm_set_deep_ring(int max_blocks, int nbuf) {
-  if (max_blocks < 0 || nbuf < 2 || nbuf > 4) return ST5_ERR_ARG;
-  g_deep_blocks = max_blocks; g_deep_nbuf = nbuf; return ST5_OK;
-}
-/* Weight-gradient (TN) GEMMs without row split / segments: 0 (default) = always the 128^2 LDS-DMA kernel; 1 = phased 256^2 kernel,
- * 2 = the same without the stagger of the two m-halves (A/B measurements; the header documents the same default). */
-extern "C" int st5_gemm_set_tn_phased(int mode) { if (mode < 0 || mode > 2) return ST5_ERR_ARG; g_tn8p = mode; return ST5_OK; }
-extern "C" int st5_gemm_set_nt_tile(int mode) { if (mode < 0 || mode > 5) return ST5_ERR_ARG; g_nt_tile = mode; return ST5_OK; }
-/* MX-fp8 NT block tile: 0 = per-problem choice (default), 1 = 128x128 always, 2 = phased 256x256 always (A/B measurements, tests). */
-extern "C" int st5_gemm_set_mx8_tile(int mode) { if (mode < 0 || mode > 2) return ST5_ERR_ARG; g_mx8_tile = mode; return ST5_OK; }
-/* (A/B) k-tiles of 128 an epilogue-heavy fp8 GEMM needs before the per-problem choice takes the phased 256x256 kernel; default 16, 0 = always. */
-extern "C" int st5_gemm_set_mx8_heavy_nk(int nk) { if (nk < 0) return ST5_ERR_ARG; g_mx8_heavy_nk = nk; return ST5_OK; }
-extern "C" int st5_gemm_set_nt_longk(int tiles, int nk) { if (tiles < 0 || nk < 1) return ST5_ERR_ARG; g_nt_longk_tiles = tiles; g_nt_longk_nk = nk; return ST5_OK; }
-extern "C" int st5_gemm_set_m64_max_tiles(int tiles) { if (tiles < 0) return ST5_ERR_ARG; g_m64_max_tiles = tiles; return ST5_OK; }
