@@ -741,6 +741,40 @@ int st5_beam_cross_attn(const void* q, int64_t q_ld, const void* kv, int64_t kv_
                         int32_t n_sent, int32_t n_live, int32_t beam, int32_t S, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld,
                         float* probs, int64_t p_row, int64_t p_head, float* ws, int dtype, void* stream);
 
+/* ---- the beam step on the device (csrc/beam_step.hip; SequenceGenerator(decode="device" / "graph"), sequence_generator.py:340-468 and
+ * finalize_hypos :499-543 of this project's generator) ----
+ * State, rows = n_sent * beam hypothesis rows, sentence s owns rows s*beam .. s*beam + beam - 1, never shrinks:
+ *   counter int32[1]: the step (= input positions consumed so far);  tok int32 [rows][Tmax] / score fp32 [rows][Tmax] in SLOT layout:
+ *   tok[r][j] = the token row r fed at position j (tok[.][0] = bos), score[r][j] = the cumulative score of the hypothesis that token
+ *   closed (score[.][0] = 0); a hypothesis's history is read through the ancestry table, tokens[r][j] = tok[anc[r][j]][j];
+ *   ignore uint8 [rows] (the generator's cands_to_ignore, by rank);  parent int32 [rows]: the row each continuing row came from;
+ *   records: rec_tok int32 / rec_pos fp32 [rows][rec_ld] (hypothesis h of sentence s in row s*beam + h: tokens without bos, with the
+ *   closing eos; per-position scores), rec_score fp32 [rows], rec_len int32 [rows], n_hyp int32 [n_sent], sent_done int32 [n_sent],
+ *   n_finished int32 [1] (sentences finished, for the host to poll), ticket uint32 [1] (zero; the workgroups' arrival count).
+ * st5_beam_step for step = *counter: log_softmax(logits / temperature) in fp32, the rules (eos -inf below min_len, NaN -> -inf, pad
+ *   -inf, unk -= unk_penalty, never[c] != 0 -> -inf, at step >= max_len all but eos -inf; written to lprobs_out when given), top
+ *   2 * beam of lprobs + score[.][step] per sentence (step 0: beam row 0 only) with the TIE RULE: higher score first, among equal
+ *   scores (-inf included) the lower flat index beam_row * V + token; EOS / continuation / cands_to_ignore logic of the generator;
+ *   finished hypotheses appended to the record while the sentence has fewer than `beam` and is not finished (score divided by
+ *   len_div[step] when len_div is given: the host's fp32 table of (step + 1) ** len_penalty); a sentence is finished at `beam`
+ *   hypotheses or at step == max_len; continuing rows get tok / score at position step + 1, parent and ignore (not at step ==
+ *   max_len); the counter advances.  Nothing is written once the counter is past max_len.
+ *   beam <= 32 and V - 1 >= 2 * beam, Tmax >= max_len + 1, rec_ld >= max_len + 1, else ST5_ERR_ARG.
+ * st5_beam_reorder_dev, launched behind st5_beam_step: anc[r][j] = anc[parent[r]][j] for j < *counter, in place (parents lie inside
+ *   the row's sentence; a parent outside gives -1); nothing when *counter > max_len.
+ * st5_beam_embed_step: y[r] = emb_scale * table[tok[r][t]] + pos[clamp(t + pos_off)], t = clamp(*counter, 0, Tmax - 1): the text
+ *   decoder pre-net's newest row (a token outside [0, V) gives NaN). */
+int st5_beam_step(const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_sent, int32_t beam, int32_t V,
+                  float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax, uint8_t* ignore,
+                  int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score, int32_t* rec_len, int32_t* n_hyp,
+                  int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter, const uint8_t* never, const float* len_div,
+                  int32_t pad, int32_t unk, int32_t eos, float unk_penalty, int32_t min_len, int32_t max_len, void* stream);
+int st5_beam_reorder_dev(int32_t* anc, int64_t anc_ld, const int32_t* parent, int32_t n_sent, int32_t beam, int32_t Tmax,
+                         const int32_t* counter, int32_t max_len, void* stream);
+int st5_beam_embed_step(const float* table, int32_t V, const int32_t* tok, int32_t Tmax, const int32_t* counter, const float* pos,
+                        int32_t pos_rows, int32_t pos_off, float emb_scale, void* y, int64_t y_ld, int32_t rows, int32_t cols, int dtype,
+                        void* stream);
+
 /* Skinny-M GEMM of the decode loops (csrc/decode_gemm.hip): out[m, n] = epilogue(sum_k x[m, k] * w[n, k] + bias[n]) for 1 <= M <= 32,
  * w in nn.Linear layout [N, K] (stacked weights are one [sum N_i, K] matrix), x / w / res in `dtype`, fp32 accumulation.  Weight-streaming:
  * every weight byte is read once; row m of out depends on row m of x only (same bits for any M and any other rows); the reduction order

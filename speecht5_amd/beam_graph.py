@@ -1,0 +1,247 @@
+"""ASR beam search with the step index on the device (SequenceGenerator(decode="device")) and replayed from a HIP graph
+(decode="graph"), on the pattern of tts_graph.py.
+
+One step is a fixed sequence of kernel launches on caller-owned buffers: the text decoder pre-net's newest row
+(st5_beam_embed_step), the decoder layers over the slot state (TransformerDecoder.beam_slots_device_step: every GEMM on the
+weight-streaming skinny-M kernel, the self-attention K|V written into slot `counter` through that kernel's device-side output
+offset), the optional final LayerNorm, the tied output projection with fp32 output, the beam step (st5_beam_step: log-softmax, rules,
+candidates, EOS logic, finalisation into per-sentence records, the next tokens; it advances the counter) and the in-place ancestry
+reorder (st5_beam_reorder_dev).  Every launch reads ONE int32 counter in device memory.  Nothing in the step depends on a host
+value, allocates, or builds a weight image, so the same sequence is enqueued kernel by kernel ("device") or captured once and
+replayed ("graph").  Finished sentences are NOT removed from the batch: their rows keep running and their records are frozen.
+
+The position of the newest token is a function of the step alone, counter + padding_idx + 1: without forced prefixes no hypothesis
+contains `pad` (its log-probability is -inf at every step; `prefix_tokens` is refused), which is what SinusoidalPositionalEmbedding
+counts.
+
+The captured step has no forked stream, no parallel branch and no allocation; st5_gemm (per-stream split-K tables) is not part of
+it; every buffer the graph has baked in belongs to the BeamDeviceDecode object, which outlives the graph.
+
+`attention` of the returned hypotheses is an empty tensor in these modes: no probability record is kept."""
+import gc
+
+import torch
+
+from . import functional as Fn
+from . import hip
+from .tts_graph import GRAPH_WARMUP_STEPS, decode_stream, replay_schedule
+
+DECODE_MODES = ("device", "graph")
+
+
+def check_generator(gen):
+    """ValueError naming the option of SequenceGenerator `gen` that the device-stepped modes do not cover (asked at construction)."""
+    mode = gen.decode
+    if gen.model.models_size != 1:
+        raise ValueError(f"decode={mode!r}: more than one model ({gen.model.models_size}) is not supported; use decode='slots'")
+    if gen.ctc_weight > 0:
+        raise ValueError(f"decode={mode!r}: ctc_weight > 0 is not supported (the CTC prefix scorer reads host values per step); "
+                         f"use decode='slots'")
+    if gen.lm_model is not None:
+        raise ValueError(f"decode={mode!r}: an LM (lm_model) is not supported; use decode='slots'")
+    if gen.repeat_ngram_blocker is not None:
+        raise ValueError(f"decode={mode!r}: no_repeat_ngram_size > 0 is not supported; use decode='slots'")
+    if gen.match_source_len:
+        raise ValueError(f"decode={mode!r}: match_source_len is not supported; use decode='slots'")
+    if gen.custom_search:
+        raise ValueError(f"decode={mode!r}: a custom search_strategy is not supported (the device beam step is fairseq's BeamSearch)")
+    m = gen.model.models[0]
+    dec = getattr(m, "decoder", None)
+    if not hasattr(dec, "beam_slots_device_step") or not hasattr(m, "text_decoder_prenet") or not hasattr(m, "text_decoder_postnet"):
+        raise ValueError(f"decode={mode!r} needs a SpeechT5 text decoder with a slot API; {type(m).__name__} has none")
+    dec.check_beam_slots()
+    if any(l.encoder_attn is None for l in dec.layers):
+        raise ValueError(f"decode={mode!r}: a decoder layer has no encoder attention")
+    Fn.beam_step_check(gen.beam_size, gen.vocab_size)
+
+
+def never_mask(gen, device):
+    """uint8 [V]: the symbols no hypothesis may contain (SequenceGenerator._never), built once per call."""
+    never = torch.zeros(gen.vocab_size, dtype=torch.uint8)
+    never[gen.blank] = 1
+    if gen.mask != gen.unk:
+        never[gen.mask] = 1
+    if gen.mask_idxs.numel():
+        never[gen.mask_idxs] = 1
+    return never.to(device)
+
+
+class BeamDeviceDecode:
+    """Buffers and launch sequence of one generate() call's decode steps."""
+
+    def __init__(self, gen, model, encoder_out, n_sent, max_len, bos):
+        beam, V = gen.beam_size, gen.vocab_size
+        dec, pre, post = model.decoder, model.text_decoder_prenet, model.text_decoder_postnet
+        st = dec.init_beam_slots(n_sent, beam, max_len + 2, encoder_out)
+        dev, dtype = st.bufs[0].device, Fn.compute_dtype()
+        rows, C = st.rows, pre.embed_dim
+        self.slots, self.gen, self.n_sent, self.max_len = st, gen, n_sent, max_len
+        self.bs = Fn.BeamStepState(n_sent, beam, max_len, bos, dev, anc=st.bufs[0])
+        bs = self.bs
+        self.never = never_mask(gen, dev)
+        self.len_div = Fn.beam_len_div(max_len, gen.len_penalty, dev) if gen.normalize_scores else None
+        self.host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        self.event = torch.cuda.Event()
+        new = lambda *shape, dt=dtype: torch.empty(*shape, dtype=dt, device=dev)   # noqa: E731
+        stats = new(2 * rows, dt=torch.float32)
+        weights = []     # (every compute-dtype weight image of the step: held here, so the weight cache cannot drop one mid-call)
+        ops = []         # the step: zero-argument launches in order
+        shapes = []      # (N, K) of every skinny product, for the shared workspace
+
+        def lin(x, ws_, bs_, out, **epi):
+            w = Fn.fused_weight(list(ws_), dtype)
+            weights.append(w)
+            b = None if any(b is None for b in bs_) else Fn.fused_bias(list(bs_))
+            shapes.append(tuple(w.shape))
+            ops.append(lambda: Fn.linear_skinny(x, w, b, out=out, ws=self.ws, **epi))
+            return out
+
+        def norm(ln, x, y):
+            ops.append(lambda: Fn.layer_norm_into(x, ln.weight, ln.bias, ln.eps, y, stats))
+            return y
+
+        # pre-net: embed_scale * E[token] + pos[counter + padding_idx + 1] (see the module docstring for why the step decides it)
+        table = pre.embed_tokens.weight.detach()
+        pos = pre.embed_positions.table(max_len + 2 + pre.padding_idx + 2, dev)
+        x = new(rows, C)
+        ops.append(lambda x=x: Fn.beam_embed_step(table, bs, pos, pre.padding_idx + 1, pre.embed_scale, x))
+        x = dec.beam_slots_device_step(st, bs.counter, x, lin, norm, new, ops)
+        # tied output projection, fp32 out (no cast kernel), then the beam step and the ancestry reorder
+        proj = post.output_projection
+        self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
+        ops.append(lambda: Fn.beam_step(self.logits, V, bs, self.never, self.len_div, temperature=gen.temperature, pad=gen.pad,
+                                        unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len))
+        ops.append(lambda: Fn.beam_reorder_dev(bs))
+        nbytes = max(int(hip.lib().st5_gemm_skinny_ws_bytes(N, K)) for N, K in shapes)
+        self.ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+        self.ops, self.weights = ops, weights
+
+    def buffer_ptrs(self):
+        """Data pointers of what must never move during a call: slot K/V, encoder-side K|V, the hypothesis records."""
+        st = self.slots
+        return tuple(t.data_ptr() for t in st.kv) + tuple(kv.data_ptr() for kv, _ in st.xkv) + (self.bs.records.data_ptr(),
+                                                                                                  st.bufs[0].data_ptr())
+
+    def step(self):
+        for op in self.ops:
+            op()
+
+    def poll(self):
+        """Sentences finished after the steps enqueued so far: one pinned non-blocking copy and an event."""
+        self.host.copy_(self.bs.n_finished, non_blocking=True)
+        self.event.record()
+        self.event.synchronize()
+        return int(self.host[0])
+
+    def run(self, mode, poll_steps, stats):
+        cap = self.max_len + 1                    # steps 0 .. max_len
+        graph = None
+        try:
+            for _first, n_eager, n_replay, poll in replay_schedule(cap, poll_steps, GRAPH_WARMUP_STEPS if mode == "graph" else cap):
+                if n_replay and graph is None:
+                    for _ in range(n_eager):        # (the warm-up steps in front of the capture)
+                        self.step()
+                        stats["device_steps"] += 1
+                    n_eager = 0
+                    graph = self._capture()
+                for _ in range(n_eager):
+                    self.step()
+                    stats["device_steps"] += 1
+                for _ in range(n_replay):
+                    graph.replay()
+                    stats["graph_replays"] += 1
+                if poll:
+                    stats["polls"] += 1
+                    if self.poll() == self.n_sent:
+                        break
+        finally:
+            if graph is not None:
+                # released here, with nothing in flight: a CUDAGraph must never be destroyed inside a later capture
+                torch.cuda.current_stream().synchronize()
+                graph.reset()
+                del graph
+
+    def _capture(self):
+        stream = torch.cuda.current_stream()
+        stream.synchronize()
+        # A graph object freed by the cyclic collector DURING a capture aborts the process.  The collector is switched off for the
+        # capture's duration instead of being run in front of it: a full gc.collect() is 26 ... 32 ms per call beside a Base model, the
+        # capture itself 1 ... 2 ms.
+        gc_was_on = gc.isenabled()
+        gc.disable()
+        try:
+            graph = torch.cuda.CUDAGraph()
+            # capture_begin / capture_end directly: the step allocates nothing, so the capture needs no memory pool of its own.  The
+            # capture ENQUEUES nothing: the captured step runs for the first time at its first replay.
+            graph.capture_begin(capture_error_mode="thread_local")
+            try:
+                self.step()
+            except BaseException as first:
+                try:                   # the capture is invalid by now and ending it may fail in turn: the step's error is the cause
+                    graph.capture_end()
+                except Exception:
+                    pass
+                raise first
+            graph.capture_end()
+        finally:
+            if gc_was_on:
+                gc.enable()
+        return graph
+
+    def finalized(self):
+        """generate()'s return value from ONE device-to-host read of the records: per sentence the hypotheses best first."""
+        bs, beam = self.bs, self.bs.beam
+        _, _, score, length, n_hyp, _ = bs.unpack_records(bs.records.cpu())
+        out = []
+        for s in range(self.n_sent):
+            hyps = []
+            for k in range(int(n_hyp[s])):
+                h = s * beam + k
+                n = int(length[h])
+                hyps.append({"tokens": bs.rec_tok[h, :n].to(torch.int64), "score": bs.rec_score[h].clone(),
+                             "attention": torch.empty(0), "alignment": torch.empty(0), "positional_scores": bs.rec_pos[h, :n].clone()})
+            order = torch.sort(score[s * beam: s * beam + len(hyps)], descending=True)[1]
+            out.append([hyps[i] for i in order])
+        return out
+
+
+def generate(gen, sample, prefix_tokens=None, constraints=None, bos_token=None):
+    """SequenceGenerator._generate in "device" / "graph" mode."""
+    mode = gen.decode
+    assert mode in DECODE_MODES
+    if prefix_tokens is not None:
+        raise ValueError(f"decode={mode!r}: prefix_tokens are not supported (the newest position would depend on the prefix's pads); "
+                         f"use decode='slots'")
+    if constraints is not None:
+        raise ValueError(f"decode={mode!r}: constraints are not supported")
+    check_generator(gen)          # (the generator's attributes may have changed since construction)
+    net_input = sample["net_input"]
+    src_tokens, _ = gen._source_lengths(net_input)
+    n_sent, src_len = src_tokens.size()[:2]
+    max_len = min(int(gen.max_len_a * src_len + gen.max_len_b), gen.max_len - 1)
+    assert gen.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
+    model = gen.model.models[0]
+    encoder_outs = gen.model.forward_encoder(net_input, exact_rows=True) if gen.exact_rows else gen.model.forward_encoder(net_input)
+    device = src_tokens.device
+    stats = {"polls": 0, "device_steps": 0, "graph_replays": 0}
+    cur = torch.cuda.current_stream(device)
+    # "graph" never runs on the legacy NULL stream (it cannot capture); the caller's stream is ordered in front of the loop and behind it
+    side = decode_stream(model, device) if mode == "graph" else cur
+    if side != cur:
+        side.wait_stream(cur)
+    with torch.cuda.stream(side):
+        st = BeamDeviceDecode(gen, model, encoder_outs[0], n_sent, max_len, gen.eos if bos_token is None else bos_token)
+        first = st.buffer_ptrs()
+        st.run(mode, gen.BEAM_POLL_STEPS, stats)
+        out = st.finalized()
+        last = st.buffer_ptrs()
+    if side != cur:
+        cur.wait_stream(side)
+        for hyps in out:
+            for h in hyps:
+                for t in (h["tokens"], h["score"], h["positional_scores"]):
+                    t.record_stream(cur)
+    gen.beam_decode_mode = mode
+    gen.beam_polls, gen.beam_device_steps, gen.beam_graph_replays = stats["polls"], stats["device_steps"], stats["graph_replays"]
+    gen.beam_buffer_ptrs = (first, last)
+    return out

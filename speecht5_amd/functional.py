@@ -3389,11 +3389,12 @@ def beam_cross_attn_ws(rows, S, H, hd, device):
     return torch.empty((n + 3) // 4, dtype=torch.float32, device=device) if n else None
 
 
-def beam_cross_attn(q, kv, k_off, sent, n_sent, beam, S, H, hd, kpm=None, probs=None, ws=None):
+def beam_cross_attn(q, kv, k_off, sent, n_sent, beam, S, H, hd, kpm=None, probs=None, ws=None, ctx=None):
     """q [n_live * beam, >= C] (compute dtype, row stride q.stride(0)); kv [n_sent * S, kv_ld] rows holding this layer's K at column
     k_off and V at k_off + C, once per sentence; sent int32 [n_live]: row r reads the block of sentence sent[r // beam]; kpm uint8
     [n_sent, S] (1 = padded key) or None.  probs: None, or (fp32 tensor whose first element is row 0 / head 0 / key 0 of the record,
-    row stride, head stride).  Returns ctx [n_live * beam, C]."""
+    row stride, head stride).  Returns ctx [n_live * beam, C] (the caller's `ctx` when given: nothing is allocated then, provided ws
+    is large enough)."""
     rows = q.shape[0]
     n_live = sent.numel()
     C = H * hd
@@ -3404,9 +3405,11 @@ def beam_cross_attn(q, kv, k_off, sent, n_sent, beam, S, H, hd, kpm=None, probs=
         ws = beam_cross_attn_ws(rows, S, H, hd, q.device)
     p, p_row, p_head = probs if probs is not None else (None, 0, 0)
     assert p is None or p.dtype == torch.float32
-    ctx = torch.empty(rows, C, dtype=q.dtype, device=q.device)
+    if ctx is None:
+        ctx = torch.empty(rows, C, dtype=q.dtype, device=q.device)
+    assert ctx.dtype == q.dtype and ctx.shape == (rows, C) and ctx.stride(1) == 1
     hip.check(hip.lib().st5_beam_cross_attn(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), int(k_off), hip.ptr(kpm),
-                                            sent.data_ptr(), n_sent, n_live, beam, S, H, hd, ctx.data_ptr(), C, hip.ptr(p), p_row, p_head,
+                                            sent.data_ptr(), n_sent, n_live, beam, S, H, hd, ctx.data_ptr(), ctx.stride(0), hip.ptr(p), p_row, p_head,
                                             hip.ptr(ws), _dt(q), hip.stream()), "st5_beam_cross_attn")
     return ctx
 
@@ -3534,6 +3537,105 @@ def layer_norm_into(x, weight, bias, eps, y, stats):
     assert x.is_contiguous() and y.is_contiguous() and y.shape == x.shape and stats.numel() >= 2 * rows
     hip.check(hip.lib().st5_layernorm_fwd(x.data_ptr(), weight.data_ptr(), bias.data_ptr(), y.data_ptr(), stats.data_ptr(),
                                           stats.data_ptr() + 4 * rows, rows, cols, float(eps), _dt(x), hip.stream()), "st5_layernorm_fwd")
+    return y
+
+
+# -------------------------------------------------------------------------------------------------
+# The beam step on the device (csrc/beam_step.hip): what SequenceGenerator(decode="device" / "graph") launches between the output
+# projection and the next decode step.  Inference only, no autograd; nothing here allocates once the state exists.
+# -------------------------------------------------------------------------------------------------
+BEAM_STEP_MAX_BEAM = 32
+
+
+def beam_step_check(beam, V):
+    """ValueError naming what st5_beam_step does not cover: more than 32 beams, or a dictionary so small that the generator's
+    k = min(2 * beam, V - 1) would no longer be 2 * beam."""
+    if beam > BEAM_STEP_MAX_BEAM:
+        raise ValueError(f"beam_size {beam} > {BEAM_STEP_MAX_BEAM}: the device beam step keeps one sentence's rows in one workgroup")
+    if V - 1 < 2 * beam:
+        raise ValueError(f"beam_size {beam} with a dictionary of {V}: the device beam step takes 2 * beam candidates and needs "
+                         f"V - 1 >= 2 * beam")
+
+
+def beam_len_div(max_len, len_penalty, device):
+    """fp32 [max_len + 1]: (step + 1) ** len_penalty, what a hypothesis that ends at `step` has its score divided by."""
+    return torch.tensor([float(t + 1) ** float(len_penalty) for t in range(max_len + 1)], dtype=torch.float32, device=device)
+
+
+class BeamStepState:
+    """Device state of st5_beam_step for n_sent sentences x beam rows and steps 0 .. max_len (include/speecht5_hip.h).  `anc` is the
+    slot cache's ancestry table [rows, Tmax] (identity at the start), shared with the decoder's self-attention."""
+
+    def __init__(self, n_sent, beam, max_len, bos, device, anc=None):
+        rows, Tmax = n_sent * beam, max_len + 2
+        i32 = dict(dtype=torch.int32, device=device)
+        self.n_sent, self.beam, self.max_len, self.Tmax, self.rows = n_sent, beam, max_len, Tmax, rows
+        self.counter = torch.zeros(1, **i32)
+        self.tok = torch.zeros(rows, Tmax, **i32)
+        self.tok[:, 0] = int(bos)
+        self.score = torch.zeros(rows, Tmax, dtype=torch.float32, device=device)
+        self.anc = anc if anc is not None else torch.arange(rows, **i32).unsqueeze(1).expand(rows, Tmax).contiguous()
+        assert self.anc.dtype == torch.int32 and self.anc.shape == (rows, Tmax) and self.anc.stride(1) == 1
+        self.ignore = torch.zeros(rows, dtype=torch.uint8, device=device)
+        self.parent = torch.arange(rows, **i32)
+        # the records live in ONE buffer, so that the call's end is one device-to-host copy (unpack_records)
+        L = max_len + 1
+        self.records = torch.zeros(2 * rows * L + 2 * rows + 2 * n_sent, **i32)
+        cut = self._cuts()
+        self.rec_tok = self.records[cut[0]:cut[1]].view(rows, L)
+        self.rec_pos = self.records[cut[1]:cut[2]].view(torch.float32).view(rows, L)
+        self.rec_score = self.records[cut[2]:cut[3]].view(torch.float32)
+        self.rec_len = self.records[cut[3]:cut[4]]
+        self.n_hyp = self.records[cut[4]:cut[5]]
+        self.sent_done = self.records[cut[5]:cut[6]]
+        self.n_finished = torch.zeros(1, **i32)
+        self.ticket = torch.zeros(1, **i32)
+
+
+    def _cuts(self):
+        rows, L, n = self.rows, self.max_len + 1, self.n_sent
+        sizes = [rows * L, rows * L, rows, rows, n, n]
+        return [sum(sizes[:i]) for i in range(len(sizes) + 1)]
+
+    def unpack_records(self, host):
+        """(rec_tok, rec_pos, rec_score, rec_len, n_hyp, sent_done) as views of `host`, a copy of self.records."""
+        cut, rows, L = self._cuts(), self.rows, self.max_len + 1
+        part = [host[cut[i]:cut[i + 1]] for i in range(6)]
+        return (part[0].view(rows, L), part[1].view(torch.float32).view(rows, L), part[2].view(torch.float32), part[3], part[4],
+                part[5])
+
+
+def beam_step(logits, V, st, never, len_div, *, temperature, pad, unk, eos, unk_penalty, min_len, lprobs=None):
+    """One st5_beam_step on state `st` (BeamStepState): logits fp32 [rows, >= V] (row stride logits.stride(0)); never uint8 [V];
+    len_div = beam_len_div(...) or None (scores are not normalised); lprobs: fp32 [rows, >= V] that receives the ruled
+    log-probabilities, or None."""
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == st.rows and logits.shape[1] >= V
+    assert never.dtype == torch.uint8 and never.is_contiguous() and never.numel() == V
+    assert len_div is None or (len_div.dtype == torch.float32 and len_div.is_contiguous() and len_div.numel() >= st.max_len + 1)
+    assert lprobs is None or (lprobs.dtype == torch.float32 and lprobs.stride(1) == 1 and lprobs.shape[0] == st.rows and lprobs.shape[1] >= V)
+    hip.check(hip.lib().st5_beam_step(logits.data_ptr(), logits.stride(0), hip.ptr(lprobs), 0 if lprobs is None else lprobs.stride(0),
+                                      st.n_sent, st.beam, int(V), float(temperature), st.tok.data_ptr(), st.score.data_ptr(),
+                                      st.anc.data_ptr(), st.anc.stride(0), st.Tmax, st.ignore.data_ptr(), st.parent.data_ptr(),
+                                      st.rec_tok.data_ptr(), st.rec_pos.data_ptr(), st.rec_tok.stride(0), st.rec_score.data_ptr(),
+                                      st.rec_len.data_ptr(), st.n_hyp.data_ptr(), st.sent_done.data_ptr(), st.n_finished.data_ptr(),
+                                      st.ticket.data_ptr(), st.counter.data_ptr(), never.data_ptr(), hip.ptr(len_div), int(pad), int(unk),
+                                      int(eos), float(unk_penalty), int(min_len), st.max_len, hip.stream()), "st5_beam_step")
+
+
+def beam_reorder_dev(st):
+    """The ancestry reorder behind beam_step, in place: st.anc[r, j] = st.anc[st.parent[r], j] for j < counter."""
+    hip.check(hip.lib().st5_beam_reorder_dev(st.anc.data_ptr(), st.anc.stride(0), st.parent.data_ptr(), st.n_sent, st.beam, st.Tmax,
+                                             st.counter.data_ptr(), st.max_len, hip.stream()), "st5_beam_reorder_dev")
+
+
+def beam_embed_step(table, st, pos, pos_off, emb_scale, y):
+    """y[r] = emb_scale * table[st.tok[r, counter]] + pos[counter + pos_off] (fp32 tables, y [rows, C] in the compute dtype)."""
+    V, C = table.shape
+    assert table.dtype == torch.float32 and table.is_contiguous() and pos.dtype == torch.float32 and pos.is_contiguous()
+    assert pos.shape[1] == C and y.shape == (st.rows, C) and y.stride(1) == 1
+    hip.check(hip.lib().st5_beam_embed_step(table.data_ptr(), V, st.tok.data_ptr(), st.Tmax, st.counter.data_ptr(), pos.data_ptr(),
+                                            pos.shape[0], int(pos_off), float(emb_scale), y.data_ptr(), y.stride(0), st.rows, C, _dt(y),
+                                            hip.stream()), "st5_beam_embed_step")
     return y
 
 

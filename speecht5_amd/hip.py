@@ -243,6 +243,12 @@ _SIGS = {
     "st5_beam_cross_attn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "st5_beam_cross_attn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),
+    "st5_beam_step": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_int64,
+                              c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                              c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p]),
+    "st5_beam_reorder_dev": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "st5_beam_embed_step": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int64,
+                                    c_int32, c_int32, c_int, c_void_p]),
     "st5_angular_margin_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
     "st5_angular_margin_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float,
                                        c_float, c_void_p]),

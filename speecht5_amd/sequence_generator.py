@@ -172,6 +172,8 @@ def hip_fuse_lm(lprobs, logits, lm_weight):
 
 
 class SequenceGenerator(nn.Module):
+    BEAM_POLL_STEPS = 8     # decode="device" / "graph": steps between two host reads of the finished-sentence count
+
     def __init__(self, models, tgt_dict, beam_size=1, max_len_a=0, max_len_b=200, max_len=0, min_len=1, normalize_scores=True,
                  len_penalty=1.0, unk_penalty=0.0, temperature=1.0, match_source_len=False, no_repeat_ngram_size=0,
                  search_strategy=None, eos=None, symbols_to_strip_from_output=None, lm_model=None, lm_weight=1.0, ctc_weight=0.0,
@@ -183,11 +185,16 @@ class SequenceGenerator(nn.Module):
         `decode`: "concat" (the default: the reference's incremental state, keys / values concatenated per step, encoder output
         replicated by beam and re-ordered every step) or "slots": every model decodes over a slot cache with an ancestry table and
         keeps the encoder side once per sentence (TransformerDecoder.init_beam_slots, csrc/beam_decode.hip); a beam reorder is one
-        gather of an int32 table.  A model whose decoder has no slot API is refused (ValueError), there is no fallback."""
+        gather of an int32 table.  A model whose decoder has no slot API is refused (ValueError), there is no fallback.
+        "device" / "graph" (beam_graph.py): the slot cache with the whole step on the device -- the beam step is one HIP kernel
+        (csrc/beam_step.hip), the step index a device counter, the host polls the finished-sentence count every BEAM_POLL_STEPS
+        steps; "graph" replays the step from a HIP graph.  One model, no CTC / LM / prefix / constraints / n-gram blocking /
+        match_source_len / custom search (ValueError naming the option); `attention` of the hypotheses is an empty tensor (no
+        probability record is kept); ties between candidates go to the lower beam_row * V + token."""
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)
-        if decode not in ("concat", "slots"):
-            raise ValueError(f"decode={decode!r}: expected 'concat' or 'slots'")
+        if decode not in ("concat", "slots", "device", "graph"):
+            raise ValueError(f"decode={decode!r}: expected 'concat', 'slots', 'device' or 'graph'")
         if decode == "slots":
             for m in self.model.models:
                 if not hasattr(getattr(m, "decoder", None), "init_beam_slots"):
@@ -219,11 +226,15 @@ class SequenceGenerator(nn.Module):
         self.repeat_ngram_blocker = NGramRepeatBlock(no_repeat_ngram_size) if no_repeat_ngram_size > 0 else None
         assert temperature > 0, "--temperature must be greater than 0"
         self.search = BeamSearch(tgt_dict) if search_strategy is None else search_strategy
+        self.custom_search = search_strategy is not None
         self.should_set_src_lengths = getattr(self.search, "needs_src_lengths", False)
         self.model.eval()
         self.lm_model, self.lm_weight, self.ctc_weight = lm_model, lm_weight, ctc_weight
         if self.lm_model is not None:
             self.lm_model.eval()
+        if decode in ("device", "graph"):
+            from . import beam_graph
+            beam_graph.check_generator(self)     # (every option these modes do not cover: ValueError here, there is no fallback)
 
     def cuda(self):
         self.model.cuda()
@@ -261,6 +272,9 @@ class SequenceGenerator(nn.Module):
 
     def _generate(self, sample, prefix_tokens: Optional[Tensor] = None, constraints: Optional[Tensor] = None,
                   bos_token: Optional[int] = None):
+        if self.decode in ("device", "graph"):
+            from . import beam_graph
+            return beam_graph.generate(self, sample, prefix_tokens, constraints, bos_token)
         net_input = sample["net_input"]
         incremental_states = [{} for _ in range(self.model.models_size)]
         src_tokens, src_lengths = self._source_lengths(net_input)
