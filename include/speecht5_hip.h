@@ -373,6 +373,19 @@ int st5_colsum_ws(const void* x, float* out, void* ws, int64_t rows, int32_t col
 int st5_colsum_ws_gate(const void* x, float* out, void* ws, int64_t rows, int32_t cols, int64_t ld, float scale, int32_t accumulate,
                        const float* gate, int dtype, void* stream);
 int64_t st5_colsum_ws_bytes(int64_t rows, int32_t cols);
+/* Relative-position part of the self-attention backward in one launch (bf16, head_dim 64; csrc/relpos_bwd.hip).  dqp [B*H, T, nb] are the
+ * bucket gradients the dkv kernel wrote; q / dq point at head 0 of batch 0 of a [B*T, ld] buffer (head h at column 64 h); pe [nb, 64].
+ *   dq[bh][t][:]    = bf16(alpha * (dqp[bh][t][:] . pe) + dq[bh][t][:])      (read and written)
+ *   part[bh][b][:]  = alpha * sum_t dqp[bh][t][b] * q[bh][t][:]              (fp32 [B*H, nb, 64]; part == NULL: the dq half alone)
+ * Both are the bytes st5_gemm produces for the same operands (NT with beta = 1; k-strided A and B with ST5_GEMM_OUT_F32).  Rows t >= T
+ * are neither read into the sums nor written.  nb: see st5_relpos_bwd_supported.  gate (may be NULL): the layer gate, *gate == 0 ->
+ * nothing is read, dq and part are left unwritten. */
+int st5_relpos_bwd(const void* dqp, const void* q, int64_t q_ld, const void* pe, void* dq, int64_t dq_ld, float* part, int32_t B, int32_t H,
+                   int32_t T, int32_t nb, float alpha, const float* gate, int dtype, void* stream);
+int st5_relpos_bwd_supported(int32_t nb);   /* nb a multiple of 64, at most 320 (the partial lives in accumulator registers) */
+/* dpe[c] (dtype) = sum over rows of part[r][c], in the order of st5_colsum_ws (overwrite form, scale 1) followed by st5_cast_from_f32: same
+ * bytes, one launch.  gate (may be NULL): *gate == 0 -> part is not read, dpe = exact zeros. */
+int st5_relpos_dpe_final(const float* part, void* dpe, int64_t rows, int32_t cols, const float* gate, int dtype, void* stream);
 /* out[0] (+)= scale * sum(x^2)   (features_pen, speech_encoder_prenet.py:172) */
 int st5_sumsq(const void* x, float* out, int64_t n, float scale, int32_t accumulate, int dtype, void* stream);
 /* y = a*x + b*y */

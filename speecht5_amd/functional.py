@@ -1927,6 +1927,22 @@ def set_flash_attention(enabled):
     _FLASH.enabled = bool(enabled)
 
 
+# Relative-position part of the fused attention backward: st5_relpos_bwd + st5_relpos_dpe_final (two launches) instead of
+# two batched GEMMs, the two-stage column sum and the cast (five or six).  Same bytes.  ST5_RELPOS_BWD_FUSED=0 (read once) or
+# set_relpos_bwd_fused(False) keeps the GEMM sequence: the reference of tests/test_relpos_bwd_gpu.py and the parent arm of A/B runs.
+_RELPOS = SimpleNamespace(fused=os.environ.get("ST5_RELPOS_BWD_FUSED", "1") != "0")
+
+
+def set_relpos_bwd_fused(enabled):
+    """Switch the relative-position dQ / dPE products of the fused attention backward between the one-pass kernel and the GEMM sequence."""
+    _RELPOS.fused = bool(enabled)
+
+
+def relpos_bwd_fused(nb):
+    """True when the attention backward runs the one-pass kernel for a table of nb buckets (it then needs no transposed table copy)."""
+    return _RELPOS.fused and bool(hip.lib().st5_relpos_bwd_supported(nb))
+
+
 def _can_flash(dtype, hd, want_probs):
     return _FLASH.enabled and dtype == torch.bfloat16 and hd == 64 and not want_probs
 
@@ -1984,7 +2000,7 @@ def _attn_side_raw():
 
 def _flash_bwd(dctx, ctx, lse, q, k, v, dq, dk, dv, B, H, T, S, hd, pe, want_dpe, maxrel, kpm, causal, p_drop, seed, qp=None,
                pe_t=None, dkv_live=False):
-    """Writes dq/dk/dv slices; returns dPE (fp32) or None.  dkv_live (inside a gated layer): dk / dv are read outside the layer (the shared
+    """Writes dq/dk/dv slices; returns dPE (compute dtype from the one-pass kernel, fp32 from the GEMM sequence) or None.  dkv_live (inside a gated layer): dk / dv are read outside the layer (the shared
     cross-attention gradient buffer), so a dropped layer stores zeros there; everything else it leaves unwritten -- except dPE, zeros."""
     lg = hip.gate()
     dev = dctx.device
@@ -2019,6 +2035,19 @@ def _flash_bwd(dctx, ctx, lse, q, k, v, dq, dk, dv, B, H, T, S, hd, pe, want_dpe
     if pe is None:
         return None
     dqt, dqld, dqoff = dq
+    if relpos_bwd_fused(nb):
+        # dQ += alpha * dQP . PE and the per-(batch, head) partials alpha * dQP^T . Q in one pass over dQP; then their ordered sum, cast
+        L = hip.lib()
+        part = _gout(torch.empty(BH, nb, hd, dtype=torch.float32, device=dev)) if want_dpe else None
+        hip.check(L.st5_relpos_bwd(dqp.data_ptr(), _eptr(q), qld, pe.data_ptr(), _eptr(dq), dqld, hip.ptr(part), B, H, T, nb, alpha,
+                                   lg or None, hip.BF16, hip.stream()), "st5_relpos_bwd")
+        if not want_dpe:
+            return None
+        g = _gout(torch.empty(nb, hd, dtype=dtype, device=dev))
+        # (inside a gated layer the gradient is LIVE: a dropped layer's is exact zeros)
+        hip.check(L.st5_relpos_dpe_final(part.data_ptr(), g.data_ptr(), BH, nb * hd, lg or None, hip.BF16, hip.stream()),
+                  "st5_relpos_dpe_final")
+        return g
     # dQ += alpha * dQP . PE  (NT form on the LDS-DMA kernel when the caller made the K-major copy PE^T [hd, nb])
     if pe_t is not None:
         hip.gemm(hip.operand(dqp, nb, zs0=H * T * nb, zs1=T * nb), hip.operand(pe_t, nb),
@@ -2081,7 +2110,7 @@ class SelfAttentionFunction(torch.autograd.Function):
             dpe = _flash_bwd(dctx.contiguous(), ctx, lse, (qkv, 3 * d, 0), (qkv, 3 * d, d), (qkv, 3 * d, 2 * d), (dqkv, 3 * d, 0),
                              (dqkv, 3 * d, d), (dqkv, 3 * d, 2 * d), B, H, T, T, hd, pe, pe is not None and ctx_.needs_input_grad[1],
                              maxrel, kpm, causal, p_drop, seed, qp=qp, pe_t=pe_t)
-            if dpe is not None and pe.dtype != torch.float32:
+            if dpe is not None and dpe.dtype != pe.dtype:
                 dpe = to_compute(dpe)
             return dqkv, dpe, None, None
         qkv, probs, pdrop, pe = ctx_.saved_tensors

@@ -136,6 +136,10 @@ _SIGS = {
     "st5_colsum_ws": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_float, c_int32, c_int,
                               c_void_p]),
     "st5_colsum_ws_bytes": (c_int64, [c_int64, c_int32]),
+    "st5_relpos_bwd": (c_int, [c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                               c_float, c_void_p, c_int, c_void_p]),
+    "st5_relpos_bwd_supported": (c_int, [c_int32]),
+    "st5_relpos_dpe_final": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_void_p, c_int, c_void_p]),
     "st5_sumsq": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_int32, c_int, c_void_p]),
     "st5_axpby": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_float, c_int, c_void_p]),
     "st5_select": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p]),

@@ -93,7 +93,8 @@ class MultiheadAttention(nn.Module, IncrementalState):
             pe, maxrel, pe_t = None, 0, None
             if position_bias is not None and self.has_relative_attention_bias:
                 pe, maxrel = position_bias.table, position_bias.maxlen
-                if torch.is_grad_enabled() and qkv.requires_grad:
+                # (the one-pass relative-position backward reads the table itself; only the GEMM sequence wants the K-major copy)
+                if torch.is_grad_enabled() and qkv.requires_grad and not (Fn._can_flash(qkv.dtype, hd, False) and Fn.relpos_bwd_fused(pe.shape[0])):
                     pe_t = position_bias.transposed()
             ctx = Fn.SelfAttentionFunction.apply(qkv, pe, kpm, (B, H, T, hd, maxrel, causal, p, pe_t))
         else:
