@@ -784,6 +784,42 @@ int st5_beam_step(const float* logits, int64_t ld, float* lprobs_out, int64_t lp
                   int32_t pad, int32_t unk, int32_t eos, float unk_penalty, int32_t min_len, int32_t max_len, void* stream);
 int st5_beam_reorder_dev(int32_t* anc, int64_t anc_ld, const int32_t* parent, int32_t n_sent, int32_t beam, int32_t Tmax,
                          const int32_t* counter, int32_t max_len, void* stream);
+/* st5_beam_step_logprobs: st5_beam_step on log-probabilities lp [rows][ld] instead of logits: the log-softmax is skipped (the rules'
+ *   expression is evaluated with maximum 0, log-sum 0 and temperature 1, which returns lp[r][c] itself), everything else is
+ *   st5_beam_step, the same kernel. */
+int st5_beam_step_logprobs(const float* lp, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_sent, int32_t beam, int32_t V,
+                           int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax, uint8_t* ignore, int32_t* parent,
+                           int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score, int32_t* rec_len, int32_t* n_hyp,
+                           int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter, const uint8_t* never,
+                           const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty, int32_t min_len, int32_t max_len,
+                           void* stream);
+/* ---- joint CTC / attention scoring in the device-stepped beam search (csrc/beam_ctc.hip): the rows form of the CTC prefix scorer
+ * behind the step counter of st5_beam_step.  rows = S * beam, row r belongs to sentence r / beam; x [S][Tfr][V], lens [S] as for
+ * st5_ctc_prefix_score_rows; tok [rows][tok_ld] int32 is st5_beam_step's; nc candidates per row, nc <= 1024.  Buffers: state
+ * [rows][Tfr][2], r_new [rows][Tfr][nc][2], log_psi [rows][nc], prev [rows], cs int32 [rows][nc], lp [rows][lp_ld], unknown int32 [1].
+ * Nothing is written when the counter is outside the range given below.  Launch order inside a step: candidates, score, the beam
+ * step on lp, select, st5_beam_reorder_dev.
+ * st5_beam_ctc_candidates, step = *counter in [0, max_len]: lp[r][c] = (logits[r][c] / temperature - max) - log(sum), the unruled
+ *   fp32 log-softmax with st5_beam_step's statistics; cs[r][0 .. nc) = the nc best tokens of lp[r], never[c] != 0 tokens and NaN
+ *   counted as -inf, in rank order under the TIE RULE (higher value first, among equal values the lower token).  nc <= V.
+ * st5_ctc_prefix_score_rows_dev, step = *counter in [0, max_len]: log_psi and r_new of st5_ctc_prefix_score_rows (bit for bit) for
+ *   sent[r] = r / beam, out_len = step, last[r] = tok[r][step], then lp[r][cs[r][j]] = (float)(1 - ctc_weight) * lp[r][cs[r][j]] +
+ *   (float)ctc_weight * (log_psi[r][j] - prev[r]), every operation rounded to fp32.  A candidate outside [0, V) gives log_psi NaN
+ *   and leaves lp alone.  0 <= ctc_weight <= 1.
+ * st5_ctc_select_dev, t = *counter in [1, max_len] (behind the beam step): row r continues row p = parent[r] with token tok[r][t];
+ *   state[r] = the extension's state r_new[p][.][slot] (logzero at and behind the sentence's frames), prev[r] = log_psi[p][slot],
+ *   slot = the token's position in cs[p].  A token outside cs[p]: slot 0 is gathered and *unknown = 1 (sticky), unless ignore[r] or
+ *   sent_done[r / beam] is set.  A parent outside [0, rows): logzero state, prev NaN, *unknown = 1 under the same condition. */
+int st5_beam_ctc_candidates(const float* logits, int64_t ld, int32_t rows, int32_t V, float temperature, const uint8_t* never,
+                            const int32_t* counter, int32_t max_len, float* lp, int64_t lp_ld, int32_t* cs, int32_t nc, void* stream);
+int st5_ctc_prefix_score_rows_dev(const float* x, const int32_t* lens, int32_t S, int32_t Tfr, int32_t V, int32_t blank, int32_t eos,
+                                  int32_t beam, const float* r_prev, const int32_t* tok, int32_t tok_ld, const int32_t* counter,
+                                  int32_t max_len, const int32_t* cs, int32_t nc, float* log_psi, float* r_new, const float* prev, float* lp,
+                                  int64_t lp_ld, double ctc_weight, void* stream);
+int st5_ctc_select_dev(const int32_t* lens, int32_t S, int32_t Tfr, int32_t beam, const int32_t* cs, int32_t nc, const float* log_psi,
+                       const float* r_new, const int32_t* parent, const int32_t* tok, int32_t tok_ld, const uint8_t* ignore,
+                       const int32_t* sent_done, const int32_t* counter, int32_t max_len, float* state, float* prev, int32_t* unknown,
+                       void* stream);
 int st5_beam_embed_step(const float* table, int32_t V, const int32_t* tok, int32_t Tmax, const int32_t* counter, const float* pos,
                         int32_t pos_rows, int32_t pos_off, float emb_scale, void* y, int64_t y_ld, int32_t rows, int32_t cols, int dtype,
                         void* stream);

@@ -17,6 +17,16 @@ counts.
 The captured step has no forked stream, no parallel branch and no allocation; st5_gemm (per-stream split-K tables) is not part of
 it; every buffer the graph has baked in belongs to the BeamDeviceDecode object, which outlives the graph.
 
+Joint CTC / attention scoring (ctc_weight > 0) runs in these modes with ctc_rows=True only: no sentence leaves the batch, so row r is
+scored against sentence r // beam's own posterior and frame count for the whole call.  The step then is: pre-net row, decoder layers,
+projection, st5_beam_ctc_candidates (log-probabilities and the 7 x beam best tokens of every row), st5_ctc_prefix_score_rows_dev (the
+rows scorer with out_len and the last labels read on the device, the mix (1 - w) lp + w (log psi - prev) in its epilogue), [an LM term
+would go here], st5_beam_step_logprobs (the beam step on log-probabilities), st5_ctc_select_dev (the continued rows' prefix states),
+the reorder (csrc/beam_ctc.hip; buffers: functional.BeamCtcState).  A hypothesis continued by a token outside its CTC candidates sets
+a sticky device flag (rows that are ignored or belong to a finished sentence do not); the host reads it where it reads the
+finished-sentence count and at the end, and raises _generate's KeyError then, a few steps later than the slots loop would.  An LM
+(lm_model) stays refused.
+
 `attention` of the returned hypotheses is an empty tensor in these modes: no probability record is kept."""
 import gc
 
@@ -34,9 +44,9 @@ def check_generator(gen):
     mode = gen.decode
     if gen.model.models_size != 1:
         raise ValueError(f"decode={mode!r}: more than one model ({gen.model.models_size}) is not supported; use decode='slots'")
-    if gen.ctc_weight > 0:
-        raise ValueError(f"decode={mode!r}: ctc_weight > 0 is not supported (the CTC prefix scorer reads host values per step); "
-                         f"use decode='slots'")
+    if gen.ctc_weight > 0 and not gen.ctc_rows:
+        raise ValueError(f"decode={mode!r}: ctc_weight > 0 needs ctc_rows=True (no sentence leaves the batch here, so every sentence is "
+                         f"scored against its own CTC posterior); the first-sentence scoring of ctc_rows=False is decode='slots' only")
     if gen.lm_model is not None:
         raise ValueError(f"decode={mode!r}: an LM (lm_model) is not supported; use decode='slots'")
     if gen.repeat_ngram_blocker is not None:
@@ -80,7 +90,8 @@ class BeamDeviceDecode:
         bs = self.bs
         self.never = never_mask(gen, dev)
         self.len_div = Fn.beam_len_div(max_len, gen.len_penalty, dev) if gen.normalize_scores else None
-        self.host = torch.empty(1, dtype=torch.int32, pin_memory=True)
+        self.host = torch.zeros(2, dtype=torch.int32, pin_memory=True)     # (n_finished, the CTC scorer's `unknown` flag)
+        self.ctc = self._ctc_state(gen, model, encoder_out, n_sent, dev) if gen.ctc_weight > 0 else None
         self.event = torch.cuda.Event()
         new = lambda *shape, dt=dtype: torch.empty(*shape, dtype=dt, device=dev)   # noqa: E731
         stats = new(2 * rows, dt=torch.float32)
@@ -109,28 +120,56 @@ class BeamDeviceDecode:
         # tied output projection, fp32 out (no cast kernel), then the beam step and the ancestry reorder
         proj = post.output_projection
         self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
-        ops.append(lambda: Fn.beam_step(self.logits, V, bs, self.never, self.len_div, temperature=gen.temperature, pad=gen.pad,
-                                        unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len))
+        rules = dict(temperature=gen.temperature, pad=gen.pad, unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len)
+        if self.ctc is None:
+            ops.append(lambda: Fn.beam_step(self.logits, V, bs, self.never, self.len_div, **rules))
+        else:
+            # log-probabilities and candidates, prefix scores mixed into them, [an LM term would go here], the beam step on them, the
+            # continued rows' prefix states
+            ctc = self.ctc
+            ops.append(lambda: Fn.beam_ctc_candidates(self.logits, V, bs, ctc, self.never, gen.temperature))
+            ops.append(lambda: Fn.ctc_prefix_score_rows_dev(bs, ctc))
+            ops.append(lambda: Fn.beam_step(ctc.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
+            ops.append(lambda: Fn.ctc_select_dev(bs, ctc))
         ops.append(lambda: Fn.beam_reorder_dev(bs))
         nbytes = max(int(hip.lib().st5_gemm_skinny_ws_bytes(N, K)) for N, K in shapes)
         self.ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
         self.ops, self.weights = ops, weights
 
+    def _ctc_state(self, gen, model, encoder_out, n_sent, dev):
+        """The CTC posterior and frame counts as _generate builds them for ctc_rows, and the step's CTC buffers."""
+        from .sequence_generator import CTC_SCORING_RATIO, CTCPrefixScorerRows
+        post = model.get_normalized_probs_for_ctc(encoder_out, log_probs=True).transpose(0, 1)      # B x T x V
+        nc = min(post.shape[-1] - gen.mask_idxs.numel(), int(gen.beam_size * CTC_SCORING_RATIO))
+        pm = encoder_out["encoder_padding_mask"]
+        pm = pm[0] if isinstance(pm, (list, tuple)) and len(pm) > 0 else (pm if isinstance(pm, torch.Tensor) else None)
+        frames = torch.full((n_sent,), post.size(1), dtype=torch.int32, device=dev) if pm is None or pm.numel() == 0 \
+            else (post.size(1) - pm.sum(dim=1)).to(torch.int32)
+        self.ctc_beam = nc
+        return Fn.BeamCtcState(CTCPrefixScorerRows(post, frames, gen.blank, gen.eos), self.bs, nc, gen.ctc_weight)
+
     def buffer_ptrs(self):
-        """Data pointers of what must never move during a call: slot K/V, encoder-side K|V, the hypothesis records."""
+        """Data pointers of what must never move during a call: slot K/V, encoder-side K|V, the hypothesis records, the CTC buffers."""
         st = self.slots
+        ctc = () if self.ctc is None else tuple(t.data_ptr() for t in self.ctc.buffers())
         return tuple(t.data_ptr() for t in st.kv) + tuple(kv.data_ptr() for kv, _ in st.xkv) + (self.bs.records.data_ptr(),
-                                                                                                  st.bufs[0].data_ptr())
+                                                                                                  st.bufs[0].data_ptr()) + ctc
 
     def step(self):
         for op in self.ops:
             op()
 
     def poll(self):
-        """Sentences finished after the steps enqueued so far: one pinned non-blocking copy and an event."""
-        self.host.copy_(self.bs.n_finished, non_blocking=True)
+        """Sentences finished after the steps enqueued so far: one pinned non-blocking copy (with CTC a second one, of the scorer's
+        `unknown` flag) and an event.  KeyError, _generate's, when a hypothesis was continued outside its CTC candidates."""
+        self.host[:1].copy_(self.bs.n_finished, non_blocking=True)
+        if self.ctc is not None:
+            self.host[1:].copy_(self.ctc.unknown, non_blocking=True)
         self.event.record()
         self.event.synchronize()
+        if int(self.host[1]):
+            raise KeyError("a hypothesis was extended by a token outside its CTC candidate list "
+                           f"(ctc_beam={self.ctc_beam}); its prefix state does not exist")
         return int(self.host[0])
 
     def run(self, mode, poll_steps, stats):
@@ -154,6 +193,13 @@ class BeamDeviceDecode:
                     stats["polls"] += 1
                     if self.poll() == self.n_sent:
                         break
+            else:
+                # No break: the schedule ran out, and its last group never polls (step max_len finishes every sentence, so a polled
+                # group in front of it that saw them all would have broken out).  The steps behind the last poll may have set
+                # `unknown`: read it once more.  Not an extra synchronisation of every call (a call that ends at a poll does not get
+                # here; finalized() synchronises next anyway), and not counted in stats["polls"], which counts the schedule's polls.
+                if self.ctc is not None:
+                    self.poll()
         finally:
             if graph is not None:
                 # released here, with nothing in flight: a CUDAGraph must never be destroyed inside a later capture

@@ -9,9 +9,10 @@
 //   3. the top 2 * beam of lprobs + prev over the sentence's beam * V candidates (step 0: beam row 0's V candidates), ordered by the
 //      64-bit key (monotone image of the fp32 score, ~flat index): higher score first, among equal scores (-inf included, -0 = +0) the
 //      lower flat index beam_row * V + token first.  The key is unique, so the order is total and there is no tie to break later.
-//      Selection: MSB-first radix select on the key (8 bits a pass, one LDS histogram bin per thread, stops as soon as the bucket that
-//      holds the k-th key is taken whole: after the 4 score bytes when the scores differ), one gather pass, a rank sort of the 2 * beam
-//      keys.  The score of a candidate is recomputed from the logits in every pass (V is general, a row need not fit in LDS);
+//      Selection (beam_select.h, shared with beam_ctc.hip): MSB-first radix select on the key (8 bits a pass, one LDS histogram bin
+//      per thread, stops as soon as the bucket that holds the k-th key is taken whole: after the 4 score bytes when the scores differ),
+//      one gather pass, a rank sort of the 2 * beam keys.  The score of a candidate is recomputed from the logits in every pass (V is
+//      general, a row need not fit in LDS);
 //   4. the generator's EOS logic on the sorted candidates (one thread: 2 * beam <= 64 entries): an eos candidate among the first `beam`
 //      with a finite score and a rank whose ignore flag is clear is a finished hypothesis; the first `beam` candidates that are
 //      neither finished-eos nor (rank < beam and ignored) continue, then the masked ones in rank order; the new ignore flags follow;
@@ -21,6 +22,8 @@
 //      at `beam` hypotheses or at step == max_len, and counted once in *n_finished;
 //   6. continuing row k of the sentence: tok[r][step + 1], score[r][step + 1], parent[r] (a row index of the whole launch), ignore[r];
 //      the last workgroup to finish advances the counter.
+// st5_beam_step_logprobs: the same kernel on log-probabilities (the CTC-mixed ones of beam_ctc.hip): stage 1 is skipped, mx = lse = 0
+//   and temperature 1 leave the expression of stage 2 at x[c], bit for bit.
 // st5_beam_reorder_dev: the ancestry reorder for the step the counter has just left, IN PLACE: parents lie inside the row's own
 //   sentence, so the thread that owns column j of a sentence reads its `beam` entries before it writes them.
 // st5_beam_embed_step: the text decoder pre-net's newest row, embed_scale * E[tok[r][counter]] + pos[counter + pos_off].
@@ -29,22 +32,25 @@
 #include <math.h>
 #include <stdint.h>
 #include "common.h"
+#include "beam_select.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
 
-constexpr int BS_THREADS = 256;
-constexpr int BS_WAVES = BS_THREADS / 64;
+constexpr int BS_THREADS = bsel::THREADS;
+constexpr int BS_WAVES = bsel::WAVES;
 constexpr int BS_MAX_BEAM = 32;
 constexpr int BS_MAX_K = 2 * BS_MAX_BEAM;
 
-typedef unsigned long long u64;
+using bsel::u64;
+using bsel::fkey;
+using bsel::unfkey;
 
 struct BeamStepArgs {
   const float* logits; int64_t ld;
   float* lprobs; int64_t lp_ld;
   int n_sent, beam, V, Tmax;
-  float temperature;
+  float temperature; int logprobs;      // logprobs: `logits` holds log-probabilities (stage 1 is skipped)
   int32_t* tok; float* score; const int32_t* anc; int64_t anc_ld;
   uint8_t* ignore; int32_t* parent;
   int32_t* rec_tok; float* rec_pos; int64_t rec_ld; float* rec_score; int32_t* rec_len;
@@ -66,20 +72,12 @@ __device__ __forceinline__ float bs_ruled(const BeamStepArgs& a, const float* __
   return lp;
 }
 
-// monotone 32-bit image of a score (larger = better; -0 counts as +0), and the unique 64-bit key of a candidate
-__device__ __forceinline__ uint32_t bs_fkey(float s) {
-  if (s == 0.f) s = 0.f;
-  const uint32_t u = __float_as_uint(s);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float bs_unfkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
-
 #pragma clang fp contract(off)
 __device__ __forceinline__ u64 bs_key(const BeamStepArgs& a, int64_t row0, int b, int c, const float* s_mx, const float* s_lse,
                                       const float* s_prev, int step) {
   float s = bs_ruled(a, a.logits + (row0 + b) * a.ld, c, s_mx[b], s_lse[b], step);
   if (step > 0) s = s + s_prev[b];
-  return ((u64)bs_fkey(s) << 32) | (uint32_t)(~(uint32_t)(b * a.V + c));
+  return ((u64)fkey(s) << 32) | (uint32_t)(~(uint32_t)(b * a.V + c));
 }
 
 __global__ void __launch_bounds__(BS_THREADS) beam_step_kernel(const BeamStepArgs a) {
@@ -91,27 +89,18 @@ __global__ void __launch_bounds__(BS_THREADS) beam_step_kernel(const BeamStepArg
   const int64_t row0 = (int64_t)s * beam;
 
   __shared__ float s_mx[BS_MAX_BEAM], s_lse[BS_MAX_BEAM], s_prev[BS_MAX_BEAM];
-  __shared__ unsigned s_hist[BS_THREADS], s_wtot[BS_WAVES];
-  __shared__ u64 s_sel[BS_MAX_K], s_sorted[BS_MAX_K];
-  __shared__ u64 s_prefix;
-  __shared__ unsigned s_need, s_nsel;
-  __shared__ int s_stop, s_nnew;
+  __shared__ u64 s_sorted[BS_MAX_K];
+  __shared__ int s_nnew;
   __shared__ int s_fin_parent[BS_MAX_BEAM], s_fin_slot[BS_MAX_BEAM];
   __shared__ float s_fin_score[BS_MAX_BEAM];
 
-  // ---- 1. row maximum and log-sum-exp: one wave per row in turn ----
+  // ---- 1. row maximum and log-sum-exp: one wave per row in turn (log-probability input: both are zero) ----
   for (int b = wave; b < beam; b += BS_WAVES) {
-    const float* x = a.logits + (row0 + b) * a.ld;
-    float mx = -INFINITY;
-    for (int c = lane; c < V; c += 64) mx = fmaxf(mx, x[c] / a.temperature);
-    mx = wave_max(mx);
-    double sum = 0.0;
-    for (int c = lane; c < V; c += 64) sum += (double)expf(x[c] / a.temperature - mx);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
+    float mx = 0.f, lse = 0.f;
+    if (!a.logprobs) bsel::row_stats(a.logits + (row0 + b) * a.ld, V, a.temperature, lane, mx, lse);
     if (lane == 0) {
       s_mx[b] = mx;
-      s_lse[b] = (float)log(sum);
+      s_lse[b] = lse;
       s_prev[b] = step > 0 ? a.score[(row0 + b) * Tmax + step] : 0.f;
     }
   }
@@ -124,78 +113,9 @@ __global__ void __launch_bounds__(BS_THREADS) beam_step_kernel(const BeamStepArg
       for (int c = tid; c < V; c += BS_THREADS) a.lprobs[(row0 + b) * a.lp_ld + c] = bs_ruled(a, x, c, s_mx[b], s_lse[b], step);
     }
 
-  // ---- 3. top 2 * beam by radix select on the unique key ----
-  const int nb = step == 0 ? 1 : beam;
-  const int iters = (V + BS_THREADS - 1) / BS_THREADS;
-  u64 prefix = 0;
-  unsigned need = (unsigned)K;
-  int fshift = 0;
-  for (int shift = 56; shift >= 0; shift -= 8) {
-    s_hist[tid] = 0;
-    __syncthreads();
-    for (int b = 0; b < nb; ++b)
-      for (int it = 0; it < iters; ++it) {       // (the same trip count in every lane: the wave-wide ballots below see all of them)
-        const int c = it * BS_THREADS + tid;
-        const bool valid = c < V;
-        const u64 key = valid ? bs_key(a, row0, b, c, s_mx, s_lse, s_prev, step) : 0;
-        const bool in = valid && (shift == 56 || (key >> (shift + 8)) == prefix);
-        const unsigned d = (unsigned)(key >> shift) & 255u;
-        const u64 m = __ballot(in);
-        if (m != 0) {
-          // whole waves of equal digits (rows of -inf) add once instead of 64 times to one LDS word
-          const int first = __ffsll((long long)m) - 1;
-          const unsigned d0 = (unsigned)__shfl((int)d, first, 64);
-          const u64 same = __ballot(in && d == d0);
-          if (same == m) {
-            if (lane == first) atomicAdd(&s_hist[d0], (unsigned)__popcll(m));
-          } else if (in) {
-            atomicAdd(&s_hist[d], 1u);
-          }
-        }
-      }
-    __syncthreads();
-    // keys above digit tid inside the current bucket: suffix sum over the 256 bins
-    const unsigned cnt = s_hist[tid];
-    unsigned acc = cnt;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned v = (unsigned)__shfl_down((int)acc, o, 64);
-      if (lane + o < 64) acc += v;
-    }
-    if (lane == 0) s_wtot[wave] = acc;
-    __syncthreads();
-    unsigned above = acc - cnt;
-    for (int w = wave + 1; w < BS_WAVES; ++w) above += s_wtot[w];
-    if (above < need && need <= above + cnt) {   // exactly one bin holds the need-th key from the top
-      s_prefix = (prefix << 8) | (u64)tid;
-      s_need = need - above;
-      s_stop = cnt == need - above;              // the bucket is taken whole: the lower bits decide nothing
-    }
-    __syncthreads();
-    prefix = s_prefix;
-    need = s_need;
-    fshift = shift;
-    if (s_stop) break;
-  }
-  if (tid == 0) s_nsel = 0;
-  __syncthreads();
-  for (int b = 0; b < nb; ++b)
-    for (int c = tid; c < V; c += BS_THREADS) {
-      const u64 key = bs_key(a, row0, b, c, s_mx, s_lse, s_prev, step);
-      if ((key >> fshift) >= prefix) {
-        const unsigned p = atomicAdd(&s_nsel, 1u);
-        if (p < (unsigned)K) s_sel[p] = key;
-      }
-    }
-  __syncthreads();
-  const int nsel = (int)min(s_nsel, (unsigned)K);   // (= K: the limits guarantee V > 2 * beam candidates)
-  if (tid < nsel) {
-    const u64 mine = s_sel[tid];
-    int rank = 0;
-    for (int j = 0; j < nsel; ++j) rank += s_sel[j] > mine;
-    s_sorted[rank] = mine;
-  }
-  __syncthreads();
+  // ---- 3. top 2 * beam on the unique key (beam_select.h) ----
+  const int nsel = bsel::select_top<BS_MAX_K>([&](int b, int c) { return bs_key(a, row0, b, c, s_mx, s_lse, s_prev, step); },
+                                              step == 0 ? 1 : beam, V, K, s_sorted);   // (= K: the limits guarantee V > 2 * beam)
 
   // ---- 4. - 6. EOS logic, record bookkeeping and the continuing rows: 2 * beam entries, one thread ----
   if (tid == 0) {
@@ -204,7 +124,7 @@ __global__ void __launch_bounds__(BS_THREADS) beam_step_kernel(const BeamStepArg
     u64 masked = 0;
     for (int i = 0; i < nsel; ++i) {
       const u64 key = s_sorted[i];
-      const float sc = bs_unfkey((uint32_t)(key >> 32));
+      const float sc = unfkey((uint32_t)(key >> 32));
       const uint32_t f = ~(uint32_t)key;
       const bool fin = (int)(f % (uint32_t)V) == a.eos && sc != -INFINITY;
       bool m = fin;
@@ -239,7 +159,7 @@ __global__ void __launch_bounds__(BS_THREADS) beam_step_kernel(const BeamStepArg
           const uint32_t f = ~(uint32_t)key;
           const int64_t r = row0 + k;
           a.tok[r * Tmax + step + 1] = (int32_t)(f % (uint32_t)V);
-          a.score[r * Tmax + step + 1] = bs_unfkey((uint32_t)(key >> 32));
+          a.score[r * Tmax + step + 1] = unfkey((uint32_t)(key >> 32));
           a.parent[r] = (int32_t)(row0 + f / (uint32_t)V);
           a.ignore[r] = m ? 1 : 0;
           ++k;
@@ -335,12 +255,12 @@ __global__ void __launch_bounds__(256) beam_embed_step_kernel(const float* __res
 
 }  // namespace
 
-extern "C" int st5_beam_step(const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_sent, int32_t beam, int32_t V,
-                             float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax,
-                             uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score,
-                             int32_t* rec_len, int32_t* n_hyp, int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter,
-                             const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
-                             int32_t min_len, int32_t max_len, void* stream) {
+static int beam_step_launch(int logprobs, const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_sent, int32_t beam,
+                            int32_t V, float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax,
+                            uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score,
+                            int32_t* rec_len, int32_t* n_hyp, int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter,
+                            const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                            int32_t min_len, int32_t max_len, void* stream) {
   if (!logits || !tok || !score || !anc || !ignore || !parent || !rec_tok || !rec_pos || !rec_score || !rec_len || !n_hyp || !sent_done ||
       !n_finished || !ticket || !counter || !never)
     return ST5_ERR_ARG;
@@ -351,7 +271,7 @@ extern "C" int st5_beam_step(const float* logits, int64_t ld, float* lprobs_out,
   if (eos < 0 || eos >= V) return ST5_ERR_ARG;
   BeamStepArgs a;
   a.logits = logits; a.ld = ld; a.lprobs = lprobs_out; a.lp_ld = lp_ld;
-  a.n_sent = n_sent; a.beam = beam; a.V = V; a.Tmax = Tmax; a.temperature = temperature;
+  a.n_sent = n_sent; a.beam = beam; a.V = V; a.Tmax = Tmax; a.temperature = temperature; a.logprobs = logprobs;
   a.tok = tok; a.score = score; a.anc = anc; a.anc_ld = anc_ld; a.ignore = ignore; a.parent = parent;
   a.rec_tok = rec_tok; a.rec_pos = rec_pos; a.rec_ld = rec_ld; a.rec_score = rec_score; a.rec_len = rec_len;
   a.n_hyp = n_hyp; a.sent_done = sent_done; a.n_finished = n_finished; a.ticket = ticket; a.counter = counter;
@@ -359,6 +279,28 @@ extern "C" int st5_beam_step(const float* logits, int64_t ld, float* lprobs_out,
   a.pad = pad; a.unk = unk; a.eos = eos; a.unk_penalty = unk_penalty; a.min_len = min_len; a.max_len = max_len;
   hipLaunchKernelGGL(beam_step_kernel, dim3(n_sent), dim3(BS_THREADS), 0, reinterpret_cast<hipStream_t>(stream), a);
   return hipGetLastError() == hipSuccess ? ST5_OK : ST5_ERR_LAUNCH;
+}
+
+extern "C" int st5_beam_step(const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_sent, int32_t beam, int32_t V,
+                             float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax,
+                             uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score,
+                             int32_t* rec_len, int32_t* n_hyp, int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter,
+                             const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                             int32_t min_len, int32_t max_len, void* stream) {
+  return beam_step_launch(0, logits, ld, lprobs_out, lp_ld, n_sent, beam, V, temperature, tok, score, anc, anc_ld, Tmax, ignore, parent,
+                          rec_tok, rec_pos, rec_ld, rec_score, rec_len, n_hyp, sent_done, n_finished, ticket, counter, never, len_div, pad,
+                          unk, eos, unk_penalty, min_len, max_len, stream);
+}
+
+extern "C" int st5_beam_step_logprobs(const float* lp, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_sent, int32_t beam, int32_t V,
+                                      int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax, uint8_t* ignore,
+                                      int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score, int32_t* rec_len,
+                                      int32_t* n_hyp, int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter,
+                                      const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                                      int32_t min_len, int32_t max_len, void* stream) {
+  return beam_step_launch(1, lp, ld, lprobs_out, lp_ld, n_sent, beam, V, 1.f, tok, score, anc, anc_ld, Tmax, ignore, parent, rec_tok,
+                          rec_pos, rec_ld, rec_score, rec_len, n_hyp, sent_done, n_finished, ticket, counter, never, len_div, pad, unk, eos,
+                          unk_penalty, min_len, max_len, stream);
 }
 
 extern "C" int st5_beam_reorder_dev(int32_t* anc, int64_t anc_ld, const int32_t* parent, int32_t n_sent, int32_t beam, int32_t Tmax,

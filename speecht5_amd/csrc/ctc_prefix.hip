@@ -8,11 +8,12 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "common.h"
+#include "ctc_rows_walk.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
 
-constexpr float LOGZERO = -10000000000.0f;   // ctc_prefix_score.py:21
+using ctc_rows::LOGZERO;
 
 // numpy's logaddexp for float32 (npy_logaddexpf): x + log1p(exp(-|x - y|)) on the larger operand
 __device__ __forceinline__ float logaddexp(float a, float b) {
@@ -79,20 +80,7 @@ __global__ void ctc_prefix_score_kernel(const float* __restrict__ x, int T, int 
 //     that buffer are not written (ctc_select_rows_kernel fills LOGZERO there when it gathers the continued hypotheses).
 // out_len > T_s (a short sentence in a batch that decodes on): eos gets logaddexp(r_prev[T_s-1]) as always, every other candidate
 // LOGZERO, the state is all LOGZERO.
-// logaddexp without the branches: the larger operand and -|a - b| are selected, then ONE log1pf(expf()) serves both orders.  The
-// same operations on the same values as logaddexp above in every case (d > 0: a + log1pf(expf(-d)); else b + log1pf(expf(d));
-// a == b: a + ln 2), hence the same bits; straight-line code lets the three recursions of a frame overlap in the pipeline, where
-// the branchy form runs them one after the other and, in a wave whose lanes disagree on the order, both sides of each.
-__device__ __forceinline__ float logaddexp_sel(float a, float b) {
-  const float d = a - b;
-  const bool gt = d > 0.f;
-  const float g = (gt ? a : b) + log1pf(expf(gt ? -d : d));
-  return a == b ? a + 0.693147180559945309417232121458176568f : g;
-}
-
-constexpr int ROWS_SEG = 2048;            // frames per LDS segment
-constexpr int ROWS_U = 16;                // frames per prefetched chunk
-constexpr int ROWS_REP = ROWS_SEG + 4;    // offset of the repeat form in phi_s (+4: the two forms never share a bank slot)
+// The walk of one pair is ctc_rows::walk (ctc_rows_walk.h), shared with the device-stepped form in beam_ctc.hip.
 
 // r[s][t] = (LOGZERO, sum_{u<=t} x[s][u][blank]) for t < lens[s], summed in frame order; (LOGZERO, LOGZERO) behind
 __global__ void ctc_initial_state_rows_kernel(const float* __restrict__ x, const int* __restrict__ lens, int Tmax, int V, int blank,
@@ -116,8 +104,6 @@ ctc_prefix_score_rows_kernel(const float* __restrict__ x, const int* __restrict_
                              int V, int blank, int eos, const float* __restrict__ r_prev, const long long* __restrict__ last,
                              int out_len, const long long* __restrict__ cs, int nc, float* __restrict__ log_psi_out,
                              float* __restrict__ r_new) {
-  __shared__ __attribute__((aligned(16))) float phi_s[ROWS_REP + ROWS_SEG];
-  __shared__ __attribute__((aligned(16))) float xb_s[ROWS_SEG];
   const int h = blockIdx.x, c = threadIdx.x;
   const bool live = c < nc;
   const int s = sent[h];
@@ -128,66 +114,10 @@ ctc_prefix_score_rows_kernel(const float* __restrict__ x, const int* __restrict_
     return;
   }
   const long long tok = live ? cs[(long long)h * nc + c] : (long long)blank;
-  const float* xs = x + (long long)s * Tmax * V;
-  const float* rp = r_prev + (long long)h * Tmax * 2;
-  float2* r = reinterpret_cast<float2*>(r_new) + (long long)h * Tmax * nc + c;      // frame t at r[t * nc]
-  const bool repeat = out_len > 0 && tok == last[h];
-  const int po = repeat ? ROWS_REP : 0;
-  const int start = out_len > 1 ? out_len : 1;
-  const int head = start - 1 < T ? start - 1 : T;
-  if (live)
-    for (int t = 0; t < head; ++t) r[(long long)t * nc] = make_float2(LOGZERO, LOGZERO);
-  float rn, rb;
-  if (out_len == 0) { rn = xs[tok]; rb = LOGZERO; }
-  else { rn = LOGZERO; rb = LOGZERO; }
-  if (start - 1 < T && live) r[(long long)(start - 1) * nc] = make_float2(rn, rb);
-  float log_psi = rn;
-  for (int t0 = start; t0 < T; t0 += ROWS_SEG) {        // (block-uniform trip count)
-    const int n = T - t0 < ROWS_SEG ? T - t0 : ROWS_SEG;
-    __syncthreads();                                    // the previous segment has been walked
-    for (int j = threadIdx.x; j < n; j += blockDim.x) {
-      const int t = t0 + j;
-      const float pn = rp[2 * (t - 1)], pb = rp[2 * (t - 1) + 1];
-      phi_s[j] = logaddexp_sel(pn, pb);
-      phi_s[ROWS_REP + j] = pb;
-      xb_s[j] = xs[(long long)t * V + blank];
-    }
-    __syncthreads();
-    if (live) {
-      const float* xt_p = xs + (long long)t0 * V + tok;
-      float2* rt = r + (long long)t0 * nc;
-      float xa[ROWS_U];
-#pragma unroll
-      for (int u = 0; u < ROWS_U; ++u) xa[u] = u < n ? xt_p[(long long)u * V] : 0.f;
-      for (int j0 = 0; j0 < n; j0 += ROWS_U) {
-        float xn[ROWS_U];
-#pragma unroll
-        for (int u = 0; u < ROWS_U; ++u) {              // the next chunk's gathers fly while this chunk is walked
-          const int jn = j0 + ROWS_U + u;
-          xn[u] = jn < n ? xt_p[(long long)jn * V] : 0.f;
-        }
-#pragma unroll
-        for (int u = 0; u < ROWS_U; ++u) {
-          const int j = j0 + u;
-          if (j < n) {
-            const float phi = phi_s[po + j];
-            const float xt = xa[u];
-            const float nn = logaddexp_sel(rn, phi) + xt;
-            const float nb = logaddexp_sel(rn, rb) + xb_s[j];
-            log_psi = logaddexp_sel(log_psi, phi + xt);
-            rn = nn; rb = nb;
-            rt[(long long)j * nc] = make_float2(rn, rb);
-          }
-        }
-#pragma unroll
-        for (int u = 0; u < ROWS_U; ++u) xa[u] = xn[u];
-      }
-    }
-  }
-  if (!live) return;
-  if (tok == eos) log_psi = logaddexp_sel(rp[2 * (T - 1)], rp[2 * (T - 1) + 1]);
-  if (tok == blank) log_psi = LOGZERO;
-  log_psi_out[(long long)h * nc + c] = log_psi;
+  const float log_psi = ctc_rows::walk(x + (long long)s * Tmax * V, T, V, blank, eos, r_prev + (long long)h * Tmax * 2,
+                                       out_len > 0 && tok == last[h], out_len, tok, live, nc,
+                                       reinterpret_cast<float2*>(r_new) + (long long)h * Tmax * nc + c);
+  if (live) log_psi_out[(long long)h * nc + c] = log_psi;
 }
 
 // Next step's prefix state of each continued hypothesis n: the extension (parent[n], slot of token[n] in cs[parent[n]]) of this

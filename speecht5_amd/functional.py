@@ -3634,21 +3634,25 @@ class BeamStepState:
                 part[5])
 
 
-def beam_step(logits, V, st, never, len_div, *, temperature, pad, unk, eos, unk_penalty, min_len, lprobs=None):
+def beam_step(logits, V, st, never, len_div, *, temperature, pad, unk, eos, unk_penalty, min_len, lprobs=None, logprobs=False):
     """One st5_beam_step on state `st` (BeamStepState): logits fp32 [rows, >= V] (row stride logits.stride(0)); never uint8 [V];
     len_div = beam_len_div(...) or None (scores are not normalised); lprobs: fp32 [rows, >= V] that receives the ruled
-    log-probabilities, or None."""
+    log-probabilities, or None.  logprobs=True: `logits` holds log-probabilities already (st5_beam_step_logprobs: no log-softmax,
+    `temperature` has been applied by whoever made them and is not used)."""
     assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == st.rows and logits.shape[1] >= V
     assert never.dtype == torch.uint8 and never.is_contiguous() and never.numel() == V
     assert len_div is None or (len_div.dtype == torch.float32 and len_div.is_contiguous() and len_div.numel() >= st.max_len + 1)
     assert lprobs is None or (lprobs.dtype == torch.float32 and lprobs.stride(1) == 1 and lprobs.shape[0] == st.rows and lprobs.shape[1] >= V)
-    hip.check(hip.lib().st5_beam_step(logits.data_ptr(), logits.stride(0), hip.ptr(lprobs), 0 if lprobs is None else lprobs.stride(0),
-                                      st.n_sent, st.beam, int(V), float(temperature), st.tok.data_ptr(), st.score.data_ptr(),
-                                      st.anc.data_ptr(), st.anc.stride(0), st.Tmax, st.ignore.data_ptr(), st.parent.data_ptr(),
-                                      st.rec_tok.data_ptr(), st.rec_pos.data_ptr(), st.rec_tok.stride(0), st.rec_score.data_ptr(),
-                                      st.rec_len.data_ptr(), st.n_hyp.data_ptr(), st.sent_done.data_ptr(), st.n_finished.data_ptr(),
-                                      st.ticket.data_ptr(), st.counter.data_ptr(), never.data_ptr(), hip.ptr(len_div), int(pad), int(unk),
-                                      int(eos), float(unk_penalty), int(min_len), st.max_len, hip.stream()), "st5_beam_step")
+    head = (logits.data_ptr(), logits.stride(0), hip.ptr(lprobs), 0 if lprobs is None else lprobs.stride(0), st.n_sent, st.beam, int(V))
+    tail = (st.tok.data_ptr(), st.score.data_ptr(), st.anc.data_ptr(), st.anc.stride(0), st.Tmax, st.ignore.data_ptr(),
+            st.parent.data_ptr(), st.rec_tok.data_ptr(), st.rec_pos.data_ptr(), st.rec_tok.stride(0), st.rec_score.data_ptr(),
+            st.rec_len.data_ptr(), st.n_hyp.data_ptr(), st.sent_done.data_ptr(), st.n_finished.data_ptr(), st.ticket.data_ptr(),
+            st.counter.data_ptr(), never.data_ptr(), hip.ptr(len_div), int(pad), int(unk), int(eos), float(unk_penalty), int(min_len),
+            st.max_len, hip.stream())
+    if logprobs:
+        hip.check(hip.lib().st5_beam_step_logprobs(*head, *tail), "st5_beam_step_logprobs")
+    else:
+        hip.check(hip.lib().st5_beam_step(*head, float(temperature), *tail), "st5_beam_step")
 
 
 def beam_reorder_dev(st):
@@ -3666,6 +3670,77 @@ def beam_embed_step(table, st, pos, pos_off, emb_scale, y):
                                             pos.shape[0], int(pos_off), float(emb_scale), y.data_ptr(), y.stride(0), st.rows, C, _dt(y),
                                             hip.stream()), "st5_beam_embed_step")
     return y
+
+
+# -------------------------------------------------------------------------------------------------
+# Joint CTC / attention scoring behind the step counter (csrc/beam_ctc.hip): candidates, prefix scores + mix, select.
+# -------------------------------------------------------------------------------------------------
+BEAM_CTC_MAX_CANDIDATES = 1024
+BEAM_CTC_MAX_STATE_BYTES = 1 << 30     # cap of the extensions' states r_new (rows * frames * candidates * 8 bytes)
+
+
+class BeamCtcState:
+    """Device state of the CTC part of a device-stepped beam search step, beside BeamStepState `bs`: `scorer` is the
+    CTCPrefixScorerRows of the call (posterior x [n_sent, Tfr, V], lens), row r is scored against sentence r // beam.  Buffers: state
+    [rows, Tfr, 2] (initial_state() per sentence, repeated by beam), r_new [rows, Tfr, nc, 2], log_psi [rows, nc], prev [rows] (0),
+    cs int32 [rows, nc], lp [rows, V], unknown int32 [1].  ValueError when r_new would exceed BEAM_CTC_MAX_STATE_BYTES."""
+
+    def __init__(self, scorer, bs, nc, ctc_weight):
+        rows, Tfr, V = bs.rows, scorer.T, scorer.V
+        if scorer.S != bs.n_sent:
+            raise ValueError(f"{scorer.S} posteriors for {bs.n_sent} sentences")
+        if not 0 < nc <= min(BEAM_CTC_MAX_CANDIDATES, V):
+            raise ValueError(f"{nc} CTC candidates per row: the device scorer takes 1 .. min({BEAM_CTC_MAX_CANDIDATES}, V = {V})")
+        nbytes = rows * Tfr * nc * 8
+        if nbytes > BEAM_CTC_MAX_STATE_BYTES:
+            raise ValueError(f"the CTC extension states of {rows} rows x {Tfr} frames x {nc} candidates take {nbytes} bytes, more than "
+                             f"the {BEAM_CTC_MAX_STATE_BYTES} the device-stepped decode allows; decode fewer sentences at once or use "
+                             f"decode='slots'")
+        dev = scorer.x.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        self.scorer, self.nc, self.ctc_weight, self.rows, self.Tfr, self.V = scorer, int(nc), float(ctc_weight), rows, Tfr, V
+        self.state = scorer.initial_state().repeat_interleave(bs.beam, dim=0).contiguous()
+        self.r_new = torch.empty(rows, Tfr, nc, 2, **f32)
+        self.log_psi = torch.empty(rows, nc, **f32)
+        self.prev = torch.zeros(rows, **f32)
+        self.cs = torch.zeros(rows, nc, dtype=torch.int32, device=dev)
+        self.lp = torch.empty(rows, V, **f32)
+        self.unknown = torch.zeros(1, dtype=torch.int32, device=dev)
+
+    def buffers(self):
+        return (self.scorer.x, self.scorer.lens, self.state, self.r_new, self.log_psi, self.prev, self.cs, self.lp, self.unknown)
+
+
+def beam_ctc_candidates(logits, V, bs, ctc, never, temperature):
+    """ctc.lp = log_softmax(logits / temperature) (unruled, st5_beam_step's statistics) and ctc.cs = the ctc.nc best tokens of every
+    row, never-tokens and NaN as -inf, under the tie rule, for the step in bs.counter."""
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == bs.rows == ctc.rows and logits.shape[1] >= V
+    assert never.dtype == torch.uint8 and never.is_contiguous() and never.numel() == V == ctc.V
+    hip.check(hip.lib().st5_beam_ctc_candidates(logits.data_ptr(), logits.stride(0), bs.rows, int(V), float(temperature), never.data_ptr(),
+                                                bs.counter.data_ptr(), bs.max_len, ctc.lp.data_ptr(), ctc.lp.stride(0), ctc.cs.data_ptr(),
+                                                ctc.nc, hip.stream()), "st5_beam_ctc_candidates")
+
+
+def ctc_prefix_score_rows_dev(bs, ctc):
+    """ctc.log_psi / ctc.r_new of the candidates ctc.cs for out_len = counter and last = bs.tok[:, counter], and the mix into ctc.lp."""
+    sc = ctc.scorer
+    assert bs.rows == ctc.rows and bs.tok.dtype == torch.int32 and bs.tok.is_contiguous()
+    hip.check(hip.lib().st5_ctc_prefix_score_rows_dev(sc.x.data_ptr(), sc.lens.data_ptr(), sc.S, sc.T, sc.V, sc.blank, sc.eos, bs.beam,
+                                                      ctc.state.data_ptr(), bs.tok.data_ptr(), bs.Tmax, bs.counter.data_ptr(), bs.max_len,
+                                                      ctc.cs.data_ptr(), ctc.nc, ctc.log_psi.data_ptr(), ctc.r_new.data_ptr(),
+                                                      ctc.prev.data_ptr(), ctc.lp.data_ptr(), ctc.lp.stride(0), ctc.ctc_weight,
+                                                      hip.stream()), "st5_ctc_prefix_score_rows_dev")
+
+
+def ctc_select_dev(bs, ctc):
+    """Behind the beam step: ctc.state / ctc.prev of the continued rows from their parents' extensions; ctc.unknown is set when a
+    row that still counts was continued by a token outside its parent's candidates."""
+    sc = ctc.scorer
+    assert bs.rows == ctc.rows
+    hip.check(hip.lib().st5_ctc_select_dev(sc.lens.data_ptr(), sc.S, sc.T, bs.beam, ctc.cs.data_ptr(), ctc.nc, ctc.log_psi.data_ptr(),
+                                           ctc.r_new.data_ptr(), bs.parent.data_ptr(), bs.tok.data_ptr(), bs.Tmax, bs.ignore.data_ptr(),
+                                           bs.sent_done.data_ptr(), bs.counter.data_ptr(), bs.max_len, ctc.state.data_ptr(),
+                                           ctc.prev.data_ptr(), ctc.unknown.data_ptr(), hip.stream()), "st5_ctc_select_dev")
 
 
 # -------------------------------------------------------------------------------------------------

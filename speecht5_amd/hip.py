@@ -6,7 +6,7 @@ fallback: if the shared library is missing or a kernel returns an error the call
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, byref, c_char_p, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
+from ctypes import POINTER, Structure, byref, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_uint64, c_void_p
 
 import torch
 
@@ -251,6 +251,17 @@ _SIGS = {
                               c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                               c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_int32, c_int32, c_void_p]),
     "st5_beam_reorder_dev": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p]),
+    "st5_beam_step_logprobs": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_int64,
+                                       c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_void_p,
+                                       c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_float, c_int32,
+                                       c_int32, c_void_p]),
+    "st5_beam_ctc_candidates": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_void_p, c_int32, c_void_p, c_int64,
+                                        c_void_p, c_int32, c_void_p]),
+    "st5_ctc_prefix_score_rows_dev": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p,
+                                              c_int32, c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int64, c_double, c_void_p]),
+    "st5_ctc_select_dev": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                   c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "st5_beam_embed_step": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int64,
                                     c_int32, c_int32, c_int, c_void_p]),
     "st5_angular_margin_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),

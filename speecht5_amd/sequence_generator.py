@@ -9,7 +9,8 @@ the top `beam` are finalized, finished sentences leave the batch, length normali
 every step re-scores the best `7 x beam` next tokens of each hypothesis with the CTC prefix probability of the FIRST sentence's
 encoder output (sequence_generator.py:273-284, 370-418):  lprob' = (1 - w) lprob + w (log psi(h.c) - log psi(h)).
 `ctc_rows=True` (not in the reference, off by default) scores every sentence against its own posterior and frame count instead,
-which is what makes the joint recipe batchable (CTCPrefixScorerRows, the st5_ctc_*_rows entries of csrc/ctc_prefix.hip).
+which is what makes the joint recipe batchable (CTCPrefixScorerRows, the st5_ctc_*_rows entries of csrc/ctc_prefix.hip), and the
+only CTC scoring that decode="device" / "graph" run (beam_graph.py: the same scorer behind the device step counter, csrc/beam_ctc.hip).
 
 What differs is where it runs: the reference moves every hypothesis to the host, scores it with numpy and keeps the prefix
 states in a Python dict keyed by the token string (one device sync per hypothesis and step); here the CTC posterior, the
@@ -188,7 +189,8 @@ class SequenceGenerator(nn.Module):
         gather of an int32 table.  A model whose decoder has no slot API is refused (ValueError), there is no fallback.
         "device" / "graph" (beam_graph.py): the slot cache with the whole step on the device -- the beam step is one HIP kernel
         (csrc/beam_step.hip), the step index a device counter, the host polls the finished-sentence count every BEAM_POLL_STEPS
-        steps; "graph" replays the step from a HIP graph.  One model, no CTC / LM / prefix / constraints / n-gram blocking /
+        steps; "graph" replays the step from a HIP graph.  One model, ctc_weight > 0 with ctc_rows=True only (csrc/beam_ctc.hip; a
+        hypothesis that leaves its CTC candidates raises KeyError at the next poll), no LM / prefix / constraints / n-gram blocking /
         match_source_len / custom search (ValueError naming the option); `attention` of the hypotheses is an empty tensor (no
         probability record is kept); ties between candidates go to the lower beam_row * V + token."""
         super().__init__()
