@@ -823,6 +823,16 @@ int st5_ctc_select_dev(const int32_t* lens, int32_t S, int32_t Tfr, int32_t beam
 int st5_beam_embed_step(const float* table, int32_t V, const int32_t* tok, int32_t Tmax, const int32_t* counter, const float* pos,
                         int32_t pos_rows, int32_t pos_off, float emb_scale, void* y, int64_t y_ld, int32_t rows, int32_t cols, int dtype,
                         void* stream);
+/* ---- shallow fusion of a language model in the device-stepped beam search (csrc/beam_lm.hip), step = *counter in [0, max_len], nothing
+ * is written outside it.  lm_logits [rows][lm_ld] in `lm_dtype` (ST5_F32 / ST5_BF16), V_lm <= V; lp [rows][lp_ld] fp32.
+ * st5_beam_lm_logprobs, logits != NULL: lp[r][c] = (logits[r][c] / temperature - max) - log(sum), st5_beam_ctc_candidates' lp (the
+ *   same statistics and bits), then for c < V_lm: lp[r][c] += lm_weight * ((lm_logits[r][c] - max_lm) - log(sum_lm)); the beam step on
+ *   log-probabilities follows.  logits == NULL: the LM term alone is added into lp in place (the CTC-mixed log-probabilities; behind
+ *   st5_ctc_prefix_score_rows_dev, in front of st5_beam_step_logprobs).  The product and the sum are each rounded to fp32 (torch's
+ *   lprobs[:, :V_lm] += lm_weight * log_softmax); columns V_lm .. V - 1 get no LM term; -inf stays -inf. */
+int st5_beam_lm_logprobs(const float* logits, int64_t ld, int32_t rows, int32_t V, float temperature, const void* lm_logits, int64_t lm_ld,
+                         int32_t V_lm, float lm_weight, int lm_dtype, const int32_t* counter, int32_t max_len, float* lp, int64_t lp_ld,
+                         void* stream);
 
 /* Skinny-M GEMM of the decode loops (csrc/decode_gemm.hip): out[m, n] = epilogue(sum_k x[m, k] * w[n, k] + bias[n]) for 1 <= M <= 32,
  * w in nn.Linear layout [N, K] (stacked weights are one [sum N_i, K] matrix), x / w / res in `dtype`, fp32 accumulation.  Weight-streaming:

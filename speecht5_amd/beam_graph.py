@@ -20,12 +20,25 @@ it; every buffer the graph has baked in belongs to the BeamDeviceDecode object, 
 Joint CTC / attention scoring (ctc_weight > 0) runs in these modes with ctc_rows=True only: no sentence leaves the batch, so row r is
 scored against sentence r // beam's own posterior and frame count for the whole call.  The step then is: pre-net row, decoder layers,
 projection, st5_beam_ctc_candidates (log-probabilities and the 7 x beam best tokens of every row), st5_ctc_prefix_score_rows_dev (the
-rows scorer with out_len and the last labels read on the device, the mix (1 - w) lp + w (log psi - prev) in its epilogue), [an LM term
-would go here], st5_beam_step_logprobs (the beam step on log-probabilities), st5_ctc_select_dev (the continued rows' prefix states),
+rows scorer with out_len and the last labels read on the device, the mix (1 - w) lp + w (log psi - prev) in its epilogue), [the LM
+term, see below], st5_beam_step_logprobs (the beam step on log-probabilities), st5_ctc_select_dev (the continued rows' prefix states),
 the reorder (csrc/beam_ctc.hip; buffers: functional.BeamCtcState).  A hypothesis continued by a token outside its CTC candidates sets
 a sticky device flag (rows that are ignored or belong to a finished sentence do not); the host reads it where it reads the
-finished-sentence count and at the end, and raises _generate's KeyError then, a few steps later than the slots loop would.  An LM
-(lm_model) stays refused.
+finished-sentence count and at the end, and raises _generate's KeyError then, a few steps later than the slots loop would.
+
+Shallow fusion (lm_model) runs in these modes when the LM is a speecht5_amd.transformer_lm.TransformerLanguageModel
+(task.build_generator converts fairseq LMs to it).  No sentence leaves the batch, so the LM's rows are the decoder's rows with the same
+ancestry: the LM's slot caches are read through the DECODER's ancestry table (st.bufs[0]; TransformerLanguageModel.init_decode(anc=)),
+there is no second table and no reorder of the LM's own.  Its launches (TransformerLanguageModel.device_step: st5_beam_embed_step with
+the LM's tables, the layers on the skinny-M kernel, K|V into slot `counter`, st5_lm_decode_attn_dev, the final LayerNorm, the output
+projection with fp32 output) follow the decoder's projection; then st5_beam_lm_logprobs (csrc/beam_lm.hip) puts the LM term into the
+step's log-probabilities.  Without CTC: st5_beam_lm_logprobs on the decoder's logits (log-softmax with the beam step's statistics, then
+lp[:, :V_lm] += lm_weight * log_softmax(lm logits)), st5_beam_step_logprobs, the reorder.  With CTC: candidates, prefix scores and mix,
+st5_beam_lm_logprobs in place on the mixed log-probabilities, st5_beam_step_logprobs, select, the reorder -- _generate's order (CTC
+candidates and mix on the unfused log-probabilities, then the LM, then the rules).  The step stays serial.  Without an LM the launch
+list is what it is without this paragraph.  Refused, each with a ValueError that names lm_model: any other LM object (the full-prefix
+fallback has no device form), an LM with a larger dictionary than the model's (V_lm > vocab_size), and max_len + 2 positions more than
+lm.max_positions() (asked at generate(), where max_len is known).
 
 `attention` of the returned hypotheses is an empty tensor in these modes: no probability record is kept."""
 import gc
@@ -48,7 +61,14 @@ def check_generator(gen):
         raise ValueError(f"decode={mode!r}: ctc_weight > 0 needs ctc_rows=True (no sentence leaves the batch here, so every sentence is "
                          f"scored against its own CTC posterior); the first-sentence scoring of ctc_rows=False is decode='slots' only")
     if gen.lm_model is not None:
-        raise ValueError(f"decode={mode!r}: an LM (lm_model) is not supported; use decode='slots'")
+        from .transformer_lm import TransformerLanguageModel
+        lm = gen.lm_model
+        if not isinstance(lm, TransformerLanguageModel):
+            raise ValueError(f"decode={mode!r}: an LM (lm_model) of type {type(lm).__name__} is not supported (only "
+                             f"speecht5_amd.transformer_lm.TransformerLanguageModel has a device-stepped form); use decode='slots'")
+        V_lm = lm.decoder.embed_tokens.num_embeddings
+        if V_lm > gen.vocab_size:
+            raise ValueError(f"decode={mode!r}: lm_model has a dictionary of {V_lm} symbols, more than the model's {gen.vocab_size}")
     if gen.repeat_ngram_blocker is not None:
         raise ValueError(f"decode={mode!r}: no_repeat_ngram_size > 0 is not supported; use decode='slots'")
     if gen.match_source_len:
@@ -63,6 +83,13 @@ def check_generator(gen):
     if any(l.encoder_attn is None for l in dec.layers):
         raise ValueError(f"decode={mode!r}: a decoder layer has no encoder attention")
     Fn.beam_step_check(gen.beam_size, gen.vocab_size)
+
+
+def check_lm_positions(gen, max_len):
+    """ValueError when the call's max_len + 2 positions are more than the LM takes (asked at generate(): max_len depends on the input)."""
+    if gen.lm_model is not None and max_len + 2 > gen.lm_model.max_positions():
+        raise ValueError(f"decode={gen.decode!r}: lm_model takes {gen.lm_model.max_positions()} positions, this call needs max_len + 2 = "
+                         f"{max_len + 2}; lower max_len_a / max_len_b or use decode='slots'")
 
 
 def never_mask(gen, device):
@@ -121,14 +148,27 @@ class BeamDeviceDecode:
         proj = post.output_projection
         self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
         rules = dict(temperature=gen.temperature, pad=gen.pad, unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len)
-        if self.ctc is None:
+        # shallow fusion: the LM's step over the same rows and the decoder's ancestry table, behind the decoder's projection
+        lm, w_lm = gen.lm_model, float(gen.lm_weight)
+        self.lm_state = self.lm_logits = self.lp = None
+        if lm is not None:
+            self.lm_state = lm.init_decode(rows, max_len + 2, anc=st.bufs[0])
+            self.lm_logits = lm.device_step(self.lm_state, bs, lin, norm, new, ops)
+        if self.ctc is None and lm is None:
             ops.append(lambda: Fn.beam_step(self.logits, V, bs, self.never, self.len_div, **rules))
+        elif self.ctc is None:
+            # log-probabilities with the LM term, the beam step on them
+            self.lp = new(rows, V, dt=torch.float32)
+            ops.append(lambda: Fn.beam_lm_logprobs(self.lp, V, bs, self.lm_logits, w_lm, logits=self.logits, temperature=gen.temperature))
+            ops.append(lambda: Fn.beam_step(self.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
         else:
-            # log-probabilities and candidates, prefix scores mixed into them, [an LM term would go here], the beam step on them, the
-            # continued rows' prefix states
+            # log-probabilities and candidates, prefix scores mixed into them, the LM term, the beam step on them, the continued rows'
+            # prefix states
             ctc = self.ctc
             ops.append(lambda: Fn.beam_ctc_candidates(self.logits, V, bs, ctc, self.never, gen.temperature))
             ops.append(lambda: Fn.ctc_prefix_score_rows_dev(bs, ctc))
+            if lm is not None:
+                ops.append(lambda: Fn.beam_lm_logprobs(ctc.lp, V, bs, self.lm_logits, w_lm))
             ops.append(lambda: Fn.beam_step(ctc.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
             ops.append(lambda: Fn.ctc_select_dev(bs, ctc))
         ops.append(lambda: Fn.beam_reorder_dev(bs))
@@ -149,11 +189,14 @@ class BeamDeviceDecode:
         return Fn.BeamCtcState(CTCPrefixScorerRows(post, frames, gen.blank, gen.eos), self.bs, nc, gen.ctc_weight)
 
     def buffer_ptrs(self):
-        """Data pointers of what must never move during a call: slot K/V, encoder-side K|V, the hypothesis records, the CTC buffers."""
+        """Data pointers of what must never move during a call: slot K/V, encoder-side K|V, the hypothesis records, the CTC buffers,
+        the LM's slot caches, its logits and (without CTC) the fused log-probabilities."""
         st = self.slots
         ctc = () if self.ctc is None else tuple(t.data_ptr() for t in self.ctc.buffers())
+        lm = () if self.lm_state is None else tuple(t.data_ptr() for t in self.lm_state.kv) + tuple(
+            t.data_ptr() for t in (self.lm_logits, self.lp) if t is not None)
         return tuple(t.data_ptr() for t in st.kv) + tuple(kv.data_ptr() for kv, _ in st.xkv) + (self.bs.records.data_ptr(),
-                                                                                                  st.bufs[0].data_ptr()) + ctc
+                                                                                                  st.bufs[0].data_ptr()) + ctc + lm
 
     def step(self):
         for op in self.ops:
@@ -266,6 +309,7 @@ def generate(gen, sample, prefix_tokens=None, constraints=None, bos_token=None):
     n_sent, src_len = src_tokens.size()[:2]
     max_len = min(int(gen.max_len_a * src_len + gen.max_len_b), gen.max_len - 1)
     assert gen.min_len <= max_len, "min_len cannot be larger than max_len, please adjust these!"
+    check_lm_positions(gen, max_len)
     model = gen.model.models[0]
     encoder_outs = gen.model.forward_encoder(net_input, exact_rows=True) if gen.exact_rows else gen.model.forward_encoder(net_input)
     device = src_tokens.device

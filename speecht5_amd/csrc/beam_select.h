@@ -1,4 +1,4 @@
-// What the kernels of a device-stepped beam search step share (beam_step.hip, beam_ctc.hip): the log-softmax statistics of one row,
+// What the kernels of a device-stepped beam search step share (beam_step.hip, beam_ctc.hip, beam_lm.hip): the log-softmax statistics of one row,
 // the monotone key of an fp32 score, and the top-K selection by radix select on a unique 64-bit key.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -27,13 +27,15 @@ __device__ __forceinline__ uint32_t fkey(float s) {
 }
 __device__ __forceinline__ float unfkey(uint32_t k) { return __uint_as_float((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k); }
 
-// Row maximum of x / temperature and the logarithm of the fp64 sum of expf(x / temperature - mx), by ONE wave (every lane gets both)
-__device__ __forceinline__ void row_stats(const float* __restrict__ x, int V, float temperature, int lane, float& mx_out, float& lse_out) {
+// Row maximum of x / temperature and the logarithm of the fp64 sum of expf(x / temperature - mx), by ONE wave (every lane gets both);
+// x in fp32 or bf16 (the LM's logits of beam_lm.hip)
+template <typename T>
+__device__ __forceinline__ void row_stats(const T* __restrict__ x, int V, float temperature, int lane, float& mx_out, float& lse_out) {
   float mx = -INFINITY;
-  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, x[c] / temperature);
+  for (int c = lane; c < V; c += 64) mx = fmaxf(mx, Elem<T>::to_f(x[c]) / temperature);
   mx = wave_max(mx);
   double sum = 0.0;
-  for (int c = lane; c < V; c += 64) sum += (double)expf(x[c] / temperature - mx);
+  for (int c = lane; c < V; c += 64) sum += (double)expf(Elem<T>::to_f(x[c]) / temperature - mx);
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) sum += __shfl_xor(sum, o, 64);
   mx_out = mx;

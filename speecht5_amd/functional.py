@@ -3744,6 +3744,28 @@ def ctc_select_dev(bs, ctc):
 
 
 # -------------------------------------------------------------------------------------------------
+# Shallow fusion of a language model behind the step counter (csrc/beam_lm.hip).
+# -------------------------------------------------------------------------------------------------
+def beam_lm_logprobs(lp, V, bs, lm_logits, lm_weight, logits=None, temperature=1.0):
+    """The LM term of a device-stepped beam search step, for the step in bs.counter (nothing is written once it is past bs.max_len).
+    lm_logits [rows, V_lm] (fp32 or the compute dtype, V_lm <= V); lp fp32 [rows, >= V].
+    With `logits` (fp32 [rows, >= V], no CTC in the step): lp = log_softmax(logits / temperature) with st5_beam_step's statistics
+    (beam_ctc_candidates' lp, bit for bit), then lp[:, :V_lm] += lm_weight * log_softmax(lm_logits).
+    Without (logits=None): the LM term alone is added into lp in place (the CTC-mixed log-probabilities).
+    -inf entries stay -inf; columns V_lm .. V - 1 get no LM term."""
+    V_lm = lm_logits.shape[1]
+    assert lp.dtype == torch.float32 and lp.stride(1) == 1 and lp.shape[0] == bs.rows and lp.shape[1] >= V
+    assert lm_logits.stride(1) == 1 and lm_logits.shape[0] == bs.rows and V_lm <= V
+    assert logits is None or (logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == bs.rows and
+                              logits.shape[1] >= V and logits.data_ptr() != lp.data_ptr())
+    hip.check(hip.lib().st5_beam_lm_logprobs(hip.ptr(logits), 0 if logits is None else logits.stride(0), bs.rows, int(V), float(temperature),
+                                             lm_logits.data_ptr(), lm_logits.stride(0), V_lm, float(lm_weight), _dt(lm_logits),
+                                             bs.counter.data_ptr(), bs.max_len, lp.data_ptr(), lp.stride(0), hip.stream()),
+              "st5_beam_lm_logprobs")
+    return lp
+
+
+# -------------------------------------------------------------------------------------------------
 # Speaker-identification head (s2c, speaker_decoder_postnet.py): BatchNorm1d over [B, C] rows (st5_batchnorm_act_*), cosine logits
 # F.linear(F.normalize(x), F.normalize(W)) (st5_norm_rows + st5_gemm) with the AM / AAM margin (csrc/speaker_head.hip), and the time
 # mean of --sid-pooling-layer encoder.  The head runs in fp32 whatever the compute dtype: it is B rows wide.

@@ -190,8 +190,10 @@ class SequenceGenerator(nn.Module):
         "device" / "graph" (beam_graph.py): the slot cache with the whole step on the device -- the beam step is one HIP kernel
         (csrc/beam_step.hip), the step index a device counter, the host polls the finished-sentence count every BEAM_POLL_STEPS
         steps; "graph" replays the step from a HIP graph.  One model, ctc_weight > 0 with ctc_rows=True only (csrc/beam_ctc.hip; a
-        hypothesis that leaves its CTC candidates raises KeyError at the next poll), no LM / prefix / constraints / n-gram blocking /
-        match_source_len / custom search (ValueError naming the option); `attention` of the hypotheses is an empty tensor (no
+        hypothesis that leaves its CTC candidates raises KeyError at the next poll), lm_model only as a HIP
+        transformer_lm.TransformerLanguageModel whose dictionary is no larger than the model's and which takes max_len + 2 positions
+        (its step runs behind the decoder's over the same ancestry table, csrc/beam_lm.hip fuses it), no prefix / constraints / n-gram
+        blocking / match_source_len / custom search (ValueError naming the option); `attention` of the hypotheses is an empty tensor (no
         probability record is kept); ties between candidates go to the lower beam_row * V + token."""
         super().__init__()
         self.model = models if isinstance(models, EnsembleModel) else EnsembleModel(models)

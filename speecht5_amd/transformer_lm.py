@@ -20,6 +20,8 @@ Two ways to run it:
   position j, written once (the K / V projection GEMM writes it in place).  One int32 ancestry table anc [rows, Tmax], shared by
   all layers, says which slot row r reads at position j; a beam reorder gathers that table (st5_lm_reorder) and moves no key or
   value.  Attention of the newest position: st5_lm_decode_attn (csrc/lm_decode.hip).
+  device_step: the same step as a list of launches behind a device step counter, for the device-stepped beam search
+  (beam_graph.py): the slot caches are read through the text decoder's ancestry table, there is no reorder of the LM's own.
 
 Layouts it does not implement raise NotImplementedError naming the option: adaptive softmax / adaptive input, learned positions,
 layernorm_embedding, post-LN layers, no_decoder_final_norm, character embeddings, decoder_input_dim != decoder_embed_dim."""
@@ -209,13 +211,21 @@ class TransformerLanguageModel(nn.Module):
 
     # ---- incremental path (beam search) ----
     @torch.no_grad()
-    def init_decode(self, rows, max_len):
+    def init_decode(self, rows, max_len, anc=None):
         """Slot caches [rows, max_len, 2C] per layer in the compute dtype, the ancestry table (identity: every row reads its own
-        slots) and the attention workspace -- allocated once per generate() call."""
+        slots) and the attention workspace -- allocated once per generate() call.
+        anc: an int32 [rows, max_len] ancestry table that somebody else owns and reorders (the text decoder's, in the device-stepped
+        beam search: the LM's rows are the decoder's rows with the same ancestry).  The state then holds no table of its own and is
+        one for device_step; decode_step / reorder need the default."""
         dev = self.decoder.embed_tokens.weight.device
         dtype = Fn.compute_dtype()
         C = self.args.decoder_embed_dim
         kv = [torch.empty(rows, max_len, 2 * C, dtype=dtype, device=dev) for _ in self.decoder.layers]
+        if anc is not None:
+            if anc.dtype != torch.int32 or tuple(anc.shape) != (rows, max_len) or anc.stride(1) != 1 or anc.device != dev:
+                raise ValueError(f"init_decode: anc must be an int32 [{rows}, {max_len}] table on {dev}, got {anc.dtype} "
+                                 f"{tuple(anc.shape)} on {anc.device}")
+            return DecodeState(kv, [anc], Fn.lm_decode_attn_ws(rows, max_len, self.num_heads, self.head_dim, dev), max_len)
         ident = torch.arange(rows, dtype=torch.int32, device=dev).unsqueeze(1).expand(rows, max_len)
         bufs = [ident.contiguous(), torch.empty(rows, max_len, dtype=torch.int32, device=dev)]
         ws = Fn.lm_decode_attn_ws(rows, max_len, self.num_heads, self.head_dim, dev)
@@ -250,6 +260,42 @@ class TransformerLanguageModel(nn.Module):
         x = dec.layer_norm(x)
         state.t = p + 1
         return Fn.linear(x, dec.output_projection.weight, None)
+
+    @torch.no_grad()
+    def device_step(self, state, bs, lin, norm, new, ops):
+        """The LM's share of one DEVICE-STEPPED beam search step (beam_graph.BeamDeviceDecode), on the pattern of
+        TransformerDecoder.beam_slots_device_step: appends to `ops` the zero-argument launches that take the newest token of every
+        hypothesis row (bs.tok[:, counter], bs: functional.BeamStepState) through the LM, and returns the buffer of the fp32 logits
+        [rows, V_lm].  `state`: init_decode(rows, Tmax, anc=the decoder's ancestry table).  Position = the int32 device scalar
+        bs.counter: the embedding reads position counter + padding_idx + 1, K|V go to slot `counter` through the skinny GEMM's
+        device-side output offset, the attention reads positions 0 .. counter over state.anc.  lin(x, weights, biases, out,
+        **epilogue) / norm(layer_norm, x, y) / new(*shape) are the caller's launch builders: every buffer is the caller's, nothing
+        is allocated per step and no launch depends on a host value."""
+        dec = self.decoder
+        rows, Tmax, anc, counter = state.rows, state.Tmax, state.anc, bs.counter
+        if bs.rows != rows or bs.Tmax != Tmax:
+            raise ValueError(f"device_step: a decode state of {rows} rows x {Tmax} positions beside a beam state of {bs.rows} x {bs.Tmax}")
+        H, hd = self.num_heads, self.head_dim
+        C = H * hd
+        table = dec.embed_tokens.weight.detach()
+        pos = dec.embed_positions.table(Tmax + dec.padding_idx + 2, table.device)
+        x = new(rows, C)
+        ops.append(lambda x=x: Fn.beam_embed_step(table, bs, pos, dec.padding_idx + 1, dec.embed_scale, x))
+        for layer, slots in zip(dec.layers, state.kv):
+            sa = layer.self_attn
+            h = norm(layer.self_attn_layer_norm, x, new(rows, C))
+            q = lin(h, [sa.q_proj.weight], [sa.q_proj.bias], new(rows, C))
+            lin(h, [sa.k_proj.weight, sa.v_proj.weight], [sa.k_proj.bias, sa.v_proj.bias], slots, step=counter, step_stride=2 * C,
+                step_cap=Tmax, out_ld=Tmax * 2 * C)
+            ctx = new(rows, C)
+            ops.append(lambda q=q, slots=slots, ctx=ctx: Fn.lm_decode_attn_dev(q, slots, anc, counter, 1, Tmax, H, hd, ctx, state.ws))
+            x = lin(ctx, [sa.out_proj.weight], [sa.out_proj.bias], new(rows, C), residual=x)
+            h = norm(layer.final_layer_norm, x, new(rows, C))
+            f = lin(h, [layer.fc1.weight], [layer.fc1.bias], new(rows, layer.fc1.weight.shape[0]), act=layer.act)
+            x = lin(f, [layer.fc2.weight], [layer.fc2.bias], new(rows, C), residual=x)
+        x = norm(dec.layer_norm, x, new(rows, C))
+        proj = dec.output_projection
+        return lin(x, [proj.weight], [None], new(rows, proj.weight.shape[0], dt=torch.float32), out_f32=True)
 
     @torch.no_grad()
     def reorder(self, state, order):
