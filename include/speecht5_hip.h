@@ -498,6 +498,13 @@ int st5_conv1d_cout1(const void* x, int64_t x_bs, int32_t x_ts, const void* w, c
 int st5_stft_frames(const float* wav, float* out, int32_t B, int32_t S, int32_t n_fft, int32_t hop, void* stream);
 int st5_stft_magnitude(const float* reim, float* mag, int64_t rows, int32_t nbins, int32_t ldh, void* stream);
 int st5_log10_floor(const float* x, float* y, int64_t n, float floor_value, void* stream);
+/* st5_stft_frames_rows: st5_stft_frames for B waveforms of DIFFERENT lengths in one launch (the per-item `logmelfilterbank` of
+ * data/speech_to_speech_dataset.py:141-157 for a whole batch).  wav = device array of B base pointers (fp32 [len[b]]), len int32 [B],
+ * frame_off int64 [B + 1] = running sum of L_b = 1 + len[b] / hop (frame_off[B] = total_frames).  out fp32 [total_frames, n_fft]
+ * (16-byte aligned), item b's frames in rows [frame_off[b], frame_off[b + 1]), each centred and reflect-padded at the item's OWN
+ * ends.  The caller guarantees len[b] > n_fft / 2 (the tables live on the device); n_fft % 4 == 0. */
+int st5_stft_frames_rows(const float* const* wav, const int32_t* len, const int64_t* frame_off, float* out, int32_t B, int64_t total_frames,
+                         int32_t n_fft, int32_t hop, void* stream);
 
 /* ---- collation of the speech-pretraining batch on the device (data/speech_dataset.py:302-446 SpeechPretrainDataset.collater,
  *      collater_audio, crop_to_max_size, collater_frm_label; fairseq collate_tokens): every tensor of the batch is a RAGGED GATHER of
@@ -720,6 +727,17 @@ int st5_angular_margin_bwd(const float* cos, int64_t ld, const int32_t* target, 
 int st5_time_mean_fwd(const void* x, int64_t t_stride, int64_t b_stride, int32_t T, int32_t B, int32_t C, float* y, int dtype,
                       void* stream);
 int st5_time_mean_bwd(const float* dy, int32_t T, int32_t B, int32_t C, int32_t accumulate, void* dx, int dtype, void* stream);
+/* ---- Speech enhancement output (s2s with --se-predict, SpeechT5/speecht5/models/speecht5.py:937-953; csrc/elementwise.hip) ----
+ * The post-net's outputs `before` and `after` combined with the source features `src` (all fp32, n elements, same layout), both in
+ * one launch.  ST5_SE_MASKING: y = sigmoid(x) * src; ST5_SE_DELTA: y = x - src (`target` returns the outputs as they are: no
+ * kernel).  st5_se_predict_bwd: g = d * src * s * (1 - s) with s = sigmoid(x) recomputed from x (masking), g = d (delta); no gradient
+ * goes to src (data).  Outputs do not alias inputs.  16-byte vectors when every pointer is 16-byte aligned, scalars otherwise. */
+#define ST5_SE_MASKING 0
+#define ST5_SE_DELTA 1
+int st5_se_predict_fwd(const float* before, const float* after, const float* src, float* out_before, float* out_after, int64_t n,
+                       int32_t mode, void* stream);
+int st5_se_predict_bwd(const float* d_before, const float* d_after, const float* before, const float* after, const float* src,
+                       float* g_before, float* g_after, int64_t n, int32_t mode, void* stream);
 /* ... over TWO gradient buffers: the step uses g + g2 (g2 may be NULL); zero_grads != 0 leaves both buffers zeroed.  With
  * st5_sumsq_pair (sum of squares of x + y) for the clipping norm this replaces "g += g2", two fills and the plain step. */
 int st5_adam_step_pair(float* p, float* g, float* g2, int32_t zero_grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,

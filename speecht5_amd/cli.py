@@ -24,7 +24,7 @@ MODEL_OPTIONS = [
     ("--freeze-encoder-updates", "int", None, None), ("--freeze-decoder-updates", "int", None, None),
     ("--no-freeze-encoder-layer", "str", None, None), ("--share-input-output-embed", "flag", False, None),
     ("--share-ctc-embed", "flag", False, None), ("--encoder-sliding-window-attn", "int", None, None),
-    # speech pre-net variants / speaker options (parsed for recipe compatibility; the SID / SE heads are out of scope)
+    # speech pre-net variants / speaker and speech-enhancement options
     ("--encoder-speech-prenet", "str", "conv", ["conv", "linear"]), ("--conv-kernel-sizes", "str", "5,5", None),
     ("--conv-channels", "int", 1024, None), ("--subsample-stride", "str", "2,2", None),
     ("--spk-embed-integration-type", "str", None, ["pre", "add"]), ("--dprenet-dropout-rate", "float", 0.5, None),

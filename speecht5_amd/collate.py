@@ -258,6 +258,70 @@ class SpeechToClassCollater:
     __call__ = collater
 
 
+class SpeechToSpeechCollater:
+    """SpeechToSpeechDataset.collater (data/speech_to_speech_dataset.py:169-228) + collater_audio (:230-244) + _collate_frames (:22-40).
+    samples: [{"id", "audio_name", "tgt_name", "source": fp32 [S] (device), "target": fp32 [L, odim] (device) or None,
+    "spkembs": fp32 [D] (device), and with target None "target_wav": fp32 [S'] (device)}].  target None: the item's log-mel is computed here -- the reference's __getitem__ does it per item
+    with librosa on the host (:141-157) -- for ALL such items of the batch in one ragged pass (features.LogMelFilterBank.rows), and
+    the batch tensors are gathered straight from its packed result."""
+
+    def __init__(self, device, *, reduction_factor=1, logmel=None):
+        self.device, self.reduction_factor, self._logmel = device, reduction_factor, logmel
+
+    def _fbanks(self, samples):
+        fbanks = [s.get("target") for s in samples]
+        todo = [i for i, f in enumerate(fbanks) if f is None]
+        if todo:
+            if self._logmel is None:
+                from .features import LogMelFilterBank
+                self._logmel = LogMelFilterBank(self.device)
+            # (the reference takes the log-mel of the TARGET utterance's waveform; an item without "target" carries it as "target_wav")
+            if any(samples[i].get("target_wav") is None for i in todo):
+                raise ValueError("an s2s item needs \"target\" (log-mel frames) or \"target_wav\" (the target utterance's waveform)")
+            packed, off = self._logmel.rows([samples[i]["target_wav"] for i in todo])
+            for k, i in enumerate(todo):
+                fbanks[i] = packed[off[k]:off[k + 1]]
+        return [f.contiguous() for f in fbanks]
+
+    @staticmethod
+    def plan(audio_sizes, fbank_sizes, r):
+        """The batch's host-side bookkeeping (Python ints; no device work): padded source length S, padded target length Lmax,
+        decoder-input length Lin -- frames r-1, 2r-1, ... of the PADDED batch behind a zero frame, which is there even when no frame
+        survives the thinning (:188-197) --, the per-item decoder-input lengths L // r (:191) and ntokens = the summed source sizes."""
+        Lmax = max(fbank_sizes)
+        return dict(S=max(audio_sizes), Lmax=Lmax, Lin=max(len(range(r - 1, Lmax, r)), 1), tgt_lengths=[l // r for l in fbank_sizes],
+                    ntokens=int(sum(audio_sizes)))
+
+    def collater(self, samples):
+        samples = [s for s in samples if s["source"] is not None]
+        if not samples:
+            return {}
+        dev, B, r = self.device, len(samples), self.reduction_factor
+        audios = [s["source"].contiguous() for s in samples]
+        fbanks = self._fbanks(samples)
+        assert all(a.dtype == torch.float32 and a.is_cuda for a in audios) and all(f.dtype == torch.float32 and f.is_cuda for f in fbanks)
+        audio_sizes, sizes = [int(a.shape[0]) for a in audios], [int(f.shape[0]) for f in fbanks]
+        p = self.plan(audio_sizes, sizes, r)
+        source = _ragged(audios, [0] * B, audio_sizes, B, p["S"], 1, 1, 0, torch.float32, 0.0, dev)
+        padding_mask = _tail(audio_sizes, B, p["S"], False, dev)
+        odim = int(fbanks[0].shape[1])
+        dec_target = _ragged(fbanks, [0] * B, sizes, B, p["Lmax"], odim, 1, 0, torch.float32, 0.0, dev)
+        dec_lengths = _lengths(sizes, dev)
+        prev = _ragged(fbanks, [-1] * B, sizes, B, p["Lin"], odim, r, 1, torch.float32, 0.0, dev)
+        tgt_lengths = _lengths(p["tgt_lengths"], dev) if r > 1 else dec_lengths
+        labels = _tail([l - 1 for l in sizes], B, p["Lmax"], True, dev)            # (:200-202: 1.0 from the last frame on)
+        spk = [s["spkembs"].contiguous() for s in samples]
+        spkembs = _ragged(spk, [0] * B, [int(v.shape[0]) for v in spk], B, max(int(v.shape[0]) for v in spk), 1, 1, 0, torch.float32, 0.0, dev)
+        net_input = {"source": source, "padding_mask": padding_mask, "prev_output_tokens": prev, "tgt_lengths": tgt_lengths,
+                     "spkembs": spkembs, "task_name": "s2s"}
+        return {"id": torch.LongTensor([s["id"] for s in samples]), "name": [s["audio_name"] for s in samples],
+                "tgt_name": [s["tgt_name"] for s in samples], "net_input": net_input, "labels": labels, "dec_target": dec_target,
+                "dec_target_lengths": dec_lengths, "src_lengths": torch.LongTensor(audio_sizes), "task_name": "s2s",
+                "ntokens": p["ntokens"], "target": dec_target}
+
+    __call__ = collater
+
+
 class TextPretrainCollater:
     """collate() of data/text_dataset.py:18-99 (TextPretrainDataset.collater :435-444): source / target right-padded, the batch sorted by
     descending SOURCE length (the reference's own torch sort on the host lengths: the tie order is part of the batch), the decoder

@@ -127,6 +127,12 @@ class TexttoSpeechLoss(nn.Module):
                "sample_size": 1, "ntokens": sample["ntokens"], "nsentences": sample["target"].size(0)}
         if ga is not None:
             log["enc_dec_attn_loss"] = _item(ga, s)
+        # (:142-146) the scaled positional encodings' alphas, what reduce_metrics reports as <task>_encoder_alpha / _decoder_alpha
+        if hasattr(model, "text_encoder_prenet"):
+            log["encoder_alpha"] = _item(model.text_encoder_prenet.encoder_prenet[-1].alpha, s)
+            log["decoder_alpha"] = _item(model.speech_decoder_prenet.decoder_prenet[-1].alpha, s)
+        elif hasattr(model, "speech_encoder_prenet"):
+            log["decoder_alpha"] = _item(model.speech_decoder_prenet.decoder_prenet[-1].alpha, s)
         return loss, 1, log
 
     def compute_loss(self, model, net_output, sample):

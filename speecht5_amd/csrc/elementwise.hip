@@ -1,5 +1,6 @@
 // Element-wise, gather/scatter and small reduction kernels of the SpeechT5 hot path (HBM-bound;
 // 16-byte vector IO, grid-stride).  Each replaces a torch call site cited in include/speecht5_hip.h.
+#include <initializer_list>
 #include <mutex>
 #include "common.h"
 #include "../../include/speecht5_hip.h"
@@ -1076,6 +1077,130 @@ extern "C" int st5_tail_mask(const int32_t* n, void* out, int32_t B, int32_t T, 
   if (blocks > 65535) blocks = 65535;
   hipLaunchKernelGGL(tail_mask_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, n, dtype_f32 ? nullptr : (uint8_t*)out,
                      dtype_f32 ? (float*)out : nullptr, T, total);
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+
+// ---- speech enhancement output (s2s, --se-predict; SpeechT5/speecht5/models/speecht5.py:937-953) ----------------------------------
+// The post-net's two outputs combined with the source features: masking y = sigmoid(x) * src, delta y = x - src.  One launch walks
+// `before` and `after` together (they share src); 16-byte vectors over the aligned body, scalars over the tail (and over everything
+// when a pointer is not 16-byte aligned).
+namespace {
+// Same operations in the same order as the reference's torch expression and its autograd: s = 1 / (1 + exp(-x)), y = s * src,
+// dx = ((dy * src) * (1 - s)) * s, with s recomputed from x (nothing saved); 1 - s rounds to 0 for x >~ 17 and s underflows for
+// x <~ -88, so the gradient dies out quietly in both tails.
+__device__ __forceinline__ float se_sigmoid(float x) { return 1.f / (1.f + expf(-x)); }
+__device__ __forceinline__ float se_fwd(int mode, float x, float s) { return mode == 0 ? se_sigmoid(x) * s : x - s; }
+__device__ __forceinline__ float se_bwd(int mode, float dy, float x, float src) {
+  if (mode != 0) return dy;
+  const float s = se_sigmoid(x);
+  return ((dy * src) * (1.f - s)) * s;
+}
+__global__ __launch_bounds__(256) void se_predict_fwd_kernel(const float* __restrict__ xa, const float* __restrict__ xb,
+                                                             const float* __restrict__ src, float* __restrict__ ya, float* __restrict__ yb,
+                                                             long long n, long long nv, int mode) {
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long long)gridDim.x * blockDim.x;
+  for (long long i = tid; i < nv; i += nthr) {
+    const f32x4 a = reinterpret_cast<const f32x4*>(xa)[i], b = reinterpret_cast<const f32x4*>(xb)[i], s = reinterpret_cast<const f32x4*>(src)[i];
+    f32x4 oa, ob;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { oa[e] = se_fwd(mode, a[e], s[e]); ob[e] = se_fwd(mode, b[e], s[e]); }
+    reinterpret_cast<f32x4*>(ya)[i] = oa;
+    reinterpret_cast<f32x4*>(yb)[i] = ob;
+  }
+  for (long long i = nv * 4 + tid; i < n; i += nthr) {
+    const float s = src[i];
+    ya[i] = se_fwd(mode, xa[i], s);
+    yb[i] = se_fwd(mode, xb[i], s);
+  }
+}
+__global__ __launch_bounds__(256) void se_predict_bwd_kernel(const float* __restrict__ da, const float* __restrict__ db,
+                                                             const float* __restrict__ xa, const float* __restrict__ xb,
+                                                             const float* __restrict__ src, float* __restrict__ ga, float* __restrict__ gb,
+                                                             long long n, long long nv, int mode) {
+  const long long tid = (long long)blockIdx.x * blockDim.x + threadIdx.x, nthr = (long long)gridDim.x * blockDim.x;
+  for (long long i = tid; i < nv; i += nthr) {
+    const f32x4 a = reinterpret_cast<const f32x4*>(xa)[i], b = reinterpret_cast<const f32x4*>(xb)[i], s = reinterpret_cast<const f32x4*>(src)[i];
+    const f32x4 va = reinterpret_cast<const f32x4*>(da)[i], vb = reinterpret_cast<const f32x4*>(db)[i];
+    f32x4 oa, ob;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) { oa[e] = se_bwd(mode, va[e], a[e], s[e]); ob[e] = se_bwd(mode, vb[e], b[e], s[e]); }
+    reinterpret_cast<f32x4*>(ga)[i] = oa;
+    reinterpret_cast<f32x4*>(gb)[i] = ob;
+  }
+  for (long long i = nv * 4 + tid; i < n; i += nthr) {
+    const float s = src[i];
+    ga[i] = se_bwd(mode, da[i], xa[i], s);
+    gb[i] = se_bwd(mode, db[i], xb[i], s);
+  }
+}
+inline bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps) if ((uintptr_t)p & 15u) return false;
+  return true;
+}
+
+// ---- ragged log-mel framing: st5_stft_frames over B waveforms of different lengths, frames packed item after item ----
+// Thread = 4 consecutive samples of one frame (one 16-byte store); the item of a packed frame row is found by bisection in
+// frame_off [B + 1]; reflection happens at the item's own ends.
+__global__ __launch_bounds__(256) void stft_frames_rows_kernel(const float* const* __restrict__ wav, const int32_t* __restrict__ len,
+                                                               const int64_t* __restrict__ frame_off, float* __restrict__ out, int B,
+                                                               int n_fft, int hop, long long total4) {
+  const int q = n_fft / 4;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < total4; i += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(i % q) * 4;
+    const long long row = i / q;
+    int lo = 0, hi = B;                      // frame_off[lo] <= row < frame_off[hi]
+    while (hi - lo > 1) {
+      const int mid = (lo + hi) >> 1;
+      if (frame_off[mid] <= row) lo = mid; else hi = mid;
+    }
+    const int S = len[lo];
+    const float* __restrict__ w = wav[lo];
+    const int t0 = (int)(row - frame_off[lo]) * hop + j - n_fft / 2;
+    f32x4 v;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      int t = t0 + e;
+      t = t < 0 ? -t : t;
+      t = t >= S ? 2 * (S - 1) - t : t;
+      t = t < 0 ? 0 : (t >= S ? S - 1 : t);  // (never taken for S > n_fft / 2 and L = 1 + S / hop: keeps a bad table in bounds)
+      v[e] = w[t];
+    }
+    reinterpret_cast<f32x4*>(out)[i] = v;
+  }
+}
+}  // namespace
+
+extern "C" int st5_se_predict_fwd(const float* before, const float* after, const float* src, float* out_before, float* out_after,
+                                  int64_t n, int32_t mode, void* stream) {
+  if (!before || !after || !src || !out_before || !out_after || n < 0 || (mode != ST5_SE_MASKING && mode != ST5_SE_DELTA)) return ST5_ERR_ARG;
+  if (n == 0) return ST5_OK;
+  const long long nv = aligned16({before, after, src, out_before, out_after}) ? n / 4 : 0;
+  hipLaunchKernelGGL(se_predict_fwd_kernel, grid_for(nv + (n - nv * 4)), dim3(256), 0, (hipStream_t)stream, before, after, src, out_before,
+                     out_after, (long long)n, nv, mode);
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+extern "C" int st5_se_predict_bwd(const float* d_before, const float* d_after, const float* before, const float* after, const float* src,
+                                  float* g_before, float* g_after, int64_t n, int32_t mode, void* stream) {
+  if (!d_before || !d_after || !before || !after || !src || !g_before || !g_after || n < 0 || (mode != ST5_SE_MASKING && mode != ST5_SE_DELTA))
+    return ST5_ERR_ARG;
+  if (n == 0) return ST5_OK;
+  const long long nv = aligned16({d_before, d_after, before, after, src, g_before, g_after}) ? n / 4 : 0;
+  hipLaunchKernelGGL(se_predict_bwd_kernel, grid_for(nv + (n - nv * 4)), dim3(256), 0, (hipStream_t)stream, d_before, d_after, before, after,
+                     src, g_before, g_after, (long long)n, nv, mode);
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+
+extern "C" int st5_stft_frames_rows(const float* const* wav, const int32_t* len, const int64_t* frame_off, float* out, int32_t B,
+                                    int64_t total_frames, int32_t n_fft, int32_t hop, void* stream) {
+  if (!wav || !len || !frame_off || !out || B <= 0 || total_frames < 0 || n_fft <= 0 || n_fft % 4 || hop <= 0) return ST5_ERR_ARG;
+  if ((uintptr_t)out & 15u) return ST5_ERR_ALIGN;
+  if (total_frames == 0) return ST5_OK;
+  const long long total4 = (long long)total_frames * (n_fft / 4);
+  hipLaunchKernelGGL(stft_frames_rows_kernel, grid_for(total4), dim3(256), 0, (hipStream_t)stream, wav, len, frame_off, out, B, n_fft, hop,
+                     total4);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }

@@ -2,9 +2,9 @@
 
 The reference's data plane -- manifests, audio decoding, librosa features, tokenisation, batching by size -- stays its own CPU code
 (task.load_dataset runs the plug-in's `load_dataset`).  What moves is the step that builds the batch tensors: `GpuCollated(dataset,
-device)` wraps one of the five dataset classes of /root/reference/SpeechT5/speecht5/data/ (speech_dataset.SpeechPretrainDataset,
+device)` wraps one of the six dataset classes of /root/reference/SpeechT5/speecht5/data/ (speech_dataset.SpeechPretrainDataset,
 text_to_speech_dataset.TextToSpeechDataset, speech_to_text_dataset.SpeechToTextDataset, speech_to_class_dataset.SpeechToClassDataset,
-text_dataset.TextPretrainDataset) -- or anything
+speech_to_speech_dataset.SpeechToSpeechDataset, text_dataset.TextPretrainDataset) -- or anything
 with their attributes -- so that `__getitem__` is the dataset's own (its tensors moved to the device once, per item) and `collater` is
 the ragged-gather collater of speecht5_amd.collate, configured from the dataset's attributes.  Every other attribute (sizes,
 ordered_indices, num_tokens, set_epoch ...) is the wrapped dataset's.  `wrap_datasets` does it for a MultitaskDataset's members in place
@@ -31,6 +31,8 @@ def _collater_for(ds, device):
         return C.SpeechPretrainCollater(device, sample_rate=ds.sample_rate, label_rates=ds.label_rates, pad_list=ds.pad_list,
                                         max_sample_size=ds.max_sample_size, pad_audio=ds.pad_audio, random_crop=ds.random_crop,
                                         reduction_factor=ds.reduction_factor, single_target=getattr(ds, "single_target", False))
+    if name == "SpeechToSpeechDataset" or (hasattr(ds, "tgt_audios") and hasattr(ds, "reduction_factor")):
+        return C.SpeechToSpeechCollater(device, reduction_factor=ds.reduction_factor)
     if name == "TextToSpeechDataset" or (hasattr(ds, "src_dict") and hasattr(ds, "reduction_factor")):
         return C.TextToSpeechCollater(device, pad_idx=ds.src_dict.pad(), reduction_factor=ds.reduction_factor)
     if name == "SpeechToClassDataset" or (hasattr(ds, "tgt_dict") and hasattr(ds, "wav_classes")):

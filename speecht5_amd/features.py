@@ -10,6 +10,7 @@ librosa on the host) as two fp32 MFMA GEMMs and three small kernels of the C ABI
 
 The Hann window is folded into the DFT basis, so the framing kernel is a pure gather.  Everything is fp32 (`st5_gemm` in
 its exact-fp32 mode): features feed the decoder targets and the MSE/L1 losses at full precision in the reference too.
+`rows` is the same pipeline for a list of waveforms of different lengths (st5_stft_frames_rows), frames packed item after item.
 """
 import math
 
@@ -72,10 +73,38 @@ class LogMelFilterBank:
             raise ValueError(f"reflect padding needs more than {self.n_fft // 2} samples, got {S}")
         L = 1 + S // self.hop
         M = B * L
-        dev = wav.device
+        frames = torch.empty(M, self.n_fft, dtype=torch.float32, device=wav.device)
+        hip.check(hip.lib().st5_stft_frames(wav.data_ptr(), frames.data_ptr(), B, S, self.n_fft, self.hop, hip.stream()), "st5_stft_frames")
+        return self._from_frames(frames).view(B, L, self.num_mels)
+
+    def rows(self, wavs):
+        """Waveforms of DIFFERENT lengths in one pass: wavs = [fp32 [S_b] on the GPU] -> (packed fp32 [sum L_b, num_mels], offsets),
+        L_b = 1 + S_b // hop, item b's frames in packed[offsets[b]:offsets[b + 1]] (offsets: B + 1 host ints).  One framing launch
+        for all items (st5_stft_frames_rows: each item reflect-padded at its own ends), then the same four launches as __call__
+        over the packed frames -- 5 launches per batch where a per-item loop makes 5 per item."""
+        assert len(wavs) > 0 and all(w.is_cuda and w.dtype == torch.float32 and w.dim() == 1 for w in wavs), "wavs: fp32 [S_b] on the GPU"
+        wavs = [w.contiguous() for w in wavs]
+        sizes = [int(w.shape[0]) for w in wavs]
+        for S in sizes:
+            if S <= self.n_fft // 2:
+                raise ValueError(f"reflect padding needs more than {self.n_fft // 2} samples, got {S}")
+        offsets = [0]
+        for S in sizes:
+            offsets.append(offsets[-1] + 1 + S // self.hop)
+        dev = wavs[0].device
+        tables = (torch.tensor([w.data_ptr() for w in wavs], dtype=torch.int64).to(dev, non_blocking=True),
+                  torch.tensor(sizes, dtype=torch.int32).to(dev, non_blocking=True),
+                  torch.tensor(offsets, dtype=torch.int64).to(dev, non_blocking=True))
+        frames = torch.empty(offsets[-1], self.n_fft, dtype=torch.float32, device=dev)
+        hip.check(hip.lib().st5_stft_frames_rows(tables[0].data_ptr(), tables[1].data_ptr(), tables[2].data_ptr(), frames.data_ptr(),
+                                                 len(wavs), offsets[-1], self.n_fft, self.hop, hip.stream()), "st5_stft_frames_rows")
+        frames._st5_keep = tables + (wavs,)      # the tables (and the items) live until the kernel has run on this stream
+        return self._from_frames(frames), offsets
+
+    def _from_frames(self, frames):
+        """frames fp32 [M, n_fft] -> log10-mel fp32 [M, num_mels]: DFT GEMM, magnitude, mel GEMM, log10."""
+        M, dev = frames.shape[0], frames.device
         lib, st = hip.lib(), hip.stream()
-        frames = torch.empty(M, self.n_fft, dtype=torch.float32, device=dev)
-        hip.check(lib.st5_stft_frames(wav.data_ptr(), frames.data_ptr(), B, S, self.n_fft, self.hop, st), "st5_stft_frames")
         reim = torch.empty(M, 2 * self.ldh, dtype=torch.float32, device=dev)
         hip.gemm(hip.operand(frames, self.n_fft), hip.operand(self.basis, self.n_fft), hip.operand(reim, 2 * self.ldh),
                  M, 2 * self.ldh, self.n_fft, hip.F32)
@@ -86,4 +115,4 @@ class LogMelFilterBank:
                  M, self.num_mels, self.ldh, hip.F32)
         out = torch.empty_like(mel)
         hip.check(lib.st5_log10_floor(mel.data_ptr(), out.data_ptr(), mel.numel(), self.eps, st), "st5_log10_floor")
-        return out.view(B, L, self.num_mels)
+        return out

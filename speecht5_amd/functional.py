@@ -3931,3 +3931,44 @@ class TimeMeanFunction(torch.autograd.Function):
 
 def time_mean(x):
     return TimeMeanFunction.apply(x)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Speech enhancement output (s2s, --se-predict; speecht5.py:937-953): masking / delta of the post-net's two outputs against the source
+# features, both tensors in one launch (csrc/elementwise.hip st5_se_predict_*)
+# ---------------------------------------------------------------------------------------------------------------------------------
+SE_MASKING, SE_DELTA = 0, 1
+
+
+class SePredictFunction(torch.autograd.Function):
+    """(before, after, src) fp32 [B, L, odim], same shape -> (sigmoid(before) * src, sigmoid(after) * src) or (before - src,
+    after - src).  src is data: no gradient.  The backward recomputes the sigmoid from the saved inputs."""
+
+    @staticmethod
+    def forward(ctx, before, after, src, mode):
+        for name, t in (("before", before), ("after", after), ("src", src)):
+            if not (t.is_cuda and t.dtype == torch.float32):
+                raise RuntimeError(f"se_predict: {name} must be fp32 on the GPU (csrc/elementwise.hip), got {t.dtype} on {t.device}")
+        if not (before.shape == after.shape == src.shape):
+            raise RuntimeError(f"se_predict: shapes differ: before {tuple(before.shape)}, after {tuple(after.shape)}, src {tuple(src.shape)}")
+        before, after, src = before.contiguous(), after.contiguous(), src.contiguous()
+        yb, ya = torch.empty_like(before), torch.empty_like(after)
+        hip.check(hip.lib().st5_se_predict_fwd(before.data_ptr(), after.data_ptr(), src.data_ptr(), yb.data_ptr(), ya.data_ptr(),
+                                               before.numel(), mode, hip.stream()), "st5_se_predict_fwd")
+        ctx.save_for_backward(before, after, src)
+        ctx.mode = mode
+        return yb, ya
+
+    @staticmethod
+    def backward(ctx, db, da):
+        before, after, src = ctx.saved_tensors
+        db = torch.zeros_like(before) if db is None else db.contiguous().float()
+        da = torch.zeros_like(after) if da is None else da.contiguous().float()
+        gb, ga = torch.empty_like(before), torch.empty_like(after)
+        hip.check(hip.lib().st5_se_predict_bwd(db.data_ptr(), da.data_ptr(), before.data_ptr(), after.data_ptr(), src.data_ptr(),
+                                               gb.data_ptr(), ga.data_ptr(), before.numel(), ctx.mode, hip.stream()), "st5_se_predict_bwd")
+        return gb, ga, None, None
+
+
+def se_predict(before, after, src, mode):
+    return SePredictFunction.apply(before, after, src, mode)

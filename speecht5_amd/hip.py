@@ -174,6 +174,7 @@ _SIGS = {
     "st5_stft_frames": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p]),
     "st5_stft_magnitude": (c_int, [c_void_p, c_void_p, c_int64, c_int32, c_int32, c_void_p]),
     "st5_log10_floor": (c_int, [c_void_p, c_void_p, c_int64, c_float, c_void_p]),
+    "st5_stft_frames_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_int32, c_int32, c_void_p]),
     "st5_cross_entropy": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
                                   c_float, c_int32, c_float, c_int, c_void_p]),
     "st5_cross_entropy_rows": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int64,
@@ -271,6 +272,8 @@ _SIGS = {
                                        c_float, c_void_p]),
     "st5_time_mean_fwd": (c_int, [c_void_p, c_int64, c_int64, c_int32, c_int32, c_int32, c_void_p, c_int, c_void_p]),
     "st5_time_mean_bwd": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int, c_void_p]),
+    "st5_se_predict_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
+    "st5_se_predict_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_void_p]),
     "st5_multi_transpose_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p]),
     "st5_batchnorm_ws_bytes": (c_int64, [c_int32]),
     "st5_batchnorm_act_fwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int32, c_int32,

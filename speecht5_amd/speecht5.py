@@ -338,6 +338,16 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
 
         if task_name is not None and task_name == "s2c":   # (:925-928) decoder pooling
             return self.speaker_decoder_postnet(self._time_mean_btc(decoder_output), sid_target), None
+        # (:936-952) speech enhancement: the post-net's outputs as a mask on / a delta to the source features (reduction factor 1)
+        if task_name is not None and task_name == "s2s" and getattr(self.args, "se_predict", None) is not None:
+            assert self.reduction_factor == 1, f"{self.reduction_factor} != 1"
+            before_outs, after_outs, logits = self.speech_decoder_postnet(decoder_output)
+            se_predict = getattr(self.args, "se_predict")
+            if se_predict in ("masking", "delta"):
+                before_outs, after_outs = self._se_combine(before_outs, after_outs, src_tokens, se_predict)
+            elif se_predict != "target":
+                raise ValueError(f"{se_predict} not in [masking, target, delta]")
+            return before_outs, after_outs, logits, extra["attn"][0]
         if task_name is not None and task_name == "s2t":
             return (self.text_decoder_postnet(decoder_output), None), encoder_output
         if output_type == "text":
@@ -447,6 +457,20 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
         if incremental_state is not None:
             out = out[:, -1:]
         return out, extra
+
+    @staticmethod
+    def _se_combine(before_outs, after_outs, src_tokens, se_predict):
+        """sigmoid(outs) * src_tokens (masking) or outs - src_tokens (delta) for both post-net outputs in one launch (st5_se_predict_*).
+        src_tokens broadcasts against the outputs as in the reference's torch expression; a shape that does not (or that would
+        enlarge the outputs) raises, before any kernel sees it."""
+        if src_tokens is None:
+            raise TypeError("--se-predict masking / delta needs src_tokens (the source features) in net_input")
+        shape = tuple(before_outs.shape)
+        if tuple(torch.broadcast_shapes(shape, tuple(src_tokens.shape))) != shape:
+            raise RuntimeError(f"src_tokens {tuple(src_tokens.shape)} does not broadcast to the decoder output {shape}")
+        src = Fn.as_float(src_tokens).expand(shape)
+        mode = Fn.SE_MASKING if se_predict == "masking" else Fn.SE_DELTA
+        return Fn.se_predict(Fn.as_float(before_outs), Fn.as_float(after_outs), src, mode)
 
     def _zero_decoder_input(self, prev_output_tokens):
         """Zero decoder input [B, T, C] in the compute dtype (s2c uses a zero vector as [CLS]) and the pre-net's padding mask."""
