@@ -1,21 +1,16 @@
 """ASR beam search with the step index on the device (SequenceGenerator(decode="device")) and replayed from a HIP graph
-(decode="graph"), on the pattern of tts_graph.py.
+(decode="graph"); the mechanism (step program, layer sequence, replay loop) is step_program.py.
 
-One step is a fixed sequence of kernel launches on caller-owned buffers: the text decoder pre-net's newest row
-(st5_beam_embed_step), the decoder layers over the slot state (TransformerDecoder.beam_slots_device_step: every GEMM on the
-weight-streaming skinny-M kernel, the self-attention K|V written into slot `counter` through that kernel's device-side output
-offset), the optional final LayerNorm, the tied output projection with fp32 output, the beam step (st5_beam_step: log-softmax, rules,
-candidates, EOS logic, finalisation into per-sentence records, the next tokens; it advances the counter) and the in-place ancestry
-reorder (st5_beam_reorder_dev).  Every launch reads ONE int32 counter in device memory.  Nothing in the step depends on a host
-value, allocates, or builds a weight image, so the same sequence is enqueued kernel by kernel ("device") or captured once and
-replayed ("graph").  Finished sentences are NOT removed from the batch: their rows keep running and their records are frozen.
+The step: the text decoder pre-net's newest row (st5_beam_embed_step), the decoder layers over the slot state (cross-attention:
+st5_beam_cross_attn over the sentence-shared K|V), the optional final LayerNorm, the tied output projection with fp32 output, the beam
+step (st5_beam_step: log-softmax, rules, candidates, EOS logic, finalisation into per-sentence records, the next tokens; it advances
+the counter) and the in-place ancestry reorder (st5_beam_reorder_dev).  Finished sentences are NOT removed from the batch: their rows
+keep running and their records are frozen.  Every buffer the graph has baked in belongs to the BeamDeviceDecode object, which
+outlives the graph.
 
 The position of the newest token is a function of the step alone, counter + padding_idx + 1: without forced prefixes no hypothesis
 contains `pad` (its log-probability is -inf at every step; `prefix_tokens` is refused), which is what SinusoidalPositionalEmbedding
 counts.
-
-The captured step has no forked stream, no parallel branch and no allocation; st5_gemm (per-stream split-K tables) is not part of
-it; every buffer the graph has baked in belongs to the BeamDeviceDecode object, which outlives the graph.
 
 Joint CTC / attention scoring (ctc_weight > 0) runs in these modes with ctc_rows=True only: no sentence leaves the batch, so row r is
 scored against sentence r // beam's own posterior and frame count for the whole call.  The step then is: pre-net row, decoder layers,
@@ -41,13 +36,10 @@ fallback has no device form), an LM with a larger dictionary than the model's (V
 lm.max_positions() (asked at generate(), where max_len is known).
 
 `attention` of the returned hypotheses is an empty tensor in these modes: no probability record is kept."""
-import gc
-
 import torch
 
 from . import functional as Fn
-from . import hip
-from .tts_graph import GRAPH_WARMUP_STEPS, decode_stream, replay_schedule
+from .step_program import StepProgram, append_layers, on_decode_stream, run_steps
 
 DECODE_MODES = ("device", "graph")
 
@@ -77,7 +69,7 @@ def check_generator(gen):
         raise ValueError(f"decode={mode!r}: a custom search_strategy is not supported (the device beam step is fairseq's BeamSearch)")
     m = gen.model.models[0]
     dec = getattr(m, "decoder", None)
-    if not hasattr(dec, "beam_slots_device_step") or not hasattr(m, "text_decoder_prenet") or not hasattr(m, "text_decoder_postnet"):
+    if not hasattr(dec, "init_beam_slots") or not hasattr(m, "text_decoder_prenet") or not hasattr(m, "text_decoder_postnet"):
         raise ValueError(f"decode={mode!r} needs a SpeechT5 text decoder with a slot API; {type(m).__name__} has none")
     dec.check_beam_slots()
     if any(l.encoder_attn is None for l in dec.layers):
@@ -110,6 +102,8 @@ class BeamDeviceDecode:
         beam, V = gen.beam_size, gen.vocab_size
         dec, pre, post = model.decoder, model.text_decoder_prenet, model.text_decoder_postnet
         st = dec.init_beam_slots(n_sent, beam, max_len + 2, encoder_out)
+        if st.xkv is None:
+            raise ValueError("device-stepped beam search needs an encoder output and decoder layers with an encoder attention")
         dev, dtype = st.bufs[0].device, Fn.compute_dtype()
         rows, C = st.rows, pre.embed_dim
         self.slots, self.gen, self.n_sent, self.max_len = st, gen, n_sent, max_len
@@ -120,30 +114,24 @@ class BeamDeviceDecode:
         self.host = torch.zeros(2, dtype=torch.int32, pin_memory=True)     # (n_finished, the CTC scorer's `unknown` flag)
         self.ctc = self._ctc_state(gen, model, encoder_out, n_sent, dev) if gen.ctc_weight > 0 else None
         self.event = torch.cuda.Event()
-        new = lambda *shape, dt=dtype: torch.empty(*shape, dtype=dt, device=dev)   # noqa: E731
-        stats = new(2 * rows, dt=torch.float32)
-        weights = []     # (every compute-dtype weight image of the step: held here, so the weight cache cannot drop one mid-call)
-        ops = []         # the step: zero-argument launches in order
-        shapes = []      # (N, K) of every skinny product, for the shared workspace
-
-        def lin(x, ws_, bs_, out, **epi):
-            w = Fn.fused_weight(list(ws_), dtype)
-            weights.append(w)
-            b = None if any(b is None for b in bs_) else Fn.fused_bias(list(bs_))
-            shapes.append(tuple(w.shape))
-            ops.append(lambda: Fn.linear_skinny(x, w, b, out=out, ws=self.ws, **epi))
-            return out
-
-        def norm(ln, x, y):
-            ops.append(lambda: Fn.layer_norm_into(x, ln.weight, ln.bias, ln.eps, y, stats))
-            return y
-
+        prog = self.prog = StepProgram(dev, dtype, rows)
+        new, lin, add = prog.new, prog.lin, prog.add
         # pre-net: embed_scale * E[token] + pos[counter + padding_idx + 1] (see the module docstring for why the step decides it)
         table = pre.embed_tokens.weight.detach()
         pos = pre.embed_positions.table(max_len + 2 + pre.padding_idx + 2, dev)
         x = new(rows, C)
-        ops.append(lambda x=x: Fn.beam_embed_step(table, bs, pos, pre.padding_idx + 1, pre.embed_scale, x))
-        x = dec.beam_slots_device_step(st, bs.counter, x, lin, norm, new, ops)
+        add(lambda x=x: Fn.beam_embed_step(table, bs, pos, pre.padding_idx + 1, pre.embed_scale, x))
+        layers = list(dec.layers)
+
+        def self_attn(q, slots, ctx, H, hd):      # positions 0 .. counter over st.bufs[0], the one ancestry table, reordered in place
+            Fn.lm_decode_attn_dev(q, slots, st.bufs[0], bs.counter, 1, st.Tmax, H, hd, ctx, st.self_ws)
+
+        def cross_attn(idx, q, ctx):              # no step dependence: nothing is recorded
+            ca, (kv, k_off) = layers[idx].encoder_attn, st.xkv[idx]
+            Fn.beam_cross_attn(q, kv, k_off, st.sent, st.n_sent, st.beam, st.S, ca.num_heads, ca.head_dim, kpm=st.kpm, ws=st.cross_ws,
+                               ctx=ctx)
+
+        x = append_layers(prog, x, layers, st.kv, st.Tmax, bs.counter, self_attn, cross_attn, dec.layer_norm)
         # tied output projection, fp32 out (no cast kernel), then the beam step and the ancestry reorder
         proj = post.output_projection
         self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
@@ -153,28 +141,26 @@ class BeamDeviceDecode:
         self.lm_state = self.lm_logits = self.lp = None
         if lm is not None:
             self.lm_state = lm.init_decode(rows, max_len + 2, anc=st.bufs[0])
-            self.lm_logits = lm.device_step(self.lm_state, bs, lin, norm, new, ops)
+            self.lm_logits = lm.device_step(self.lm_state, bs, prog)
         if self.ctc is None and lm is None:
-            ops.append(lambda: Fn.beam_step(self.logits, V, bs, self.never, self.len_div, **rules))
+            add(lambda: Fn.beam_step(self.logits, V, bs, self.never, self.len_div, **rules))
         elif self.ctc is None:
             # log-probabilities with the LM term, the beam step on them
             self.lp = new(rows, V, dt=torch.float32)
-            ops.append(lambda: Fn.beam_lm_logprobs(self.lp, V, bs, self.lm_logits, w_lm, logits=self.logits, temperature=gen.temperature))
-            ops.append(lambda: Fn.beam_step(self.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
+            add(lambda: Fn.beam_lm_logprobs(self.lp, V, bs, self.lm_logits, w_lm, logits=self.logits, temperature=gen.temperature))
+            add(lambda: Fn.beam_step(self.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
         else:
             # log-probabilities and candidates, prefix scores mixed into them, the LM term, the beam step on them, the continued rows'
             # prefix states
             ctc = self.ctc
-            ops.append(lambda: Fn.beam_ctc_candidates(self.logits, V, bs, ctc, self.never, gen.temperature))
-            ops.append(lambda: Fn.ctc_prefix_score_rows_dev(bs, ctc))
+            add(lambda: Fn.beam_ctc_candidates(self.logits, V, bs, ctc, self.never, gen.temperature))
+            add(lambda: Fn.ctc_prefix_score_rows_dev(bs, ctc))
             if lm is not None:
-                ops.append(lambda: Fn.beam_lm_logprobs(ctc.lp, V, bs, self.lm_logits, w_lm))
-            ops.append(lambda: Fn.beam_step(ctc.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
-            ops.append(lambda: Fn.ctc_select_dev(bs, ctc))
-        ops.append(lambda: Fn.beam_reorder_dev(bs))
-        nbytes = max(int(hip.lib().st5_gemm_skinny_ws_bytes(N, K)) for N, K in shapes)
-        self.ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
-        self.ops, self.weights = ops, weights
+                add(lambda: Fn.beam_lm_logprobs(ctc.lp, V, bs, self.lm_logits, w_lm))
+            add(lambda: Fn.beam_step(ctc.lp, V, bs, self.never, self.len_div, logprobs=True, **rules))
+            add(lambda: Fn.ctc_select_dev(bs, ctc))
+        add(lambda: Fn.beam_reorder_dev(bs))
+        prog.finish()
 
     def _ctc_state(self, gen, model, encoder_out, n_sent, dev):
         """The CTC posterior and frame counts as _generate builds them for ctc_rows, and the step's CTC buffers."""
@@ -198,10 +184,6 @@ class BeamDeviceDecode:
         return tuple(t.data_ptr() for t in st.kv) + tuple(kv.data_ptr() for kv, _ in st.xkv) + (self.bs.records.data_ptr(),
                                                                                                   st.bufs[0].data_ptr()) + ctc + lm
 
-    def step(self):
-        for op in self.ops:
-            op()
-
     def poll(self):
         """Sentences finished after the steps enqueued so far: one pinned non-blocking copy (with CTC a second one, of the scorer's
         `unknown` flag) and an event.  KeyError, _generate's, when a hypothesis was continued outside its CTC candidates."""
@@ -214,68 +196,6 @@ class BeamDeviceDecode:
             raise KeyError("a hypothesis was extended by a token outside its CTC candidate list "
                            f"(ctc_beam={self.ctc_beam}); its prefix state does not exist")
         return int(self.host[0])
-
-    def run(self, mode, poll_steps, stats):
-        cap = self.max_len + 1                    # steps 0 .. max_len
-        graph = None
-        try:
-            for _first, n_eager, n_replay, poll in replay_schedule(cap, poll_steps, GRAPH_WARMUP_STEPS if mode == "graph" else cap):
-                if n_replay and graph is None:
-                    for _ in range(n_eager):        # (the warm-up steps in front of the capture)
-                        self.step()
-                        stats["device_steps"] += 1
-                    n_eager = 0
-                    graph = self._capture()
-                for _ in range(n_eager):
-                    self.step()
-                    stats["device_steps"] += 1
-                for _ in range(n_replay):
-                    graph.replay()
-                    stats["graph_replays"] += 1
-                if poll:
-                    stats["polls"] += 1
-                    if self.poll() == self.n_sent:
-                        break
-            else:
-                # No break: the schedule ran out, and its last group never polls (step max_len finishes every sentence, so a polled
-                # group in front of it that saw them all would have broken out).  The steps behind the last poll may have set
-                # `unknown`: read it once more.  Not an extra synchronisation of every call (a call that ends at a poll does not get
-                # here; finalized() synchronises next anyway), and not counted in stats["polls"], which counts the schedule's polls.
-                if self.ctc is not None:
-                    self.poll()
-        finally:
-            if graph is not None:
-                # released here, with nothing in flight: a CUDAGraph must never be destroyed inside a later capture
-                torch.cuda.current_stream().synchronize()
-                graph.reset()
-                del graph
-
-    def _capture(self):
-        stream = torch.cuda.current_stream()
-        stream.synchronize()
-        # A graph object freed by the cyclic collector DURING a capture aborts the process.  The collector is switched off for the
-        # capture's duration instead of being run in front of it: a full gc.collect() is 26 ... 32 ms per call beside a Base model, the
-        # capture itself 1 ... 2 ms.
-        gc_was_on = gc.isenabled()
-        gc.disable()
-        try:
-            graph = torch.cuda.CUDAGraph()
-            # capture_begin / capture_end directly: the step allocates nothing, so the capture needs no memory pool of its own.  The
-            # capture ENQUEUES nothing: the captured step runs for the first time at its first replay.
-            graph.capture_begin(capture_error_mode="thread_local")
-            try:
-                self.step()
-            except BaseException as first:
-                try:                   # the capture is invalid by now and ending it may fail in turn: the step's error is the cause
-                    graph.capture_end()
-                except Exception:
-                    pass
-                raise first
-            graph.capture_end()
-        finally:
-            if gc_was_on:
-                gc.enable()
-        return graph
 
     def finalized(self):
         """generate()'s return value from ONE device-to-host read of the records: per sentence the hypotheses best first."""
@@ -312,25 +232,23 @@ def generate(gen, sample, prefix_tokens=None, constraints=None, bos_token=None):
     check_lm_positions(gen, max_len)
     model = gen.model.models[0]
     encoder_outs = gen.model.forward_encoder(net_input, exact_rows=True) if gen.exact_rows else gen.model.forward_encoder(net_input)
-    device = src_tokens.device
     stats = {"polls": 0, "device_steps": 0, "graph_replays": 0}
-    cur = torch.cuda.current_stream(device)
-    # "graph" never runs on the legacy NULL stream (it cannot capture); the caller's stream is ordered in front of the loop and behind it
-    side = decode_stream(model, device) if mode == "graph" else cur
-    if side != cur:
-        side.wait_stream(cur)
-    with torch.cuda.stream(side):
+    with on_decode_stream(model, src_tokens.device, mode) as caller:
         st = BeamDeviceDecode(gen, model, encoder_outs[0], n_sent, max_len, gen.eos if bos_token is None else bos_token)
         first = st.buffer_ptrs()
-        st.run(mode, gen.BEAM_POLL_STEPS, stats)
+        # steps 0 .. max_len.  When the schedule runs out, the steps behind the last poll may have set the CTC scorer's `unknown` flag
+        # (the last group never polls: step max_len finishes every sentence): read it once more.  Not an extra synchronisation of every
+        # call (a call that ends at a poll does not get here; finalized() synchronises next anyway), and not counted in stats["polls"],
+        # which counts the schedule's polls.
+        if not run_steps(st.prog.step, max_len + 1, mode, gen.BEAM_POLL_STEPS, lambda: st.poll() == n_sent, stats) and st.ctc is not None:
+            st.poll()
         out = st.finalized()
         last = st.buffer_ptrs()
-    if side != cur:
-        cur.wait_stream(side)
+    if caller is not None:
         for hyps in out:
             for h in hyps:
                 for t in (h["tokens"], h["score"], h["positional_scores"]):
-                    t.record_stream(cur)
+                    t.record_stream(caller)
     gen.beam_decode_mode = mode
     gen.beam_polls, gen.beam_device_steps, gen.beam_graph_replays = stats["polls"], stats["device_steps"], stats["graph_replays"]
     gen.beam_buffer_ptrs = (first, last)

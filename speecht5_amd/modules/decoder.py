@@ -293,51 +293,6 @@ class TransformerDecoder(FairseqIncrementalDecoder):
         return x.view(B, 1, C), {"attn": [attn if len(attn_list) <= 1 else attn_list], "inner_states": inner_states}
 
     @torch.no_grad()
-    def beam_slots_device_step(self, st, counter, x, lin, norm, new, ops):
-        """The decoder's share of one DEVICE-STEPPED decode step over the slot state `st` (beam_graph.BeamDeviceDecode): appends to
-        `ops` the zero-argument launches that take x [rows, C] (the newest position of every hypothesis row) through the layers and
-        the final LayerNorm, and returns the buffer that holds the result.  Position = the int32 device scalar `counter`: K|V go to
-        slot `counter` through the skinny GEMM's device-side output offset, the self-attention reads positions 0 .. counter over
-        st.bufs[0] (the one ancestry table of this mode, reordered in place), the cross-attention has no step dependence (nothing is
-        recorded).  lin(x, weights, biases, out, **epilogue) / norm(layer_norm, x, y) / new(*shape) are the caller's launch builders:
-        every buffer is the caller's and nothing is allocated per step."""
-        if st.xkv is None:
-            raise ValueError("device-stepped beam search needs an encoder output and decoder layers with an encoder attention")
-        rows, Tmax, anc = st.rows, st.Tmax, st.bufs[0]
-        for idx, layer in enumerate(self.layers):
-            nb = layer.normalize_before
-            sa, ca = layer.self_attn, layer.encoder_attn
-            H, hd, C = sa.num_heads, sa.head_dim, sa.embed_dim
-            slots = st.kv[idx]
-            h = norm(layer.self_attn_layer_norm, x, new(rows, C)) if nb else x
-            q = lin(h, [sa.q_proj.weight], [sa.q_proj.bias], new(rows, C))
-            lin(h, [sa.k_proj.weight, sa.v_proj.weight], [sa.k_proj.bias, sa.v_proj.bias], slots, step=counter, step_stride=2 * C,
-                step_cap=Tmax, out_ld=Tmax * 2 * C)
-            ctx = new(rows, C)
-            ops.append(lambda q=q, slots=slots, ctx=ctx, H=H, hd=hd: Fn.lm_decode_attn_dev(q, slots, anc, counter, 1, Tmax, H, hd, ctx,
-                                                                                        st.self_ws))
-            x = lin(ctx, [sa.out_proj.weight], [sa.out_proj.bias], new(rows, C), residual=x)
-            if not nb:
-                x = norm(layer.self_attn_layer_norm, x, new(rows, C))
-            h = norm(layer.encoder_attn_layer_norm, x, new(rows, C)) if nb else x
-            q = lin(h, [ca.q_proj.weight], [ca.q_proj.bias], new(rows, C))
-            ctx = new(rows, C)
-            kv, k_off = st.xkv[idx]
-            ops.append(lambda q=q, kv=kv, k_off=k_off, ctx=ctx, ca=ca: Fn.beam_cross_attn(
-                q, kv, k_off, st.sent, st.n_sent, st.beam, st.S, ca.num_heads, ca.head_dim, kpm=st.kpm, ws=st.cross_ws, ctx=ctx))
-            x = lin(ctx, [ca.out_proj.weight], [ca.out_proj.bias], new(rows, C), residual=x)
-            if not nb:
-                x = norm(layer.encoder_attn_layer_norm, x, new(rows, C))
-            h = norm(layer.final_layer_norm, x, new(rows, C)) if nb else x
-            f = lin(h, [layer.fc1.weight], [layer.fc1.bias], new(rows, layer.fc1.weight.shape[0]), act=layer.act)
-            x = lin(f, [layer.fc2.weight], [layer.fc2.bias], new(rows, C), residual=x)
-            if not nb:
-                x = norm(layer.final_layer_norm, x, new(rows, C))
-        if self.layer_norm is not None:
-            x = norm(self.layer_norm, x, new(rows, C))
-        return x
-
-    @torch.no_grad()
     def reorder_beam_slots(self, st, order, batch_idxs=None):
         """Hypothesis row r continues row order[r] of the previous step (len(order) < rows when sentences left the batch; the entries
         index the rows BEFORE the shrink): one gather of the int32 ancestry table; no key, value or encoder tensor moves.

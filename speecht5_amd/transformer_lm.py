@@ -20,8 +20,8 @@ Two ways to run it:
   position j, written once (the K / V projection GEMM writes it in place).  One int32 ancestry table anc [rows, Tmax], shared by
   all layers, says which slot row r reads at position j; a beam reorder gathers that table (st5_lm_reorder) and moves no key or
   value.  Attention of the newest position: st5_lm_decode_attn (csrc/lm_decode.hip).
-  device_step: the same step as a list of launches behind a device step counter, for the device-stepped beam search
-  (beam_graph.py): the slot caches are read through the text decoder's ancestry table, there is no reorder of the LM's own.
+  device_step: the same step as a list of launches behind a device step counter (step_program.py), for the device-stepped beam
+  search (beam_graph.py): the slot caches are read through the text decoder's ancestry table, there is no reorder of the LM's own.
 
 Layouts it does not implement raise NotImplementedError naming the option: adaptive softmax / adaptive input, learned positions,
 layernorm_embedding, post-LN layers, no_decoder_final_norm, character embeddings, decoder_input_dim != decoder_embed_dim."""
@@ -35,6 +35,7 @@ from . import functional as Fn
 from . import hip
 from .modules.common import LayerNorm, SinusoidalPositionalEmbedding
 from .modules.transformer_layer import TransformerDecoderLayer
+from .step_program import append_layers
 from .t5_transformer_lm import _PRESET
 
 DEFAULT_MAX_POSITIONS = 1024   # fairseq transformer_lm: max_target_positions = tokens_per_sample (1024)
@@ -262,40 +263,27 @@ class TransformerLanguageModel(nn.Module):
         return Fn.linear(x, dec.output_projection.weight, None)
 
     @torch.no_grad()
-    def device_step(self, state, bs, lin, norm, new, ops):
-        """The LM's share of one DEVICE-STEPPED beam search step (beam_graph.BeamDeviceDecode), on the pattern of
-        TransformerDecoder.beam_slots_device_step: appends to `ops` the zero-argument launches that take the newest token of every
-        hypothesis row (bs.tok[:, counter], bs: functional.BeamStepState) through the LM, and returns the buffer of the fp32 logits
-        [rows, V_lm].  `state`: init_decode(rows, Tmax, anc=the decoder's ancestry table).  Position = the int32 device scalar
-        bs.counter: the embedding reads position counter + padding_idx + 1, K|V go to slot `counter` through the skinny GEMM's
-        device-side output offset, the attention reads positions 0 .. counter over state.anc.  lin(x, weights, biases, out,
-        **epilogue) / norm(layer_norm, x, y) / new(*shape) are the caller's launch builders: every buffer is the caller's, nothing
-        is allocated per step and no launch depends on a host value."""
+    def device_step(self, state, bs, prog):
+        """The LM's share of one DEVICE-STEPPED beam search step (beam_graph.BeamDeviceDecode): appends to `prog`
+        (step_program.StepProgram) the launches that take the newest token of every hypothesis row (bs.tok[:, counter], bs:
+        functional.BeamStepState) through the LM, and returns the buffer of the fp32 logits [rows, V_lm].  `state`: init_decode(rows,
+        Tmax, anc=the decoder's ancestry table).  Position = the int32 device scalar bs.counter: the embedding reads position
+        counter + padding_idx + 1, the layers are step_program.append_layers without encoder attention over state.anc."""
         dec = self.decoder
-        rows, Tmax, anc, counter = state.rows, state.Tmax, state.anc, bs.counter
+        rows, Tmax = state.rows, state.Tmax
         if bs.rows != rows or bs.Tmax != Tmax:
             raise ValueError(f"device_step: a decode state of {rows} rows x {Tmax} positions beside a beam state of {bs.rows} x {bs.Tmax}")
-        H, hd = self.num_heads, self.head_dim
-        C = H * hd
         table = dec.embed_tokens.weight.detach()
         pos = dec.embed_positions.table(Tmax + dec.padding_idx + 2, table.device)
-        x = new(rows, C)
-        ops.append(lambda x=x: Fn.beam_embed_step(table, bs, pos, dec.padding_idx + 1, dec.embed_scale, x))
-        for layer, slots in zip(dec.layers, state.kv):
-            sa = layer.self_attn
-            h = norm(layer.self_attn_layer_norm, x, new(rows, C))
-            q = lin(h, [sa.q_proj.weight], [sa.q_proj.bias], new(rows, C))
-            lin(h, [sa.k_proj.weight, sa.v_proj.weight], [sa.k_proj.bias, sa.v_proj.bias], slots, step=counter, step_stride=2 * C,
-                step_cap=Tmax, out_ld=Tmax * 2 * C)
-            ctx = new(rows, C)
-            ops.append(lambda q=q, slots=slots, ctx=ctx: Fn.lm_decode_attn_dev(q, slots, anc, counter, 1, Tmax, H, hd, ctx, state.ws))
-            x = lin(ctx, [sa.out_proj.weight], [sa.out_proj.bias], new(rows, C), residual=x)
-            h = norm(layer.final_layer_norm, x, new(rows, C))
-            f = lin(h, [layer.fc1.weight], [layer.fc1.bias], new(rows, layer.fc1.weight.shape[0]), act=layer.act)
-            x = lin(f, [layer.fc2.weight], [layer.fc2.bias], new(rows, C), residual=x)
-        x = norm(dec.layer_norm, x, new(rows, C))
+        x = prog.new(rows, self.num_heads * self.head_dim)
+        prog.add(lambda: Fn.beam_embed_step(table, bs, pos, dec.padding_idx + 1, dec.embed_scale, x))
+
+        def self_attn(q, slots, ctx, H, hd):
+            Fn.lm_decode_attn_dev(q, slots, state.anc, bs.counter, 1, Tmax, H, hd, ctx, state.ws)
+
+        y = append_layers(prog, x, list(dec.layers), state.kv, Tmax, bs.counter, self_attn, final_norm=dec.layer_norm)
         proj = dec.output_projection
-        return lin(x, [proj.weight], [None], new(rows, proj.weight.shape[0], dt=torch.float32), out_f32=True)
+        return prog.lin(y, [proj.weight], [None], prog.new(rows, proj.weight.shape[0], dt=torch.float32), out_f32=True)
 
     @torch.no_grad()
     def reorder(self, state, order):

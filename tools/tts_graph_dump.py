@@ -2,8 +2,10 @@
 trees (the default path must keep its bits): prints one SHA-256 per (dtype, entry point) over every returned tensor.
 
     python tools/tts_graph_dump.py > dump.txt        # run on both trees, then diff the two files
+    python tools/tts_graph_dump.py --decode device graph > dump.txt      # the same for the device-stepped modes
 
 Tiny golden model and tiny golden vocoder, text rows and speech rows, pre-net dropout 0.5 under Fn.manual_seed, fp32 and bf16."""
+import argparse
 import hashlib
 import os
 import sys
@@ -25,6 +27,13 @@ def digest(outs):
 
 
 def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
+    ap.add_argument("--decode", nargs="+", default=["eager"], choices=["eager", "device", "graph"])
+    for mode in ap.parse_args().decode:
+        dump({} if mode == "eager" else {"decode": mode}, "" if mode == "eager" else f"decode={mode} ")
+
+
+def dump(kw, tag):
     from speecht5_amd.hifigan import SpeechT5HifiGan
     from tests.util import build_tiny, load_golden
     dev = torch.device("cuda:0")
@@ -53,10 +62,13 @@ def main():
             for p in (0.0, 0.5):
                 tac.dropout_rate = p
                 Fn.manual_seed(1234)
-                print(dname, f"dropout={p}", "generate_speech_batch text  ", digest(model.generate_speech_batch(src_tokens=toks, spkembs=spk)))
-                print(dname, f"dropout={p}", "generate_speech_batch speech", digest(model.generate_speech_batch(source=src, padding_mask=pad, spkembs=spk)))
-                print(dname, f"dropout={p}", "synthesize_batch            ",
-                      digest(model.synthesize_batch(src_tokens=toks, spkembs=spk, vocoder=voc, need_attn=True)), "vocoder" if voc else "no vocoder")
+                print(tag + dname, f"dropout={p}", "generate_speech_batch text  ",
+                      digest(model.generate_speech_batch(src_tokens=toks, spkembs=spk, **kw)))
+                print(tag + dname, f"dropout={p}", "generate_speech_batch speech",
+                      digest(model.generate_speech_batch(source=src, padding_mask=pad, spkembs=spk, **kw)))
+                print(tag + dname, f"dropout={p}", "synthesize_batch            ",
+                      digest(model.synthesize_batch(src_tokens=toks, spkembs=spk, vocoder=voc, need_attn=True, **kw)),
+                      "vocoder" if voc else "no vocoder")
         Fn.weight_cache.clear()
     Fn.set_compute_dtype(torch.float32)
 
