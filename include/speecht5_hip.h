@@ -912,6 +912,21 @@ int st5_word_ids(const uint8_t* p_bytes, const int32_t* p_start, const int32_t* 
 int st5_edit_distance_rows(const int32_t* a, const int32_t* a_len, int32_t La, const int32_t* b, const int32_t* b_len, int32_t Lb,
                            int32_t B, int32_t* dist, void* stream);
 
+/* ---- batch load: the tensor leaves of an update's micro-batches copied into the captured step's static inputs by one launch
+ *      (csrc/batch_load.hip, index arithmetic in csrc/batch_load_index.h; speecht5_amd/graph.py BatchFeed).
+ * All four arrays live in DEVICE memory.  dst [n_leaves] (destination addresses), bytes [n_leaves] (byte counts >= 0) and
+ *   prefix [n_leaves + 1] (exclusive prefix of ceil(bytes / 256), prefix[0] = 0, prefix[n_leaves] = total_chunks) are written once by
+ *   the caller and constant afterwards; src [n_leaves] (source addresses) is the only thing that changes between launches.
+ * Contract: the kernel trusts the table.  The caller guarantees that every source and destination is a device allocation of at
+ *   least bytes[i] bytes that stays alive until the launch has completed, that no destination overlaps another destination or any
+ *   source, and that prefix and total_chunks follow from bytes as stated; n_leaves and total_chunks are launch arguments, and no
+ *   other size is read from anything the incoming batch wrote.  A leaf of zero bytes has no chunk and its addresses are never read.
+ * Any alignment is accepted: a lane moves 16 bytes at once when its source and destination are both 16-byte aligned, else (and in
+ *   a leaf's tail) byte by byte.  No atomics, no LDS.  total_chunks == 0: nothing is launched.  n_leaves < 0, total_chunks < 0, a
+ *   NULL array with work to do: ST5_ERR_ARG. */
+int st5_batch_load(const void* const* src, const void* const* dst, const int64_t* bytes, const int64_t* prefix, int32_t n_leaves,
+                   int64_t total_chunks, void* stream);
+
 const char* st5_version(void);
 
 #ifdef __cplusplus

@@ -85,6 +85,9 @@ class SpeechPretrainCollater:
             starts.append(int(np.random.randint(0, diff + 1)) if (diff > 0 and self.random_crop) else 0)
         source = _ragged(audios, starts, audio_sizes, B, audio_size, 1, 1, 0, torch.float32, 0.0, dev)
         padding_mask = _tail(audio_sizes, B, audio_size, False, dev)
+        # the same mask on the host, from the lengths that are host ints anyway: the span-mask draw reads it (functional.host_mirror)
+        # without a device->host read, and the batch feed of a replayed update takes it as the batch's mirror
+        padding_mask._st5_host = torch.arange(audio_size)[None, :] >= torch.tensor(audio_sizes, dtype=torch.long)[:, None]
         # log-mel targets: the frames that belong to the cropped audio (:325-331), padded to the longest
         f_lo, f_hi = [], []
         for i in range(B):

@@ -251,6 +251,39 @@ def static_shapes():
     return staging.mode is not None or _S.force_static
 
 
+def host_mirror(t):
+    """The host copy of a sample tensor whose VALUES steer host-side producers (the speech padding mask: the span-mask draw runs over
+    each row's valid frames).  It rides on the tensor as `_st5_host`: the collater attaches it (it has the lengths on the host), the
+    batch feed of a replayed update (graph.BatchFeed) re-points it at every pull -- so a producer that runs again before every replay
+    must call this each time it runs, never keep what it returned at record time.  Without either, one device->host read, remembered
+    on the tensor (a recorded / replayed step without a feed keeps the same sample tensors)."""
+    h = getattr(t, "_st5_host", None)
+    if h is None:
+        h = t.cpu()
+        t._st5_host = h
+    return h
+
+
+def batch_load_plan(nbytes):
+    """Exclusive prefix of 256-byte chunks over leaves of `nbytes` bytes (csrc/batch_load_index.h bl_chunks): [0, ..., total]."""
+    prefix = [0]
+    for n in nbytes:
+        if n < 0:
+            raise ValueError(f"a leaf of {n} bytes")
+        prefix.append(prefix[-1] + (n + 255) // 256)
+    return prefix
+
+
+def batch_load(src, dst, nbytes, prefix, n_leaves, total_chunks):
+    """st5_batch_load on the current stream: leaf i's nbytes[i] bytes from address src[i] to address dst[i]; the four int64 arrays
+    live on the device (include/speecht5_hip.h has the contract).  One launch, whatever the number of leaves."""
+    for t, n in ((src, n_leaves), (dst, n_leaves), (nbytes, n_leaves), (prefix, n_leaves + 1)):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n):
+            raise ValueError("st5_batch_load: the descriptor arrays are contiguous int64 device tensors of n_leaves (prefix: n_leaves + 1) entries")
+    hip.check(hip.lib().st5_batch_load(src.data_ptr(), dst.data_ptr(), nbytes.data_ptr(), prefix.data_ptr(), n_leaves, total_chunks,
+                                       hip.stream()), "st5_batch_load")
+
+
 def set_grad_ready_hook(fn):
     """fn(param) is called when a parameter's .grad has received its last contribution of this backward
     from this library (used to launch bucketed all-reduces while backward is still running)."""

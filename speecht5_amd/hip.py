@@ -287,6 +287,7 @@ _SIGS = {
     "st5_word_ids": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                              c_int32, c_int32, c_void_p, c_void_p, c_void_p]),
     "st5_edit_distance_rows": (c_int, [c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p]),
+    "st5_batch_load": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int64, c_void_p]),
     "st5_version": (c_char_p, []),
 }
 

@@ -136,18 +136,17 @@ class SpeechEncoderPrenet(nn.Module):
             targ_tsz = min([t.size(1) for t in target_list])
             if self.feat2tar_ratio * T > targ_tsz:
                 T = int(targ_tsz / self.feat2tar_ratio)
-        pm_host = getattr(padding_mask, "_st5_host", None)
-        if pm_host is None:
-            # one device->host read of the input padding mask, remembered on the tensor (a recorded / replayed step keeps the
-            # same sample tensors; the collater could hand over the host copy it already has the same way)
-            pm_host = padding_mask.cpu()
-            padding_mask._st5_host = pm_host
-        extra = pm_host.size(1) % T
-        pmh = pm_host[:, :-extra] if extra > 0 else pm_host
-        frame_pad_host = pmh.view(pmh.size(0), T, -1).all(-1)  # == forward_padding_mask() on the host
+        def frame_pad():
+            # the padding mask's host copy (Fn.host_mirror: the collater's, the batch feed's current one, or one device->host read
+            # remembered on the tensor), reduced to frames == forward_padding_mask() on the host.  Called by the span-mask producer
+            # every time it runs: under a batch feed the mirror is the CURRENT batch's, not the recorded one's
+            pm_host = Fn.host_mirror(padding_mask)
+            extra = pm_host.size(1) % T
+            pmh = pm_host[:, :-extra] if extra > 0 else pm_host
+            return pmh.view(pmh.size(0), T, -1).all(-1)
         pre_mask = None
-        if mask and self.mask_prob > 0 and frame_pad_host is not None:
-            pre_mask = self._sample_mask(src_tokens.size(0), T, frame_pad_host, src_tokens.device)
+        if mask and self.mask_prob > 0:
+            pre_mask = self._sample_mask(src_tokens.size(0), T, frame_pad, src_tokens.device)
         if self.feature_grad_mult > 0:
             x = self.feature_extractor(src_tokens, grad_scale=self.feature_grad_mult)  # [B, T, C]
         else:
@@ -263,17 +262,22 @@ class SpeechEncoderPrenet(nn.Module):
         return self.feature_extractor.get_out_seq_lens_tensor(src_lengths)
 
     def _sample_mask(self, B, T, frame_pad_host, device):
-        """HuBERT span mask from the numpy RNG (speech_encoder_prenet.py:237-247) -> (device bool [B,T], host copies)."""
+        """HuBERT span mask from the numpy RNG (speech_encoder_prenet.py:237-247) -> (device bool [B,T], host copies).
+        frame_pad_host: the frame padding mask on the host, or a callable that returns it -- evaluated inside the producer, which a
+        replayed step runs again before every replay."""
         box = {}
 
         def draw():
-            m = compute_mask_indices((B, T), frame_pad_host, self.mask_prob, self.hubert_mask_length, self.mask_selection,
+            fp = frame_pad_host() if callable(frame_pad_host) else frame_pad_host
+            m = compute_mask_indices((B, T), fp, self.mask_prob, self.hubert_mask_length, self.mask_selection,
                                      self.mask_other, min_masks=2, no_overlap=self.no_mask_overlap, min_space=self.mask_min_space)
-            box["mt"] = torch.from_numpy(m)
+            box["mt"], box["fp"] = torch.from_numpy(m), fp
             return box["mt"]
         dev = Fn.stage_host(draw, device)
-        if "mt" in box:   # host copies: the NCE head derives its gather indices without a device sync (eager mode)
-            dev._st5_host = (box["mt"], frame_pad_host)
+        # host copies: the NCE head derives its gather indices without a device sync (eager mode).  The static-shape form never reads
+        # them, and on the persistent buffer of a staged input they would describe the recorded step only: not attached there
+        if "mt" in box and not Fn.static_shapes():
+            dev._st5_host = (box["mt"], box["fp"])
         return dev
 
     def apply_hubert_mask(self, x, padding_mask, pre_mask=None):

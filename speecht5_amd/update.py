@@ -20,6 +20,11 @@ arithmetic: every mode produces the SAME bits, tests/test_bench_update_gpu.py an
              into three graphs and all-reduces each completed bucket range under the next one -- with micro="side_by_side" (round 6)
              both micro-batches run inside every phase on two streams and a range is summed over the two gradient buffers before it
              goes out; "one_message": one graph and one all-reduce of the whole buffer behind it; Adam follows eagerly
+
+Data: without a source every update trains on the constructor's `micro_batches` (what bench.py times).  set_source(iterable) makes
+every update train on the next element of the iterable -- a list of micro-batches with the signature of the constructor's: replayed,
+through one st5_batch_load at the head of the captured step into the constructor's tensors (graph.BatchFeed; they are overwritten);
+eagerly, directly on the batch's own tensors (DESIGN.md "Batch feed").
 """
 import os
 
@@ -79,6 +84,7 @@ class PretrainUpdate:
         self._ph = None
         self.n = 0            # update counter (fairseq's num_updates)
         self.sg = None
+        self.feed = None      # graph.BatchFeed once set_source() was called
         # Every update is enqueued on a stream of its own, never on the legacy NULL stream: on this runtime (ROCm 7.2) work issued
         # to the NULL stream from two host threads (the forward from the caller's thread, the backward from autograd's worker
         # thread) is NOT kept in issue order once another stream is busy -- measured: with the speech micro-batch on the NULL
@@ -281,7 +287,36 @@ class PretrainUpdate:
             self.opt.lr = self.lr_fn(self.n)
 
     # -- driving --------------------------------------------------------------------------------------------------------
+    def set_source(self, iterable):
+        """Every following update trains on the next element of `iterable`: a list of micro-batches with the signature (key paths,
+        shape and dtype per tensor leaf, task_name) of the constructor's.  The update pulls from it itself, on the calling thread,
+        one element per update (the two recording steps and the capture of prepare_graph() one each), always before that step's host
+        random draws; a batch the recorded step cannot take is refused with a ValueError naming the path.  When the source ends,
+        the update already prepared still runs and the following update() raises StopIteration.  For a replayed update call this
+        BEFORE prepare_graph(): the batch load is the first node of the captured step.  A later call swaps the iterable (next epoch)."""
+        from .graph import BatchFeed
+        if self.sg is not None and self.sg.feed is None:
+            raise RuntimeError("set_source() after prepare_graph(): the batch load is the first node of the captured step and this "
+                               "graph was captured without it")
+        if self.feed is None:
+            self.feed = BatchFeed(self.micro, self.device)
+        self.feed.set_source(iterable)
+        if self.sg is not None:
+            self.sg.sched.new_source()
+
     def eager_update(self):
+        if self.feed is not None:
+            # one batch of the source, run as it is: the step reads the batch's own tensors (no copy, no static input)
+            rec = self.feed.pull(for_eager=True)
+            static, self.micro = self.micro, list(rec.batch)
+            try:
+                self._eager_update()
+            finally:
+                self.micro = static
+            return
+        self._eager_update()
+
+    def _eager_update(self):
         self.advance()
         if self.stream is None:
             self.step()
@@ -298,11 +333,11 @@ class PretrainUpdate:
             phases, between = self.phase_fns() if self.mode == "in_turn" else self.phase_fns_side_by_side()
             self.sg = StepGraph(None, opt=self.opt, model=self.model, device=self.device, on_step=self.advance,
                                 prefetch_host=self.prefetch_host, after_fn=self.finish_exchange_and_update, stream=self.stream,
-                                phases=phases, between=between)
+                                phases=phases, between=between, feed=self.feed)
         else:
             self.sg = StepGraph(self.local_part if self.split else self.step, opt=self.opt, model=self.model, device=self.device,
                                 on_step=self.advance, prefetch_host=self.prefetch_host,
-                                after_fn=self.exchange_and_update if self.split else None, stream=self.stream)
+                                after_fn=self.exchange_and_update if self.split else None, stream=self.stream, feed=self.feed)
         self.sg.record()
         self.sg.record()
         self.sg.capture()
@@ -311,6 +346,8 @@ class PretrainUpdate:
     def update(self):
         """The next update: a replay when a graph exists, else eager."""
         if self.sg is not None:
+            if self.feed is not None:      # (the source runs on the caller's stream; the replay waits for an event behind it)
+                self.feed.caller_stream = torch.cuda.current_stream(self.device)
             with torch.cuda.stream(self.sg.stream):
                 self.sg.replay()
         else:
@@ -323,6 +360,8 @@ class PretrainUpdate:
 
     def close(self):
         self.finish()
+        if self.feed is not None:
+            self.feed.held = []      # (finish() ordered the caller's stream behind the last replay that read them)
         self.ddp.close()
         if self.sg is not None:      # break the cycle update -> graph -> bound step function -> update: a HIP graph object must
             self.sg.step_fn = self.sg.after_fn = self.sg.on_step = self.sg.phases = self.sg.between = None   # not wait for the cyclic
