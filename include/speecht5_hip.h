@@ -927,6 +927,23 @@ int st5_edit_distance_rows(const int32_t* a, const int32_t* a_len, int32_t La, c
 int st5_batch_load(const void* const* src, const void* const* dst, const int64_t* bytes, const int64_t* prefix, int32_t n_leaves,
                    int64_t total_chunks, void* stream);
 
+/* ---- training statistics: the logged scalars of one update copied into a row of a device ring by one launch, the last of the
+ *      update (csrc/train_stats.hip, arithmetic in csrc/train_stats_index.h; speecht5_amd/train_stats.py StatsRecorder).
+ * Replaces, on the replayed path, the trainer's `.item()` per logged scalar (fairseq Trainer.train_step -> reduce_metrics reads every
+ *   entry of the criterion's logging output on the host; under graph replay that Python does not run and the scalars live in the
+ *   graph's private pool).
+ * All four arrays live in DEVICE memory.  src [n_cells]: addresses of one-element device tensors; types [n_cells]: int32 type codes
+ *   (0 fp32, 1 fp64, 2 bf16, 3 fp16, 4 int64, 5 int32, 6 uint8 / bool; any other code: the cell is written as 0 and nothing is read);
+ *   ring [rows, 1 + n_cells]: 8-byte cells; counter [1]: int64, the number of updates recorded so far.
+ * Row counter % rows: cell 0 = counter (the stamp), cell 1 + i = the scalar at src[i], floating types widened to fp64 (exact for
+ *   fp32, bf16, fp16; a NaN stays a NaN), integer and bool types to int64.  Then counter becomes counter + 1.  Launches on one stream
+ *   are ordered, so consecutive launches fill consecutive rows; no other row and no byte outside ring and counter is written.
+ * Contract: the kernel trusts the arrays.  The caller guarantees that every source is a live, naturally aligned device scalar of its
+ *   type until the launch has completed.  One workgroup, no atomics, no LDS.  n_cells < 1, n_cells > 1024, rows < 1 or a NULL array:
+ *   ST5_ERR_ARG, nothing launched. */
+int st5_stats_record(const void* const* src, const int32_t* types, void* ring, int64_t* counter, int32_t rows, int32_t n_cells,
+                     void* stream);
+
 const char* st5_version(void);
 
 #ifdef __cplusplus

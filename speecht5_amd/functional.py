@@ -284,6 +284,21 @@ def batch_load(src, dst, nbytes, prefix, n_leaves, total_chunks):
                                        hip.stream()), "st5_batch_load")
 
 
+def stats_record(src, types, ring, counter, rows, n_cells):
+    """st5_stats_record on the current stream: the n_cells scalars at the device addresses src[i], of type codes types[i], widened
+    into row counter % rows of ring [rows, 1 + n_cells] behind the stamp `counter`; the counter then advances by one
+    (include/speecht5_hip.h has the contract; train_stats.TYPE_CODES the codes).  One launch, whatever the number of cells."""
+    ok = (src.is_cuda and src.dtype == torch.int64 and src.is_contiguous() and src.numel() >= n_cells
+          and types.is_cuda and types.dtype == torch.int32 and types.is_contiguous() and types.numel() >= n_cells
+          and ring.is_cuda and ring.element_size() == 8 and ring.is_contiguous() and ring.numel() >= rows * (1 + n_cells)
+          and counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1)
+    if not ok:
+        raise ValueError("st5_stats_record: src (int64) and types (int32) are contiguous device arrays of at least n_cells entries, "
+                         "ring a contiguous device array of at least rows * (1 + n_cells) 8-byte cells, counter one int64 on the device")
+    hip.check(hip.lib().st5_stats_record(src.data_ptr(), types.data_ptr(), ring.data_ptr(), counter.data_ptr(), rows, n_cells,
+                                         hip.stream()), "st5_stats_record")
+
+
 def set_grad_ready_hook(fn):
     """fn(param) is called when a parameter's .grad has received its last contribution of this backward
     from this library (used to launch bucketed all-reduces while backward is still running)."""

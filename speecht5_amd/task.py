@@ -340,13 +340,23 @@ class SpeechT5Task(LegacyFairseqTask):
         agg["loss"] = loss.detach().item() if sync else loss.detach()
         return agg["loss"], 1.0, agg
 
-    def forward_loss(self, sample, model, criterion, update_num):
+    def forward_loss(self, sample, model, criterion, update_num, return_log=False):
         """The forward half of train_step (tasks/speecht5.py:519-538): the locally normalised loss of one micro-batch; the
-        caller runs .backward() (ddp.accumulate_overlapped runs the forward passes of an update's micro-batches side by side)."""
+        caller runs .backward() (ddp.accumulate_overlapped runs the forward passes of an update's micro-batches side by side).
+        return_log=True: (loss, agg) with the aggregated logging output train_step(sync=False) builds (the normalised loss detached,
+        a device tensor)."""
         model.train()
         model.set_num_updates(update_num)
-        loss, sample_size, _ = criterion(model, sample)
-        return loss / sample_size
+        loss, sample_size, logging_output = criterion(model, sample)
+        loss = loss / sample_size
+        if not return_log:
+            return loss
+        agg = {"sample_size": 1, sample["task_name"]: logging_output}
+        for k in ("ntokens", "nsentences"):
+            if k in logging_output:
+                agg[k] = logging_output[k]
+        agg["loss"] = loss.detach()
+        return loss, agg
 
     def valid_step(self, sample, model, criterion):
         model.eval()

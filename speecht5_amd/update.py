@@ -25,6 +25,11 @@ Data: without a source every update trains on the constructor's `micro_batches` 
 every update train on the next element of the iterable -- a list of micro-batches with the signature of the constructor's: replayed,
 through one st5_batch_load at the head of the captured step into the constructor's tensors (graph.BatchFeed; they are overwritten);
 eagerly, directly on the batch's own tensors (DESIGN.md "Batch feed").
+
+Statistics: stats=True (one rank) ends every update with one st5_stats_record launch -- the last node of the captured step -- that
+copies the logged device scalars of every micro-batch and the squared gradient norm into a row of a device ring; logging_outputs()
+returns, without waiting, the updates whose ring copy has completed, as the reference trainer's list of train_step outputs
+(train_stats.StatsRecorder).  Off by default: nothing is launched, allocated or computed for it.
 """
 import os
 
@@ -36,7 +41,8 @@ from . import functional as Fn
 
 class PretrainUpdate:
     def __init__(self, task, model, criterion, micro_batches, *, lr=2e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, clip_norm=5.0,
-                 graph=True, micro="side_by_side", wgrad_stream=None, prefetch_host=True, device=None, lr_fn=None, exchange="phased", exchange_payload="fp32"):
+                 graph=True, micro="side_by_side", wgrad_stream=None, prefetch_host=True, device=None, lr_fn=None, exchange="phased", exchange_payload="fp32",
+                 stats=False, stats_rows=64):
         from .ddp import FlatGradDataParallel, FusedAdam
         assert micro in ("side_by_side", "in_turn_2buf", "in_turn")
         self.task, self.model, self.crit, self.micro = task, model, criterion, list(micro_batches)
@@ -44,6 +50,23 @@ class PretrainUpdate:
         self.use_graph = graph
         self.device = device if device is not None else next(model.parameters()).device
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
+        # (checked before anything is attached to the model)
+        # stats=True: every update ends with one st5_stats_record launch (train_stats.StatsRecorder) and
+        # logging_outputs() hands the caller what the reference's trainer logs; off, nothing below exists
+        self.stats = None
+        self._aggs = None         # the aggregated logging outputs of the update being enqueued, in micro-batch order
+        self._advanced = []       # (num_updates, lr) per advance(), oldest first: row k of the statistics belongs to the k-th
+        self._advanced_base = 1
+        if stats:
+            if self.world > 1:
+                raise ValueError("stats=True with a process group of more than one rank: the logging outputs of several ranks are "
+                                 "gathered by the trainer, which this update does not do")
+            parts = list(criterion.modules()) if isinstance(criterion, torch.nn.Module) else [criterion]
+            if graph and any(getattr(c, "sync_logging", False) for c in parts):     # (SpeechT5Criterion keeps the flag on its four parts)
+                raise ValueError("stats=True with graph=True needs a criterion that keeps its logged scalars on the device "
+                                 "(sync_logging=False): a `.item()` inside the captured step would fail the capture")
+            from .train_stats import StatsRecorder
+            self.stats = StatsRecorder(self.device, rows=stats_rows, clip_norm=clip_norm, grad_scale=1.0 / len(self.micro))
         # no weight-gradient stream, no attention helper stream: beside two micro-batch streams they cost time (42.0 against 31.5 ms,
         # profiles/r5_replay_hunt.txt); results are the same bits with and without them
         if wgrad_stream is None:
@@ -95,7 +118,11 @@ class PretrainUpdate:
 
     # -- pieces ---------------------------------------------------------------------------------------------------------
     def _fwd(self, s):
-        return self.task.forward_loss(s, self.model, self.crit, self.n)
+        if self.stats is None:
+            return self.task.forward_loss(s, self.model, self.crit, self.n)
+        loss, agg = self.task.forward_loss(s, self.model, self.crit, self.n, return_log=True)
+        self._aggs.append(agg)
+        return loss
 
     def local_part(self):
         """(several ranks, graph) what the graph holds: gradients of this rank's micro-batches, summed into ddp.flat."""
@@ -270,14 +297,24 @@ class PretrainUpdate:
             return
         ddp = self.ddp
         ddp.zero_grad()
+        self._aggs = [] if self.stats is not None else None
         if self.mode == "in_turn":
             # --update-freq 2: gradients of the first micro-batch only accumulate (no_sync); the bucket all-reduces are launched
             # from the backward of the LAST micro-batch, each bucket once, after its last local contribution
-            ddp.accumulate(self.micro, lambda s: self.task.train_step(s, self.model, self.crit, None, self.n, sync=False))
+            outs = ddp.accumulate(self.micro, lambda s: self.task.train_step(s, self.model, self.crit, None, self.n, sync=False))
+            if self.stats is not None:
+                self._aggs = [o[2] for o in outs]
         else:
             ddp.accumulate_overlapped(self.micro, self._fwd, backward="in_turn" if self.mode == "in_turn_2buf" else "side_by_side")
         ddp.finish()
         self.opt.step(grad_scale=1.0 / len(self.micro))
+        if self.stats is not None:
+            # the last launch of the update, on its own stream behind Adam (side by side: behind the join of the second stream, so
+            # behind every kernel that wrote a logged scalar); self._aggs holds the logged tensors until it is enqueued
+            try:
+                self.stats.record(self._aggs, self.opt)
+            finally:
+                self._aggs = None
 
     def advance(self):
         """Host-side state a replayed step does not touch: the update counter (quantizer temperature, freeze counters), lr."""
@@ -285,6 +322,8 @@ class PretrainUpdate:
         self.model.set_num_updates(self.n)
         if self.lr_fn is not None:
             self.opt.lr = self.lr_fn(self.n)
+        if self.stats is not None:
+            self._advanced.append((self.n, float(self.opt.lr)))
 
     # -- driving --------------------------------------------------------------------------------------------------------
     def set_source(self, iterable):
@@ -338,9 +377,16 @@ class PretrainUpdate:
             self.sg = StepGraph(self.local_part if self.split else self.step, opt=self.opt, model=self.model, device=self.device,
                                 on_step=self.advance, prefetch_host=self.prefetch_host,
                                 after_fn=self.exchange_and_update if self.split else None, stream=self.stream, feed=self.feed)
+        if self.stats is not None and self.feed is not None:
+            from .graph import HOST_VALUES_FREE
+            from .train_stats import check_feed_host_values
+            check_feed_host_values([s.get("task_name") for s in self.micro], HOST_VALUES_FREE)
         self.sg.record()
         self.sg.record()
         self.sg.capture()
+        if self.stats is not None:
+            with torch.cuda.stream(self.sg.stream):
+                self.stats.capture_done()     # (the captured record node's source addresses, uploaded once: constant over replays)
         return self.sg
 
     def update(self):
@@ -349,20 +395,57 @@ class PretrainUpdate:
             if self.feed is not None:      # (the source runs on the caller's stream; the replay waits for an event behind it)
                 self.feed.caller_stream = torch.cuda.current_stream(self.device)
             with torch.cuda.stream(self.sg.stream):
+                if self.stats is not None:
+                    self.stats.before_replay()
                 self.sg.replay()
+                if self.stats is not None:
+                    self.stats.replayed()     # (host bookkeeping; every stats_rows // 2 updates one asynchronous copy of the ring)
         else:
             self.eager_update()
+
+    def logging_outputs(self, wait=False):
+        """(stats=True) the updates harvested since the last call, in order, one entry per update: {"num_updates", "lr", "gnorm_sq",
+        "gnorm" (sqrt(gnorm_sq) * grad_scale in fp64: what the clip compared), "clip", "logging_outputs": [agg per micro-batch, as
+        train_step(sync=True) returns it]} -- SpeechT5Criterion.reduce_metrics(entry["logging_outputs"]) takes it as it takes the
+        reference trainer's list.  wait=False never waits for the device: only rows whose copy has completed are returned.  wait=True
+        enqueues a final copy of the ring and waits for it."""
+        if self.stats is None:
+            raise RuntimeError("logging_outputs(): this update was built with stats=False")
+        if wait:
+            self._drain_stats()
+        got = self.stats.harvest()
+        out = []
+        for e in got:
+            k = e.pop("ordinal")
+            n, lr = self._advanced[k - self._advanced_base]
+            out.append({"num_updates": n, "lr": lr, **e})
+        if got:
+            del self._advanced[:k + 1 - self._advanced_base]
+            self._advanced_base = k + 1
+        return out
+
+    def _drain_stats(self):
+        """One more copy of the ring on the update's stream, behind the newest update, and a wait for it."""
+        if self.stream is not None:
+            with torch.cuda.stream(self.stream):
+                self.stats.drain()
+        else:
+            self.stats.drain()
 
     def finish(self):
         if self.sg is not None:
             self.sg.drain()
             torch.cuda.current_stream(self.device).wait_stream(self.sg.stream)
+        if self.stats is not None:
+            self._drain_stats()      # (everything enqueued so far becomes available to the next logging_outputs())
 
     def close(self):
         self.finish()
         if self.feed is not None:
             self.feed.held = []      # (finish() ordered the caller's stream behind the last replay that read them)
         self.ddp.close()
+        if self.stats is not None:
+            self.stats.close()
         if self.sg is not None:      # break the cycle update -> graph -> bound step function -> update: a HIP graph object must
             self.sg.step_fn = self.sg.after_fn = self.sg.on_step = self.sg.phases = self.sg.between = None   # not wait for the cyclic
             self.sg.graph = self.sg.graphs = None    # collector (a collection during a LATER capture destroys it mid-capture)
