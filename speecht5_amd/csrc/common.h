@@ -434,6 +434,15 @@ inline hipError_t st5_dev_malloc(void** p, size_t bytes) {
   return rc;
 }
 template <typename T> inline hipError_t st5_dev_malloc(T** p, size_t bytes) { return st5_dev_malloc(reinterpret_cast<void**>(p), bytes); }
+// The device policy of stream_scratch.h (the per-stream workspaces of gemm.hip, norm.hip and elementwise.hip).  A stream whose capture
+// state cannot be read counts as capturing: nothing may be allocated for it now.
+struct St5Dev {
+  static bool malloc(void** p, size_t bytes) { return st5_dev_malloc(p, bytes) == hipSuccess; }
+  static bool capturing(void* stream) {
+    hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing(static_cast<hipStream_t>(stream), &st) != hipSuccess || st != hipStreamCaptureStatusNone;
+  }
+};
 
 #define HIP_CHECK_LAUNCH()                                   \
   do {                                                       \

@@ -1,8 +1,8 @@
 // Element-wise, gather/scatter and small reduction kernels of the SpeechT5 hot path (HBM-bound;
 // 16-byte vector IO, grid-stride).  Each replaces a torch call site cited in include/speecht5_hip.h.
 #include <initializer_list>
-#include <mutex>
 #include "common.h"
+#include "stream_scratch.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
@@ -616,10 +616,14 @@ __global__ void log10_floor_kernel(const float* __restrict__ x, float* __restric
     y[i] = log10f(fmaxf(x[i], floor_));
 }
 
-float* g_scratch = nullptr;  // 2048-float device scratch for block partials (lazily allocated)
-float* scratch() {
-  if (!g_scratch) { if (st5_dev_malloc(&g_scratch, 2048 * sizeof(float)) != hipSuccess) return nullptr; }
-  return g_scratch;
+// The library's scratch of this file, each ONE PER STREAM (stream_scratch.h: never handed to another stream, grown outside capture only,
+// never freed): two micro-batches' backward passes run side by side on two streams, and one buffer for the whole process would be
+// written by both.
+PerStream<GrowBuf<St5Dev>> g_sumsq_parts;   // block partials of st5_sumsq / st5_sumsq_pair: 2048 floats (grid_for's block limit)
+PerStream<GrowBuf<St5Dev>> g_fill_parts;    // st5_masked_fill_rows_bwd: partials [256][cols]
+PerStream<GrowBuf<St5Dev>> g_scatter;       // st5_embed_rows_bwd_det_w: order | sorted ids | head | tail
+float* sumsq_parts(hipStream_t s) {
+  return static_cast<float*>(g_sumsq_parts.get(s)->reserve(2048 * sizeof(float), 2048 * sizeof(float), s));
 }
 
 
@@ -671,9 +675,9 @@ extern "C" int st5_cast_to_f32(const void* src, float* dst, int64_t n, int dtype
 }
 extern "C" int st5_sumsq(const void* x, float* out, int64_t n, float scale, int32_t accumulate, int dtype, void* stream) {
   if (!x || !out || n < 0) return ST5_ERR_ARG;
-  float* part = scratch();
-  if (!part) return ST5_ERR_LAUNCH;
   hipStream_t s = (hipStream_t)stream;
+  float* part = sumsq_parts(s);
+  if (!part) return ST5_ERR_LAUNCH;
   dim3 grid = grid_for(n / 8 + 1);
   DISPATCH(dtype, hipLaunchKernelGGL(sumsq_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, part, (long long)n),
            hipLaunchKernelGGL(sumsq_kernel<float>, grid, dim3(256), 0, s, (const float*)x, part, (long long)n));
@@ -683,9 +687,9 @@ extern "C" int st5_sumsq(const void* x, float* out, int64_t n, float scale, int3
 }
 extern "C" int st5_sumsq_pair(const float* x, const float* y, float* out, int64_t n, float scale, int32_t accumulate, void* stream) {
   if (!x || !y || !out || n < 0) return ST5_ERR_ARG;
-  float* part = scratch();
-  if (!part) return ST5_ERR_LAUNCH;
   hipStream_t s = (hipStream_t)stream;
+  float* part = sumsq_parts(s);
+  if (!part) return ST5_ERR_LAUNCH;
   dim3 grid = grid_for(n / 8 + 1);
   hipLaunchKernelGGL(sumsq_pair_kernel, grid, dim3(256), 0, s, x, y, part, (long long)n);
   hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, s, part, out, (int)grid.x, scale, accumulate);
@@ -788,31 +792,9 @@ extern "C" int st5_masked_fill_rows_bwd(void* dx, const uint8_t* mask, float* dv
   const unsigned ny = (unsigned)(rows < 256 ? rows : 256);
   dim3 grid((unsigned)((cols + 255) / 256), ny);
   float* part = nullptr;
-  if (dv) {   // grow-only partial buffer [256][cols] PER STREAM (first use / growth happens outside stream capture): one buffer for the
-    // whole process would be shared by two micro-batches whose backward passes run side by side on two streams
-    struct Part { hipStream_t s; float* p; size_t n; };
-    static Part g_parts[16] = {};
-    static int g_nparts = 0;
-    static std::mutex g_mu;
-    std::lock_guard<std::mutex> lk(g_mu);
-    Part* e = nullptr;
-    for (int i = 0; i < g_nparts; ++i)
-      if (g_parts[i].s == s) e = &g_parts[i];
-    if (!e) {
-      if (g_nparts == 16) {      // (more streams than slots: recycle the first slot; hipFree waits for the device)
-        if (g_parts[0].p) (void)hipFree(g_parts[0].p);
-        e = &g_parts[0];
-      } else e = &g_parts[g_nparts++];
-      e->s = s; e->p = nullptr; e->n = 0;
-    }
-    const size_t want = (size_t)256 * cols;
-    if (want > e->n) {
-      if (e->p) (void)hipFree(e->p);
-      e->p = nullptr; e->n = 0;
-      if (st5_dev_malloc(&e->p, want * sizeof(float)) != hipSuccess) return ST5_ERR_LAUNCH;
-      e->n = want;
-    }
-    part = e->p;
+  if (dv) {
+    part = static_cast<float*>(g_fill_parts.get(s)->reserve((size_t)256 * cols * sizeof(float), 0, s));
+    if (!part) return ST5_ERR_LAUNCH;
   }
   DISPATCH(dtype, hipLaunchKernelGGL(masked_fill_rows_bwd_kernel<bf16_t>, grid, dim3(256), 0, s, (bf16_t*)dx, mask, part, (long long)rows, cols),
            hipLaunchKernelGGL(masked_fill_rows_bwd_kernel<float>, grid, dim3(256), 0, s, (float*)dx, mask, part, (long long)rows, cols));
@@ -864,10 +846,6 @@ extern "C" int st5_embed_rows_bwd(const void* dy, const int32_t* tok, float* dta
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
-// workspace of the deterministic row scatter: order | sorted ids | head | tail (grow-only), one per stream
-struct ScatterWs { hipStream_t stream; char* ptr; size_t bytes; };
-ScatterWs g_scatter[4] = {};
-int g_nscatter = 0;
 extern "C" int st5_embed_rows_bwd_det_w(const void* dy, const int32_t* tok, float* dtable, int64_t rows, int32_t cols, int32_t vocab,
                                         float scale, const float* row_w, int32_t rw_div, int32_t rw_mod, int dtype, void* stream) {
   if (!dy || !tok || !dtable || rows < 0 || cols <= 0 || cols % 4 || vocab <= 0 || (row_w && (rw_div <= 0 || rw_mod <= 0))) return ST5_ERR_ARG;
@@ -877,26 +855,11 @@ extern "C" int st5_embed_rows_bwd_det_w(const void* dy, const int32_t* tok, floa
   const long long nch = (rows + SEG - 1) / SEG;
   const size_t ints = (((size_t)rows * 2 * sizeof(int32_t)) + 255) & ~(size_t)255;
   const size_t need = ints + (size_t)2 * nch * cols * sizeof(float);
-  ScatterWs* w = nullptr;
-  for (int i = 0; i < g_nscatter; ++i)
-    if (g_scatter[i].stream == s) w = &g_scatter[i];
-  if (!w) {
-    static int victim = 0;
-    w = g_nscatter < 4 ? &g_scatter[g_nscatter++] : &g_scatter[victim++ % 4];   // (stream churn: recycle, the old owner is gone)
-    if (w->stream != s && w->ptr && hipDeviceSynchronize() != hipSuccess) return ST5_ERR_LAUNCH;
-    w->stream = s;
-  }
-  if (need > w->bytes) {   // (first use / growth: outside stream capture, like every other workspace of this library)
-    if (w->ptr) (void)hipFree(w->ptr);
-    w->ptr = nullptr; w->bytes = 0;
-    const size_t want = need < (size_t(8) << 20) ? (size_t(8) << 20) : need;
-    if (st5_dev_malloc(&w->ptr, want) != hipSuccess) return ST5_ERR_LAUNCH;
-    w->bytes = want;
-  }
-  char* g_scatter_ws = w->ptr;
-  int32_t* order = reinterpret_cast<int32_t*>(g_scatter_ws);
+  char* ws = static_cast<char*>(g_scatter.get(s)->reserve(need, size_t(8) << 20, s));
+  if (!ws) return ST5_ERR_LAUNCH;
+  int32_t* order = reinterpret_cast<int32_t*>(ws);
   int32_t* sid = order + rows;
-  float* head = reinterpret_cast<float*>(g_scatter_ws + ints);
+  float* head = reinterpret_cast<float*>(ws + ints);
   float* tail = head + (size_t)nch * cols;
   hipLaunchKernelGGL(rank_sort_kernel, dim3((unsigned)((rows + RS_ROWS - 1) / RS_ROWS)), dim3(256), 0, s, tok, order, sid, (int)rows);
   dim3 grid((unsigned)nch, (unsigned)((cols + 255) / 256));

@@ -16,6 +16,7 @@
 // consecutive columns per lane and stored as 16-byte vectors.
 #include <type_traits>
 #include "common.h"
+#include "stream_scratch.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
@@ -758,103 +759,43 @@ __global__ __launch_bounds__(256) void splitk_multi_reduce_kernel(const MrArgs a
 }
 
 bool g_defer = false;
-// Deferred-reduction state, ONE PER STREAM: the queued descriptors belong to GEMMs of that stream and are folded by a launch on
-// that stream (the backward passes of two micro-batches may run on two streams at once; a flush on one of them must not read
-// slabs the other stream is still writing).  Each state has its own bump arena.
+// Deferred-reduction state, ONE PER STREAM (stream_scratch.h: never handed to another stream): the queued descriptors belong to
+// GEMMs of that stream and are folded by a launch on that stream (the backward passes of two micro-batches may run on two streams
+// at once; a flush on one of them must not read slabs the other stream is still writing).  Each state has its own bump arena.
 struct DeferState {
-  hipStream_t stream;
-  MrArgs pending;            // pending.n descriptors queued
-  int pending_blocks;
-  float* arena;              // slab arena for deferred reductions (grown between flushes only)
-  size_t arena_bytes, arena_used;
+  MrArgs pending = {};       // pending.n descriptors queued
+  int pending_blocks = 0;
+  BumpArena<St5Dev> arena;   // slabs of the queued reductions
 
   // folds everything queued into its outputs with one launch on the state's stream
-  int flush() {
+  int flush(hipStream_t stream) {
     if (pending.n == 0) return ST5_OK;
     hipLaunchKernelGGL(splitk_multi_reduce_kernel, dim3((unsigned)pending_blocks), dim3(256), 0, stream, pending);
-    pending.n = 0; pending_blocks = 0; arena_used = 0;
+    pending.n = 0; pending_blocks = 0; arena.reset();
     HIP_CHECK_LAUNCH();
     return ST5_OK;
   }
-  // slab space for one deferred GEMM, or nullptr when the arena is too full for it
-  float* take(size_t bytes) {
-    bytes = (bytes + 255) & ~(size_t)255;
-    if (arena_used + bytes > arena_bytes) return nullptr;
-    float* p = reinterpret_cast<float*>(reinterpret_cast<char*>(arena) + arena_used);
-    arena_used += bytes;
-    return p;
-  }
-  // the same; a full arena is emptied by a flush first and grown when it is too small altogether.  nullptr: the flush or the allocation failed
-  float* take_or_grow(size_t bytes) {
-    float* slabs = take(bytes);
-    if (slabs) return slabs;
-    if (flush() != ST5_OK) return nullptr;
-    if (bytes > arena_bytes || arena_bytes == 0) {
-      if (arena) (void)hipFree(arena);   // synchronises with in-flight users
-      size_t want = arena_bytes ? arena_bytes * 2 : (size_t(1) << 30);
-      while (want < bytes * 4) want *= 2;
-      if (st5_dev_malloc(&arena, want) != hipSuccess) { arena = nullptr; arena_bytes = 0; return nullptr; }
-      arena_bytes = want;
+  // slab space for one deferred GEMM; a full arena is emptied by a flush first and grown (outside capture only) when it is too small
+  // altogether.  nullptr: the flush or the growth failed
+  float* take_or_grow(size_t bytes, hipStream_t stream) {
+    void* slabs = arena.take(bytes);
+    if (!slabs) {
+      if (flush(stream) != ST5_OK || !arena.reserve(bytes, size_t(1) << 30, stream)) return nullptr;
+      slabs = arena.take(bytes);
     }
-    return take(bytes);
+    return static_cast<float*>(slabs);
   }
 };
-constexpr int DEFER_STREAMS = 32;
-DeferState g_dstates[DEFER_STREAMS] = {};
-int g_ndstates = 0;
-DeferState* defer_state(hipStream_t s, bool create) {
-  for (int i = 0; i < g_ndstates; ++i)
-    if (g_dstates[i].stream == s) return &g_dstates[i];
-  if (!create) return nullptr;
-  if (g_ndstates == DEFER_STREAMS) {
-    // Stream churn (a test session that keeps creating streams): start the table over -- only when nothing is queued on
-    // any state and after the device has drained, the rule of the LayerNorm table (norm.hip).  A state is never handed from
-    // one stream to another while either may still have work in flight: the second micro-batch of a side-by-side update
-    // would otherwise write its slabs into the arena the first one's queued reduction still has to read.
-    for (int i = 0; i < g_ndstates; ++i)
-      if (g_dstates[i].pending.n != 0) return nullptr;
-    if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-    g_ndstates = 0;   // (the slots keep their arenas)
-  }
-  DeferState* d = &g_dstates[g_ndstates++];
-  d->stream = s; d->pending.n = 0; d->pending_blocks = 0; d->arena_used = 0;
-  return d;
-}
+PerStream<DeferState> g_dstates;
 int flush_pending(hipStream_t s) {
-  DeferState* ds = defer_state(s, false);
-  return ds ? ds->flush() : (int)ST5_OK;
+  DeferState* ds = g_dstates.find(s);
+  return ds ? ds->flush(s) : (int)ST5_OK;
 }
 
-// split-K slab workspace, one per stream (the weight-gradient stream runs split-K GEMMs beside the main stream's)
-struct SlabWs { hipStream_t stream; float* ptr; size_t bytes; };
-constexpr int SLAB_STREAMS = 8;
-SlabWs g_slabs[SLAB_STREAMS] = {};
-int g_nslabs = 0, g_slab_victim = 0;
+// split-K slab workspace of the immediate reductions, one per stream (the weight-gradient stream runs split-K GEMMs beside the main stream's)
+PerStream<GrowBuf<St5Dev>> g_slabs;
 float* slab_workspace(size_t bytes, hipStream_t stream) {
-  SlabWs* w = nullptr;
-  for (int i = 0; i < g_nslabs; ++i)
-    if (g_slabs[i].stream == stream) w = &g_slabs[i];
-  if (!w) {
-    if (g_nslabs < SLAB_STREAMS) {
-      w = &g_slabs[g_nslabs++];
-      w->ptr = nullptr; w->bytes = 0;
-    } else {
-      // table full (streams come and go over a process's life): hand the oldest entry's allocation to the new stream.  The
-      // previous owner's work may still be in flight, so drain the device once; this happens on stream churn only.
-      w = &g_slabs[g_slab_victim];
-      g_slab_victim = (g_slab_victim + 1) % SLAB_STREAMS;
-      if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-    }
-    w->stream = stream;
-  }
-  if (bytes > w->bytes) {
-    if (w->ptr) (void)hipFree(w->ptr);  // synchronises with in-flight users
-    w->ptr = nullptr;
-    const size_t want = bytes < (size_t(64) << 20) ? (size_t(64) << 20) : bytes;
-    if (st5_dev_malloc(&w->ptr, want) != hipSuccess) { w->bytes = 0; return nullptr; }
-    w->bytes = want;
-  }
-  return w->ptr;
+  return static_cast<float*>(g_slabs.get(stream)->reserve(bytes, size_t(64) << 20, stream));
 }
 
 template <typename T>
@@ -2840,13 +2781,12 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
     float* const C = reinterpret_cast<float*>(const_cast<void*>(p.C.ptr));
     if (g_defer && (p.flags & ST5_GEMM_DEFERRABLE) && !p.C.rpb && p.C.ld % 4 == 0) {
       // deferred: the slabs stay in the stream's arena, the reduction is queued for st5_gemm_flush_splitk
-      DeferState* ds = defer_state(s, true);
-      if (!ds) return ST5_ERR_LAUNCH;
+      DeferState* ds = g_dstates.get(s);
       // the same output twice in one batch (tied weights) would race inside the batched reduction: fold what is pending first
       for (int j = 0; j < ds->pending.n; ++j)
-        if (ds->pending.d[j].C == p.C.ptr) { const int rc = ds->flush(); if (rc) return rc; break; }
-      if (ds->pending.n == MR_MAX) { const int rc = ds->flush(); if (rc) return rc; }
-      float* slabs = ds->take_or_grow(need);
+        if (ds->pending.d[j].C == p.C.ptr) { const int rc = ds->flush(s); if (rc) return rc; break; }
+      if (ds->pending.n == MR_MAX) { const int rc = ds->flush(s); if (rc) return rc; }
+      float* slabs = ds->take_or_grow(need, s);
       if (!slabs) return ST5_ERR_LAUNCH;
       const int rc = launch_splitk_partials(p, dtype, use8p, nsplit, slabs, s);
       if (rc) return rc;
@@ -3060,7 +3000,9 @@ extern "C" int st5_multi_quant_mxfp8(const void* jobs, int32_t njobs, int32_t nb
 extern "C" int st5_gemm_defer_splitk(int enabled, void* stream) {
   (void)stream;
   if (!enabled && g_defer) {   // fold whatever is queued, every state on its own stream
-    for (int i = 0; i < g_ndstates; ++i) { const int rc = g_dstates[i].flush(); if (rc) return rc; }
+    int rc = ST5_OK;
+    g_dstates.for_each([&rc](void* s, DeferState& ds) { if (!rc) rc = ds.flush(static_cast<hipStream_t>(s)); });
+    if (rc) return rc;
   }
   g_defer = enabled != 0;
   return ST5_OK;

@@ -5,6 +5,7 @@
 // backward reads x and dy once for dx and once more for the (deterministic, two-stage)
 // dgamma/dbeta column reduction.
 #include "common.h"
+#include "stream_scratch.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
@@ -471,41 +472,27 @@ __global__ __launch_bounds__(1024) void ln_bwd_final_multi_kernel(const LnFinalA
   }
 }
 bool g_ln_defer = false;
-// deferred-reduction state, one per stream (as the split-K states of gemm.hip: two backward passes may run on two streams)
-struct LnDeferState { hipStream_t stream; LnFinalArgs pending; int blocks; float* arena; size_t arena_bytes, arena_used; };
-constexpr int LN_DEFER_STREAMS = 32;
-LnDeferState g_lnstates[LN_DEFER_STREAMS] = {};
-int g_nlnstates = 0;
-LnDeferState* ln_state(hipStream_t s, bool create) {
-  for (int i = 0; i < g_nlnstates; ++i)
-    if (g_lnstates[i].stream == s) return &g_lnstates[i];
-  if (!create) return nullptr;
-  if (g_nlnstates == LN_DEFER_STREAMS) {
-    // Stream churn (test sessions): start the table over -- only when nothing is queued anywhere and after the device has
-    // drained.  (Handing an idle state from one LIVE stream to another, as the first version did, let the second micro-batch of
-    // a side-by-side update write its partials into the arena the first one's queued reduction still had to read.)
-    for (int i = 0; i < g_nlnstates; ++i)
-      if (g_lnstates[i].pending.n != 0) return nullptr;
-    if (hipDeviceSynchronize() != hipSuccess) return nullptr;
-    g_nlnstates = 0;   // (the slots keep their arenas)
+// deferred-reduction state, one per stream and never handed to another (stream_scratch.h; as the split-K states of gemm.hip: two
+// backward passes may run on two streams, and the second must not write its partials into the arena the first one's queued
+// reduction still has to read)
+struct LnDeferState {
+  LnFinalArgs pending = {};
+  int blocks = 0;
+  BumpArena<St5Dev> arena;   // block partials of the queued reductions
+  // folds everything queued into its dgamma / dbeta with one launch on the state's stream
+  int flush(hipStream_t stream) {
+    if (pending.n == 0) return ST5_OK;
+    hipLaunchKernelGGL(ln_bwd_final_multi_kernel, dim3((unsigned)blocks), dim3(1024), 0, stream, pending);
+    pending.n = 0; blocks = 0; arena.reset();
+    HIP_CHECK_LAUNCH();
+    return ST5_OK;
   }
-  LnDeferState* d = &g_lnstates[g_nlnstates++];
-  d->stream = s; d->pending.n = 0; d->blocks = 0; d->arena_used = 0;
-  return d;
+};
+PerStream<LnDeferState> g_lnstates;
+int ln_flush(hipStream_t s) {
+  LnDeferState* ls = g_lnstates.find(s);
+  return ls ? ls->flush(s) : (int)ST5_OK;
 }
-#define g_ln_pending (ls->pending)
-#define g_ln_blocks (ls->blocks)
-#define g_ln_arena (ls->arena)
-#define g_ln_arena_bytes (ls->arena_bytes)
-#define g_ln_arena_used (ls->arena_used)
-int ln_flush_state(LnDeferState* ls) {
-  if (!ls || g_ln_pending.n == 0) return ST5_OK;
-  hipLaunchKernelGGL(ln_bwd_final_multi_kernel, dim3((unsigned)g_ln_blocks), dim3(1024), 0, ls->stream, g_ln_pending);
-  g_ln_pending.n = 0; g_ln_blocks = 0; g_ln_arena_used = 0;
-  HIP_CHECK_LAUNCH();
-  return ST5_OK;
-}
-int ln_flush(hipStream_t s) { return ln_flush_state(ln_state(s, false)); }
 
 int ln_blocks(long long rows) {
   long long n = (rows + 4 * BRPW - 1) / (4 * BRPW);   // blocks at one trip per wave
@@ -747,30 +734,25 @@ static int layernorm_bwd(const void* dy, const void* x, const float* gamma, cons
     const size_t shm = pg ? (size_t)8 * cols * sizeof(float) : 0;
     bool deferred = false;
     if (pg && g_ln_defer) {
-      LnDeferState* ls = ln_state(s, true);
-      if (!ls) return ST5_ERR_LAUNCH;
+      LnDeferState* ls = g_lnstates.get(s);
       // the same parameter twice in one batch (two micro-batches) would race inside the batched reduction: fold first
-      for (int j = 0; j < g_ln_pending.n; ++j)
-        if ((dgamma && g_ln_pending.d[j].dgamma == dgamma) || (dbeta && g_ln_pending.d[j].dbeta == dbeta)) {
-          const int rc = ln_flush(s); if (rc) return rc; break;
+      for (int j = 0; j < ls->pending.n; ++j)
+        if ((dgamma && ls->pending.d[j].dgamma == dgamma) || (dbeta && ls->pending.d[j].dbeta == dbeta)) {
+          const int rc = ls->flush(s); if (rc) return rc; break;
         }
-      const size_t need = ((size_t)nb * 2 * cols * sizeof(float) + 255) & ~(size_t)255;
-      if (g_ln_pending.n == LNF_MAX || g_ln_arena_used + need > g_ln_arena_bytes) {
-        const int rc = ln_flush(s); if (rc) return rc;
-        if (need > g_ln_arena_bytes) {
-          if (g_ln_arena) (void)hipFree(g_ln_arena);   // synchronises with in-flight users
-          size_t want = size_t(128) << 20;
-          while (want < need * 4) want *= 2;
-          if (st5_dev_malloc(&g_ln_arena, want) != hipSuccess) { g_ln_arena = nullptr; g_ln_arena_bytes = 0; return ST5_ERR_LAUNCH; }
-          g_ln_arena_bytes = want;
-        }
+      if (ls->pending.n == LNF_MAX) { const int rc = ls->flush(s); if (rc) return rc; }
+      // a full arena is emptied by a flush first and grown (outside capture only) when it is too small altogether
+      const size_t need = (size_t)nb * 2 * cols * sizeof(float);
+      ws = ls->arena.take(need);
+      if (!ws) {
+        const int rc = ls->flush(s); if (rc) return rc;
+        if (!ls->arena.reserve(need, size_t(128) << 20, s)) return ST5_ERR_LAUNCH;
+        ws = ls->arena.take(need);
       }
-      ws = reinterpret_cast<char*>(g_ln_arena) + g_ln_arena_used;
-      g_ln_arena_used += need;
-      LnFinalDesc& d = g_ln_pending.d[g_ln_pending.n++];
+      LnFinalDesc& d = ls->pending.d[ls->pending.n++];
       d.part = reinterpret_cast<const float*>(ws); d.dgamma = dgamma; d.dbeta = dbeta; d.nblk = nb; d.cols = cols;
-      d.blk0 = g_ln_blocks; d.pad = 0;
-      g_ln_blocks += (2 * cols + 63) / 64;
+      d.blk0 = ls->blocks; d.pad = 0;
+      ls->blocks += (2 * cols + 63) / 64;
       deferred = true;
     }
 #define LBV(TT, NV_)                                                                                                    \
@@ -849,17 +831,14 @@ extern "C" int st5_layernorm_bwd_gate(const void* dy, const void* x, const float
                        nullptr, gate);
 }
 
-#undef g_ln_pending
-#undef g_ln_blocks
-#undef g_ln_arena
-#undef g_ln_arena_bytes
-#undef g_ln_arena_used
 /* Deferred dgamma / dbeta reductions (see ln_bwd_final_multi_kernel).  While enabled, the parameter gradients of
  * st5_layernorm_bwd (vector path) are complete only after st5_layernorm_flush() on the same stream; disabling flushes. */
 extern "C" int st5_layernorm_defer(int enabled, void* stream) {
   (void)stream;
-  if (!enabled && g_ln_defer) {
-    for (int i = 0; i < g_nlnstates; ++i) { const int rc = ln_flush_state(&g_lnstates[i]); if (rc) return rc; }
+  if (!enabled && g_ln_defer) {   // fold whatever is queued, every state on its own stream
+    int rc = ST5_OK;
+    g_lnstates.for_each([&rc](void* s, LnDeferState& ls) { if (!rc) rc = ls.flush(static_cast<hipStream_t>(s)); });
+    if (rc) return rc;
   }
   g_ln_defer = enabled != 0;
   return ST5_OK;
@@ -868,9 +847,7 @@ extern "C" int st5_layernorm_flush(void* stream) { return ln_flush(reinterpret_c
 /* A/B switch: upper bound of the backward's block count (partials workspace = blocks x 2 x cols floats). */
 extern "C" int st5_layernorm_set_max_blocks(int n) { if (n < 1 || n > 4096) return ST5_ERR_ARG; g_ln_max_blocks = n; return ST5_OK; }
 
-// out[c] (+)= scale * sum_r x[r, c]; uses an internal static workspace-free two-stage path via `ws`
-// passed through the trailing part of `out`?  No: colsum allocates nothing -- the caller provides
-// ws through st5_colsum_ws (kept simple: ws is a dedicated per-stream buffer owned by the host side).
+// out[c] (+)= scale * sum_r x[r, c], in two stages through the caller's `ws` (hip.workspace: a per-stream buffer of the host side)
 extern "C" int st5_colsum_ws(const void* x, float* out, void* ws, int64_t rows, int32_t cols, int64_t ld, float scale,
                              int32_t accumulate, int dtype, void* stream) {
   if (!x || !out || !ws || rows < 0 || cols <= 0) return ST5_ERR_ARG;

@@ -551,14 +551,20 @@ def gemm_mxfp8(Aq, As, Bq, Bs, C, M, N, K, *, R=None, P=None, Cpre=None, bias=No
 # ---------------------------------------------------------------------------------------------
 # workspace: one grow-only byte buffer per device for the two-stage reductions
 _ws = {}
+_ws_retired = []   # superseded buffers, kept alive: a captured graph may hold their addresses (the rule of csrc/stream_scratch.h)
 
 
 def workspace(nbytes, device):
     """Grow-only scratch buffer of the CURRENT stream (two micro-batches may run forward side by side on two streams: a
-    buffer shared between streams would be written by both)."""
+    buffer shared between streams would be written by both).  Growth at least doubles, so the retired buffers of a stream
+    together stay smaller than its current one."""
     key = (device.type, device.index, stream())
     buf = _ws.get(key)
     if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(max(int(nbytes), 1 << 20), dtype=torch.uint8, device=device)
+        old = 0
+        if buf is not None:
+            _ws_retired.append(buf)
+            old = buf.numel()
+        buf = torch.empty(max(int(nbytes), 2 * old, 1 << 20), dtype=torch.uint8, device=device)
         _ws[key] = buf
     return buf
