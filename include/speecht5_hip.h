@@ -744,6 +744,30 @@ int st5_adam_step_pair(float* p, float* g, float* g2, int32_t zero_grads, float*
                        float eps, float weight_decay, int32_t step, const float* gnorm_sq, float max_norm, float grad_scale,
                        void* bf16_mirror, const float* hyper_dev, void* stream);
 int st5_sumsq_pair(const float* x, const float* y, float* out, int64_t n, float scale, int32_t accumulate, void* stream);
+/* ---- The Adam step behind a finite-gradient guard (ddp.FusedAdam(skip_nonfinite=True), update.PretrainUpdate(nonfinite="skip");
+ * csrc/optim.hip) ----
+ * st5_adam_step_pair with a verdict on the device: when gnorm_sq[0] is not finite -- NaN, inf, or a sum of finite squares that
+ * overflowed fp32: !(gnorm_sq[0] <= FLT_MAX) -- the step is SKIPPED: p, m, v and bf16_mirror are neither read nor written (no weight
+ * decay either), and with zero_grads != 0 the gradient buffers are left exact zeros, as an applied step leaves them.  Otherwise the
+ * step is the one of st5_adam_step_pair, same bits, with the number of APPLIED steps in the bias corrections:
+ * t_eff = t - skipped_before, t = `step` (hyper_dev[1] when hyper_dev is given), skipped_before = the skipped steps among 1 .. t - 1.
+ * gnorm_sq is required (max_norm == 0 turns the clipping off, not the verdict).
+ * guard: ST5_GUARD_CELLS int32 cells in device memory, all zero before the first step, owned by ONE optimizer:
+ *   [ST5_GUARD_COUNT + 0], [ST5_GUARD_COUNT + 1]   the running count of skipped steps, double-buffered by the parity of t: the launch
+ *                          of step t reads cell (t & 1) ^ 1 (what step t - 1 left) and one thread writes cell t & 1 -- no cell is
+ *                          read and written in one launch.  REQUIRES t to advance by exactly one from launch to launch, starting at
+ *                          1, all launches of one guard block on one stream (or otherwise ordered).  The count after step t is cell t & 1.
+ *   [ST5_GUARD_SKIPPED]    1 when the most recent launch skipped its step, else 0
+ *   [ST5_GUARD_STEP]       t of the most recent launch (what a host that kept count compares with its own)
+ * The cells are written with ordinary stores by one thread and are visible to whatever follows the launch on its stream.
+ * ST5_ERR_ARG: guard or gnorm_sq NULL (and what st5_adam_step_pair refuses). */
+#define ST5_GUARD_COUNT 0
+#define ST5_GUARD_SKIPPED 2
+#define ST5_GUARD_STEP 3
+#define ST5_GUARD_CELLS 4
+int st5_adam_step_guard(float* p, float* g, float* g2, int32_t zero_grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
+                        float eps, float weight_decay, int32_t step, const float* gnorm_sq, float max_norm, float grad_scale,
+                        void* bf16_mirror, const float* hyper_dev, int32_t* guard, void* stream);
 /* Dropout seeds: every `seed` argument of this library may instead be a device pointer to the 64-bit seed, tagged with bit 63
  * (seed = (1 << 63) | pointer): the kernels then read the seed from memory (csrc/common.h resolve_seed).  Used by captured HIP
  * graphs, whose kernel arguments cannot change between replays. */

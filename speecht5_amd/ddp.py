@@ -790,11 +790,21 @@ def default_buckets(model):
     return groups
 
 
+# the guard block's cells (include/speecht5_hip.h, ST5_GUARD_*)
+GUARD_COUNT, GUARD_SKIPPED, GUARD_STEP, GUARD_CELLS = 0, 2, 3, 4
+
+
 class FusedAdam:
     """fairseq `adam` (decoupled weight decay) + global-norm clipping on the flat buffers, one HIP kernel per step.
-    Parameters are re-pointed at views of one flat fp32 buffer so that the update is a single launch."""
+    Parameters are re-pointed at views of one flat fp32 buffer so that the update is a single launch.
 
-    def __init__(self, ddp: FlatGradDataParallel, lr=2e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, clip_norm=5.0):
+    skip_nonfinite=True: the step runs behind a verdict on the device (st5_adam_step_guard) -- when the squared gradient
+    norm is NaN, inf or overflowed, the launch leaves parameters, both moments and the bf16 image untouched and only zeroes the gradient
+    buffers.  The norm is then computed every step, also with clip_norm == 0 (clipping stays off).  `t` keeps counting ATTEMPTED steps
+    (the host never learns a verdict synchronously); the bias corrections use the applied ones, counted on the device."""
+
+    def __init__(self, ddp: FlatGradDataParallel, lr=2e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, clip_norm=5.0,
+                 skip_nonfinite=False):
         self.ddp = ddp
         self.lr, self.betas, self.eps, self.wd, self.clip = lr, betas, eps, weight_decay, clip_norm
         self.lr_step = None    # graph.StepGraph: this step's learning rate when self.lr already belongs to the next one
@@ -820,6 +830,9 @@ class FusedAdam:
         self.v = torch.zeros_like(self.pflat)
         self.gnorm_sq = torch.zeros(1, dtype=torch.float32, device=dev)
         self.t = 0
+        # the guard block of st5_adam_step_guard (include/speecht5_hip.h: two count cells, the flag, the step), one for the life of
+        # this optimizer -- a captured step holds its address
+        self.guard = torch.zeros(GUARD_CELLS, dtype=torch.int32, device=dev) if skip_nonfinite else None
         # {lr, step} in device memory: what the kernel reads when the step runs from a captured graph (graph.StepGraph), whose
         # kernel arguments are frozen; refreshed from the host image before every replay
         self.hyper_dev = None
@@ -846,6 +859,20 @@ class FusedAdam:
         h[1] = float(self.t + 1)
         self.hyper_dev.copy_(h, non_blocking=True)
 
+    def skipped(self, wait=True):
+        """(skip_nonfinite=True) how many steps the device has skipped so far.  A SYNCHRONISING read of the guard block -- for tests
+        and the end of a run, not for the training loop (PretrainUpdate(stats=True) reports each update's verdict without a wait)."""
+        if self.guard is None:
+            raise RuntimeError("skipped(): this optimizer was built with skip_nonfinite=False")
+        if wait and self.guard.is_cuda:
+            torch.cuda.synchronize(self.guard.device)
+        cells = self.guard.tolist()
+        # the count cells are double-buffered by the parity of the step, which must advance by one per launch: the device's last step
+        # is the host's count (anything else -- a guard block shared by two optimizers, `t` set by hand -- made the count meaningless)
+        if cells[GUARD_STEP] != self.t:
+            raise RuntimeError(f"guard block: the device's last step is {cells[GUARD_STEP]}, the host has counted {self.t}")
+        return cells[GUARD_COUNT + (self.t & 1)]
+
     def backward(self, loss):
         loss.backward()
 
@@ -860,33 +887,50 @@ class FusedAdam:
         lr = self.lr if self.lr_step is None else self.lr_step
         g = self.ddp.flat
         hyper = hip.ptr(self.hyper_dev) if (self.hyper_dev is not None and g.is_cuda and torch.cuda.is_current_stream_capturing()) else 0
+        guard = self.guard.data_ptr() if self.guard is not None else 0     # (skip_nonfinite: the guarded launch in both branches)
         if self.ddp._pair_pending and self.ddp.world == 1:
             # two gradient buffers (ddp.accumulate_overlapped): norm and update over g + g2 in the kernels themselves, both
             # buffers left zeroed -- no "g += g2" pass, no fills before the next update
             g2 = self.ddp.flat2
-            if self.clip > 0:
+            if self.clip > 0 or guard:
                 hip.check(L.st5_sumsq_pair(g.data_ptr(), g2.data_ptr(), self.gnorm_sq.data_ptr(), g.numel(), 1.0, 0, hip.stream()), "st5_sumsq_pair")
-            hip.check(L.st5_adam_step_pair(self.pflat.data_ptr(), g.data_ptr(), g2.data_ptr(), 1, self.m.data_ptr(), self.v.data_ptr(), g.numel(),
-                                           lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
-                                           self.gnorm_sq.data_ptr() if self.clip > 0 else 0, self.clip, grad_scale,
-                                           self.wflat.data_ptr() if self.mirror is not None else 0, hyper, hip.stream()),
-                      "st5_adam_step_pair")
+            if guard:
+                hip.check(L.st5_adam_step_guard(self.pflat.data_ptr(), g.data_ptr(), g2.data_ptr(), 1, self.m.data_ptr(), self.v.data_ptr(),
+                                                g.numel(), lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
+                                                self.gnorm_sq.data_ptr(), max(self.clip, 0.0), grad_scale,
+                                                self.wflat.data_ptr() if self.mirror is not None else 0, hyper, guard, hip.stream()),
+                          "st5_adam_step_guard")
+            else:
+                hip.check(L.st5_adam_step_pair(self.pflat.data_ptr(), g.data_ptr(), g2.data_ptr(), 1, self.m.data_ptr(), self.v.data_ptr(), g.numel(),
+                                               lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
+                                               self.gnorm_sq.data_ptr() if self.clip > 0 else 0, self.clip, grad_scale,
+                                               self.wflat.data_ptr() if self.mirror is not None else 0, hyper, hip.stream()),
+                          "st5_adam_step_pair")
             self.ddp._pair_pending = False
             self.ddp._grads_zeroed = True
         else:
             self.ddp.sum_gradient_buffers()
-            if self.clip > 0:
+            if self.clip > 0 or guard:
                 hip.check(L.st5_sumsq(g.data_ptr(), self.gnorm_sq.data_ptr(), g.numel(), 1.0, 0, hip.F32, hip.stream()), "st5_sumsq")
             # (one buffer; the kernel leaves it zeroed in passing -- the second buffer, if there is one, is zero whenever no sum
             # is pending -- so the next zero_grad() has no fill to launch)
-            hip.check(L.st5_adam_step_pair(self.pflat.data_ptr(), g.data_ptr(), 0, 1, self.m.data_ptr(), self.v.data_ptr(), g.numel(),
-                                           lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
-                                           self.gnorm_sq.data_ptr() if self.clip > 0 else 0, self.clip, grad_scale,
-                                           self.wflat.data_ptr() if self.mirror is not None else 0, hyper, hip.stream()),
-                      "st5_adam_step_pair")
+            if guard:
+                hip.check(L.st5_adam_step_guard(self.pflat.data_ptr(), g.data_ptr(), 0, 1, self.m.data_ptr(), self.v.data_ptr(), g.numel(),
+                                                lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
+                                                self.gnorm_sq.data_ptr(), max(self.clip, 0.0), grad_scale,
+                                                self.wflat.data_ptr() if self.mirror is not None else 0, hyper, guard, hip.stream()),
+                          "st5_adam_step_guard")
+            else:
+                hip.check(L.st5_adam_step_pair(self.pflat.data_ptr(), g.data_ptr(), 0, 1, self.m.data_ptr(), self.v.data_ptr(), g.numel(),
+                                               lr, self.betas[0], self.betas[1], self.eps, self.wd, self.t,
+                                               self.gnorm_sq.data_ptr() if self.clip > 0 else 0, self.clip, grad_scale,
+                                               self.wflat.data_ptr() if self.mirror is not None else 0, hyper, hip.stream()),
+                          "st5_adam_step_pair")
             self.ddp._grads_zeroed = True
         # parameters changed in place through the flat view: invalidate the compute-dtype weight cache (entries that do
         # not come from the bf16 image: conv / fp32 / non-adjacent stacks) and refresh the transposed copies
+        # (a step the guard skipped: the host does not know, and everything below is idempotent on unchanged parameters -- the
+        #  transposes and the fp8 images are rewritten with the same bytes, a cleared cache is refilled with the same casts)
         Fn.weight_cache.clear()
         if self.mirror is not None:
             for p in self.ddp.params:

@@ -10,7 +10,10 @@ What makes a training step replayable:
     so the numpy / torch CPU random streams advance exactly as in eager mode;
   * data-dependent shapes are replaced by fixed-shape forms while recording (functional.static_shapes(): the NCE head scores
     every frame and passes selection masks; the sample size becomes a device scalar);
-  * the optimizer reads the learning rate and step count from device memory (FusedAdam.enable_device_hyper).
+  * the optimizer reads the learning rate and step count from device memory (FusedAdam.enable_device_hyper).  Behind the
+    finite-gradient guard (FusedAdam(skip_nonfinite=True)) the captured Adam node is st5_adam_step_guard: frozen
+    arguments like the others', one guard block for the life of the optimizer; the step count it reads advances by one per replay
+    (replay() pushes t + 1, then counts), which the guard block's parity cells rely on.
   * LayerDrop: the per-layer host draws are staged to the device as keep flags and the layer outputs are selected on the
     device (functional.layerdrop_select; modules/encoder.py, modules/decoder.py), so the recipe's --encoder-layerdrop /
     --decoder-layerdrop 0.05 replays (a dropped layer still runs; its output and gradients are discarded).

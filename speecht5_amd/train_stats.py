@@ -5,7 +5,9 @@ the list to `reduce_metrics`.  A replayed update has no such Python: the logged 
 private pool.  StatsRecorder is their way out without a host synchronisation:
 
   * at the first update it fixes the CELL LAYOUT: per micro-batch every entry of the aggregated logging output that is a one-element
-    device tensor (key path kept, e.g. `micro[0].speech_pretrain.loss_m_0`), plus `opt.gnorm_sq` when the update clips;
+    device tensor (key path kept, e.g. `micro[0].speech_pretrain.loss_m_0`), plus `opt.gnorm_sq` when the update clips -- and, for
+    an update behind the finite-gradient guard (PretrainUpdate(nonfinite="skip")), `opt.gnorm_sq` in any case and
+    `opt.skipped`, the flag cell of the optimizer's guard block: one more descriptor of the same launch;
   * every update ends with ONE st5_stats_record launch (csrc/train_stats.hip) that copies the scalars, widened to 8-byte cells, into
     row `counter % rows` of a device ring behind the stamp `counter` -- eagerly enqueued, recorded or as the last node of the captured
     graph, always the same kernel on the same ring;
@@ -124,18 +126,19 @@ class HarvestSchedule:
 
 
 class StatsRecorder:
-    def __init__(self, device, rows=64, clip_norm=0.0, grad_scale=1.0):
+    def __init__(self, device, rows=64, clip_norm=0.0, grad_scale=1.0, guard=False):
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self.clip_norm, self.grad_scale = float(clip_norm), float(grad_scale)
+        self.guard = bool(guard)    # the optimizer steps behind st5_adam_step_guard: its flag cell is logged as `skipped`
         self.sched = HarvestSchedule(rows, self._copy_ring, lambda ev: ev.query(), lambda ev: ev.synchronize(), self._read_row)
         self.rows = rows
         self.layout = None          # [(micro-batch, key path, "cell" | "host", dtype | None)] in the order of the logging output
         self.cell_types = []        # dtype per cell, in cell order
         self.paths = []             # key path string per cell
         self.n_cells = 0
-        self.gnorm_cell = None
+        self.gnorm_cell = self.skipped_cell = None
         self.ring = self.counter = self.images = self.addr_dev = self.types_dev = None
         self._addr_host = None      # two pinned images of the address column for eagerly enqueued steps
         self._addr_event = [None, None]
@@ -188,8 +191,12 @@ class StatsRecorder:
         self.cell_types = [v.dtype for v in cells]
         self.paths = [(cell_path(i, k) if i is not None else "opt." + k[0]) for i, k, kind, _ in layout if kind == "cell"]
         self.n_cells = n = len(cells)
-        if layout[-1][0] is None:
-            self.gnorm_cell = n - 1
+        opt_cells = [e[1][0] for e in layout if e[0] is None]      # (the optimizer's scalars are the last cells, in this order)
+        for j, name in enumerate(opt_cells):
+            if name == "gnorm_sq":
+                self.gnorm_cell = n - len(opt_cells) + j
+            elif name == "skipped":
+                self.skipped_cell = n - len(opt_cells) + j
         dev = self.device
         self.ring = torch.zeros(self.rows, 1 + n, dtype=torch.int64, device=dev)
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)
@@ -218,7 +225,10 @@ class StatsRecorder:
         """The record launch of one update, on the current stream (the update's own), behind everything that wrote a logged scalar.
         `aggs` hold the logged tensors: the caller keeps them referenced until this returns; under capture they are kept here until
         capture_done()."""
-        extra = [("gnorm_sq", opt.gnorm_sq)] if (opt is not None and self.clip_norm > 0) else []
+        extra = [("gnorm_sq", opt.gnorm_sq)] if (opt is not None and (self.clip_norm > 0 or self.guard)) else []
+        if self.guard:
+            from .ddp import GUARD_SKIPPED
+            extra.append(("skipped", opt.guard[GUARD_SKIPPED:GUARD_SKIPPED + 1]))     # (a view: the cell's own address)
         layout, cells, hosts = self._flatten(aggs, extra)
         if self.layout is None:
             self._fix(layout, cells)
@@ -305,7 +315,9 @@ class StatsRecorder:
                     hi += 1
             gsq = self._value(cells, self.gnorm_cell) if self.gnorm_cell is not None else None
             gnorm = math.sqrt(gsq) * self.grad_scale if gsq is not None else None
-            out.append({"ordinal": k, "gnorm_sq": gsq, "gnorm": gnorm, "clip": (gnorm > self.clip_norm) if gnorm is not None else None,
+            out.append({"ordinal": k, "gnorm_sq": gsq, "gnorm": gnorm,
+                        "clip": (gnorm > self.clip_norm) if (gnorm is not None and self.clip_norm > 0) else None,
+                        **({"skipped": self._value(cells, self.skipped_cell)} if self.skipped_cell is not None else {}),
                         "logging_outputs": aggs})
         if taken:
             last = taken[-1][0]

@@ -30,6 +30,24 @@ Statistics: stats=True (one rank) ends every update with one st5_stats_record la
 copies the logged device scalars of every micro-batch and the squared gradient norm into a row of a device ring; logging_outputs()
 returns, without waiting, the updates whose ring copy has completed, as the reference trainer's list of train_step outputs
 (train_stats.StatsRecorder).  Off by default: nothing is launched, allocated or computed for it.
+
+Non-finite gradients: nonfinite="skip" puts the Adam step behind a verdict on the device (ddp.FusedAdam(skip_nonfinite=True),
+st5_adam_step_guard).  An update whose squared gradient norm is NaN, inf or overflowed leaves parameters, both Adam
+moments and the bf16 image as they were and zeroes the gradient buffers; the next update trains on.  It works eagerly, recorded and
+replayed, in every `micro` mode, with and without a source: in the captured step the guarded launch IS the Adam node, with frozen
+arguments and one guard block for the life of the update.  What differs from the reference's trainer, which reads the norm on the host:
+  * `n` (fairseq's num_updates) counts ATTEMPTED updates -- the host cannot know a verdict in time without a synchronisation -- so a
+    skipped update still advances set_num_updates() and the learning-rate schedule (fairseq leaves num_updates standing).  The
+    schedule index is late by the number of skipped updates; Adam's own step count, kept on the device, is exact.
+  * a skipped update has still run its forward: buffers a forward updates (the post-net's BatchNorm running statistics) have seen the
+    batch, as they have in the reference on an overflowed step.  Nothing tries to undo that.
+  * several ranks: the norm is taken over the REDUCED gradient buffer, which holds the same bits on every rank, so every rank reaches
+    the same verdict on its own; no verdict is exchanged.
+With stats=True every update's entry carries `skipped` (0 / 1), read from the guard block by the same st5_stats_record launch.
+nonfinite_limit=k (needs stats=True) is a host policy on the harvested entries: when logging_outputs() or finish() see k consecutive
+skipped updates they raise FloatingPointError naming the first of them -- the counterpart of fairseq giving up at its minimum loss
+scale, and always late by up to one harvest of the ring (stats_rows // 2 updates), during which further updates were skipped too.
+nonfinite=None (default): nothing of this exists; the update is built and launched exactly as before.
 """
 import os
 
@@ -42,7 +60,7 @@ from . import functional as Fn
 class PretrainUpdate:
     def __init__(self, task, model, criterion, micro_batches, *, lr=2e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, clip_norm=5.0,
                  graph=True, micro="side_by_side", wgrad_stream=None, prefetch_host=True, device=None, lr_fn=None, exchange="phased", exchange_payload="fp32",
-                 stats=False, stats_rows=64):
+                 stats=False, stats_rows=64, nonfinite=None, nonfinite_limit=None):
         from .ddp import FlatGradDataParallel, FusedAdam
         assert micro in ("side_by_side", "in_turn_2buf", "in_turn")
         self.task, self.model, self.crit, self.micro = task, model, criterion, list(micro_batches)
@@ -51,6 +69,18 @@ class PretrainUpdate:
         self.device = device if device is not None else next(model.parameters()).device
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # (checked before anything is attached to the model)
+        if nonfinite not in (None, "skip"):
+            raise ValueError(f"nonfinite = {nonfinite!r}: None (no check, the default) or 'skip'")
+        if nonfinite_limit is not None:
+            if nonfinite != "skip" or not stats:
+                raise ValueError("nonfinite_limit is a policy on the harvested statistics of a guarded update: it needs nonfinite='skip' "
+                                 "and stats=True")
+            if not (isinstance(nonfinite_limit, int) and nonfinite_limit >= 1):
+                raise ValueError(f"nonfinite_limit = {nonfinite_limit!r}: a number of consecutive skipped updates, at least 1")
+        self.nonfinite_limit = nonfinite_limit
+        self._harvested = []          # entries taken out of the ring, not yet handed out by logging_outputs()
+        self._skip_run = 0            # consecutive skipped updates at the end of what was harvested so far ...
+        self._skip_run_first = None   # ... and the number of the first of them
         # stats=True: every update ends with one st5_stats_record launch (train_stats.StatsRecorder) and
         # logging_outputs() hands the caller what the reference's trainer logs; off, nothing below exists
         self.stats = None
@@ -66,13 +96,15 @@ class PretrainUpdate:
                 raise ValueError("stats=True with graph=True needs a criterion that keeps its logged scalars on the device "
                                  "(sync_logging=False): a `.item()` inside the captured step would fail the capture")
             from .train_stats import StatsRecorder
-            self.stats = StatsRecorder(self.device, rows=stats_rows, clip_norm=clip_norm, grad_scale=1.0 / len(self.micro))
+            self.stats = StatsRecorder(self.device, rows=stats_rows, clip_norm=clip_norm, grad_scale=1.0 / len(self.micro),
+                                       **({"guard": True} if nonfinite == "skip" else {}))
         # no weight-gradient stream, no attention helper stream: beside two micro-batch streams they cost time (42.0 against 31.5 ms,
         # profiles/r5_replay_hunt.txt); results are the same bits with and without them
         if wgrad_stream is None:
             wgrad_stream = False
         self.ddp = FlatGradDataParallel(model, wgrad_stream=wgrad_stream)
-        self.opt = FusedAdam(self.ddp, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_norm=clip_norm)
+        self.opt = FusedAdam(self.ddp, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, clip_norm=clip_norm,
+                             **({"skip_nonfinite": True} if nonfinite == "skip" else {}))
         self.lr_fn = lr_fn
         self.prefetch_host = prefetch_host
         assert exchange_payload in ("fp32", "bf16")
@@ -408,21 +440,45 @@ class PretrainUpdate:
         "gnorm" (sqrt(gnorm_sq) * grad_scale in fp64: what the clip compared), "clip", "logging_outputs": [agg per micro-batch, as
         train_step(sync=True) returns it]} -- SpeechT5Criterion.reduce_metrics(entry["logging_outputs"]) takes it as it takes the
         reference trainer's list.  wait=False never waits for the device: only rows whose copy has completed are returned.  wait=True
-        enqueues a final copy of the ring and waits for it."""
+        enqueues a final copy of the ring and waits for it.  nonfinite="skip": every entry also carries "skipped" (0 / 1), and
+        "gnorm" is reported with clip_norm == 0 too (of a skipped update it is inf or NaN).  nonfinite_limit=k: raises
+        FloatingPointError once the harvested entries end in k or more consecutive skipped updates (the entries are kept: a caller
+        that catches the error gets them from the next call)."""
         if self.stats is None:
             raise RuntimeError("logging_outputs(): this update was built with stats=False")
         if wait:
             self._drain_stats()
+        self._take_harvest()
+        out, self._harvested = self._harvested, []
+        return out
+
+    def _take_harvest(self):
+        """The rows whose ring copy has completed -> entries kept for the next logging_outputs(); nonfinite_limit is checked on every
+        entry once, here, after the entries are safe (a caller that catches the error still gets them from logging_outputs())."""
         got = self.stats.harvest()
-        out = []
+        new = []
         for e in got:
             k = e.pop("ordinal")
             n, lr = self._advanced[k - self._advanced_base]
-            out.append({"num_updates": n, "lr": lr, **e})
+            new.append({"num_updates": n, "lr": lr, **e})
         if got:
             del self._advanced[:k + 1 - self._advanced_base]
             self._advanced_base = k + 1
-        return out
+        self._harvested += new
+        if self.nonfinite_limit is not None:
+            hit = None
+            for e in new:
+                if not e["skipped"]:
+                    self._skip_run = 0
+                    continue
+                if self._skip_run == 0:
+                    self._skip_run_first = e["num_updates"]
+                self._skip_run += 1
+                if self._skip_run == self.nonfinite_limit and hit is None:
+                    hit = self._skip_run_first
+            if hit is not None:
+                raise FloatingPointError(f"gradients are Nan/Inf: {self.nonfinite_limit} consecutive updates were skipped, the first of "
+                                         f"them update {hit} (nonfinite_limit = {self.nonfinite_limit})")
 
     def _drain_stats(self):
         """One more copy of the ring on the update's stream, behind the newest update, and a wait for it."""
@@ -433,6 +489,11 @@ class PretrainUpdate:
             self.stats.drain()
 
     def finish(self):
+        self._finish()
+        if self.nonfinite_limit is not None:
+            self._take_harvest()     # (the policy sees the end of the run too; the entries stay for logging_outputs())
+
+    def _finish(self):
         if self.sg is not None:
             self.sg.drain()
             torch.cuda.current_stream(self.device).wait_stream(self.sg.stream)
@@ -440,7 +501,7 @@ class PretrainUpdate:
             self._drain_stats()      # (everything enqueued so far becomes available to the next logging_outputs())
 
     def close(self):
-        self.finish()
+        self._finish()               # (no policy check here: close() releases, it does not report)
         if self.feed is not None:
             self.feed.held = []      # (finish() ordered the caller's stream behind the last replay that read them)
         self.ddp.close()
