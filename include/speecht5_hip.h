@@ -601,6 +601,19 @@ int st5_ctc_loss_fwd(const float* lprobs, const int64_t* targets, const int64_t*
 int st5_ctc_loss_bwd(const float* lprobs, const int64_t* targets, const int64_t* target_offsets, const int64_t* input_lengths,
                      const int64_t* target_lengths, int32_t T, int32_t B, int32_t V, int32_t max_target_len, int32_t blank,
                      int32_t zero_infinity, const float* nll, const float* grad_out, const void* ws, float* grad, void* stream);
+/* ---- CTC labels packed per row on the device (csrc/ctc_loss.hip, index arithmetic in csrc/ctc_pack_index.h).  The torch call site it
+ * replaces is criterions.SpeechtoTextLoss.compute_loss_ctc's
+ *     targets_flat = sample["target"].masked_select((target != pad) & (target != eos));  offsets = cumsum(lengths) - lengths
+ * whose result has a data-dependent shape (a device-to-host read: no stream capture survives it).
+ * target int64 [B, L] right-padded (label + </s>).  packed int64 [B, L]: row b holds the entries of target[b] that are neither `pad`
+ * nor `eos`, in order, from column 0; the rest of the row is `pad` (every element is written).  offsets int64 [B] = b * L;
+ * kept int64 [B] = kept entries per row; total int64 [1] = sum of kept, WRITTEN (never accumulated into: no memset in front of a
+ * replayed launch).  (packed, offsets, lengths <= kept) with max_target_len = L is a legal input of st5_ctc_loss_fwd / _bwd: they
+ * read targets[offsets[b] + i] for i < min(length_b, max_target_len) and assume nothing else about offsets.  One launch of one
+ * workgroup, stable (ballot + prefix popcount per 64-column chunk), no atomics, no allocation, no host read: capturable.
+ * B == 0, L == 0, negative sizes, a null pointer and packed == target return ST5_ERR_ARG with nothing launched. */
+int st5_ctc_pack_rows(const int64_t* target, int64_t pad, int64_t eos, int32_t B, int32_t L, int64_t* packed, int64_t* offsets,
+                      int64_t* kept, int64_t* total, void* stream);
 /* ---- guided attention loss of the TTS criterion (text_to_speech_loss.py:370-427) ----
  * att [B, H, To, Ti] fp32 (the selected heads of the selected layers, concatenated), ilens / olens int64 [B] on the device.
  * fwd: out2 = {alpha * mean over (to < olen_b, ti < ilen_b) of (1 - exp(-(ti/ilen_b - to/olen_b)^2 / (2 sigma^2))) att, alpha / count}.

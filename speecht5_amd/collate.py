@@ -196,10 +196,39 @@ class TextToSpeechCollater:
 
 class SpeechToTextCollater:
     """SpeechToTextDataset.collater (data/speech_to_text_dataset.py:150-207) + collater_audio (:209-224) + collater_label (:232-241).
-    samples: [{"id", "source": fp32 [S] (device), "label_list": [int64 [n] (device)]}]."""
+    samples: [{"id", "source": fp32 [S] (device), "label_list": [int64 [n] (device)]}].
+    fixed_shape=(S, L): every batch has the same tensor shapes -- what a replayed update (graph.BatchFeed) needs of its source:
+    `source` / `padding_mask` are padded to S samples, `target` / `prev_output_tokens` to L columns with `pad`; an item with more
+    than S samples or more than L - 1 labels (label + </s> must fit) is refused with a ValueError naming it.  None (default): padded
+    to the batch's own maxima, the reference's batch.  Either way the padding mask carries its host copy as `_st5_host`."""
 
-    def __init__(self, device, *, pad_idx=1, eos_idx=2):
+    def __init__(self, device, *, pad_idx=1, eos_idx=2, fixed_shape=None):
         self.device, self.pad_idx, self.eos_idx = device, pad_idx, eos_idx
+        if fixed_shape is not None:
+            if not (isinstance(fixed_shape, (tuple, list)) and len(fixed_shape) == 2
+                    and all(isinstance(v, int) and v >= 1 for v in fixed_shape)):
+                raise ValueError(f"fixed_shape = {fixed_shape!r}: (samples per row, target columns), both at least 1")
+            fixed_shape = tuple(fixed_shape)
+        self.fixed_shape = fixed_shape
+
+    @staticmethod
+    def plan(ids, sizes, n_labels, fixed_shape=None):
+        """The batch's padded shape from host ints (no device work): (samples per row S, target columns T).  Without fixed_shape the
+        batch's own maxima (T = longest label + </s>); with it the fixed pair, and a ValueError naming the first item that is longer."""
+        if fixed_shape is None:
+            return max(sizes), max(n_labels) + 1
+        S, T = fixed_shape
+        for i, size, k in zip(ids, sizes, n_labels):
+            if size > S:
+                raise ValueError(f"item {i!r}: {size} samples, fixed_shape pads `source` to {S}")
+            if k + 1 > T:
+                raise ValueError(f"item {i!r}: {k} labels + </s>, fixed_shape has {T} target columns")
+        return S, T
+
+    @staticmethod
+    def host_padding_mask(sizes, S):
+        """The padding mask on the host from the items' host lengths: row b is padded from sizes[b] on."""
+        return torch.arange(S)[None, :] >= torch.tensor([int(v) for v in sizes], dtype=torch.long)[:, None]
 
     def collater(self, samples):
         samples = [s for s in samples if s["source"] is not None]
@@ -208,12 +237,14 @@ class SpeechToTextCollater:
         dev, B = self.device, len(samples)
         audios = [s["source"].contiguous() for s in samples]
         sizes = [int(a.shape[0]) for a in audios]
-        S = max(sizes)
-        source = _ragged(audios, [0] * B, sizes, B, S, 1, 1, 0, torch.float32, 0.0, dev)
-        padding_mask = _tail(sizes, B, S, False, dev)
         labs = [s["label_list"][0].contiguous() for s in samples]
         n = [int(t.shape[0]) for t in labs]
-        T = max(n) + 1
+        S, T = self.plan([s["id"] for s in samples], sizes, n, self.fixed_shape)      # (refuses before anything is launched)
+        source = _ragged(audios, [0] * B, sizes, B, S, 1, 1, 0, torch.float32, 0.0, dev)
+        padding_mask = _tail(sizes, B, S, False, dev)
+        # the same mask on the host, from the lengths that are host ints anyway (as SpeechPretrainCollater attaches it): the span-mask
+        # draw reads it without a device->host read, and the batch feed of a replayed update takes it as the batch's mirror
+        padding_mask._st5_host = self.host_padding_mask(sizes, S)
         rows = torch.arange(B, device=dev)
         nd = _lengths(n, dev)
         # decoder target (:167-181): label + </s>, right-padded; decoder input (:183-189): </s> moved to the front

@@ -312,9 +312,15 @@ class SpeechtoTextLoss(nn.Module):
     wv_errors, and a set `wer_kenlm_model` is ignored with a one-time warning."""
 
     def __init__(self, cfg, task, sentence_avg=True, label_smoothing=0.1, ignore_prefix_size=0, report_accuracy=False,
-                 ce_weight=1.0, ctc_weight=0.0, sync_logging=True):
+                 ce_weight=1.0, ctc_weight=0.0, sync_logging=True, *, device_targets=False):
         super().__init__()
         self.task = task
+        # device_targets=True: the CTC labels are packed per row on the device (st5_ctc_pack_rows, Fn.ctc_loss_rows) instead of
+        # `target.masked_select(...)`, whose data-dependent shape is a device-to-host read -- the form a captured step needs.  The
+        # logged `ntokens` is then the kernel's count of labels (entries that are neither pad nor eos): an int64 device scalar under
+        # sync_logging=False, so a replayed update reports it per batch.  Precondition, the reference's own: labels contain neither
+        # pad nor eos.  Under it loss and gradients are the same bits in both modes.
+        self.device_targets = bool(device_targets)
         self.blank_idx = task.target_dictionary.index(getattr(task, "blank_symbol", "<ctc_blank>"))
         self.pad_idx = task.target_dictionary.pad()
         self.eos_idx = task.target_dictionary.eos()
@@ -328,6 +334,7 @@ class SpeechtoTextLoss(nn.Module):
         self.post_process = getattr(cfg, "post_process", "sentencepiece")
         self._byte_tables = {}     # asr_metrics.byte_table's cache: the dictionary's byte table on the device, built once
         self.metric_flag = None    # int32 [1] on the device: 1 once a validation step met a token id outside the dictionary
+        self._label_total = None   # (device_targets) the pack kernel's label count of the forward in flight, until it is logged
         if getattr(cfg, "wer_kenlm_model", None) is not None or getattr(cfg, "wer_args", None) is not None:
             from . import asr_metrics
             asr_metrics._warn_once("kenlm", "wer_kenlm_model / wer_args: there is no KenLM / lexicon decoder here; w_errors is counted "
@@ -356,11 +363,22 @@ class SpeechtoTextLoss(nn.Module):
             loss = self.ce_weight * loss_ce + self.ctc_weight * loss_ctc
         else:
             loss = loss_ce if self.ce_weight > 0 else loss_ctc
-        ntokens = sample["ntokens"] if "ntokens" in sample else sample["target_lengths"].sum().item()
-        sample_size = sample["target"].size(0) if self.sentence_avg else ntokens
+        if self.device_targets:
+            # the pack kernel's count of the batch's labels (ctc_weight == 0: the launch is made for the count alone): per batch also
+            # in a replayed update, where a host value of the sample is the captured pass's.  sample_size stays what it is without the
+            # keyword: B, or the host ntokens (a sample that carries none costs one device read, as it does without the keyword)
+            total, self._label_total = self._label_total, None
+            if total is None:
+                total = Fn.ctc_pack_rows(sample["target"], self.pad_idx, self.eos_idx)[3]
+            logged_ntokens = _item(total[0], s)
+            sample_size = sample["target"].size(0) if self.sentence_avg else (sample["ntokens"] if "ntokens" in sample else int(total))
+        else:
+            ntokens = sample["ntokens"] if "ntokens" in sample else sample["target_lengths"].sum().item()
+            sample_size = sample["target"].size(0) if self.sentence_avg else ntokens
+            logged_ntokens = ntokens
         log = {"loss": _item(loss, s), "ce_loss": _item(loss_ce, s) if loss_ce is not None else 0,
                "ctc_loss": _item(loss_ctc, s) if loss_ctc is not None else 0, "nll_loss": _item(nll, s) if nll is not None else 0,
-               "ntokens": ntokens, "nsentences": sample["target"].size(0), "sample_size": sample_size}
+               "ntokens": logged_ntokens, "nsentences": sample["target"].size(0), "sample_size": sample_size}
         if self.ce_weight > 0 and self.report_accuracy:
             n_correct, total = self.compute_accuracy(model, net_output_decoder, sample)
             log["n_correct"] = _item(n_correct, s)
@@ -401,6 +419,15 @@ class SpeechtoTextLoss(nn.Module):
 
     def compute_loss_ctc(self, model, net_output, sample, ctc_inputs=None):
         lprobs, input_lengths = ctc_inputs if ctc_inputs is not None else self._ctc_inputs(model, net_output)
+        if self.device_targets:
+            if not (lprobs.is_cuda and lprobs.dtype == torch.float32):
+                raise RuntimeError(f"CTC loss: expected fp32 log-probabilities on the GPU (csrc/ctc_loss.hip), got {lprobs.dtype} on {lprobs.device}")
+            if "target_lengths" not in sample:
+                raise ValueError("SpeechtoTextLoss(device_targets=True) needs sample['target_lengths'] (label + </s> per row, as the "
+                                 "collater provides them)")
+            loss, self._label_total = Fn.ctc_loss_rows(lprobs, sample["target"], input_lengths, sample["target_lengths"] - 1, self.pad_idx,
+                                                       self.eos_idx, self.blank_idx, self.zero_infinity, return_total=True)
+            return loss
         pad_mask = (sample["target"] != self.pad_idx) & (sample["target"] != self.eos_idx)
         targets_flat = sample["target"].masked_select(pad_mask)
         target_lengths = sample["target_lengths"] if "target_lengths" in sample else pad_mask.sum(-1)
@@ -430,13 +457,13 @@ class SpeechT5Criterion(FairseqCriterion):
                  use_masking=True, use_weighted_masking=False, loss_type="L1", bce_pos_weight=5.0, bce_loss_lambda=1.0,
                  use_guided_attn_loss=False, num_heads_applied_guided_attn=2, ce_weight=1.0, ctc_weight=0.0, hubert_weight=1.0,
                  dec_weight=1.0, bart_weight=1.0, pred_masked_weight=1.0, pred_nomask_weight=0.0, loss_weights=None, cfg=None,
-                 sync_logging=True, guided_attn_loss_lambda=1.0, guided_attn_loss_sigma=0.4, log_keys=None):
+                 sync_logging=True, guided_attn_loss_lambda=1.0, guided_attn_loss_sigma=0.4, log_keys=None, device_targets=False):
         super().__init__(task)
         self.speech_criterion = TexttoSpeechLoss(task, sentence_avg, use_masking, use_weighted_masking, loss_type, bce_pos_weight,
                                                  bce_loss_lambda, use_guided_attn_loss, guided_attn_loss_sigma, guided_attn_loss_lambda,
                                                  2, num_heads_applied_guided_attn, sync_logging=sync_logging)
         self.text_criterion = SpeechtoTextLoss(cfg, task, sentence_avg, label_smoothing, ignore_prefix_size, report_accuracy,
-                                               ce_weight, ctc_weight, sync_logging=sync_logging)
+                                               ce_weight, ctc_weight, sync_logging=sync_logging, device_targets=device_targets)
         self.text_pretrain_criterion = TextPretrainCriterion(task, sentence_avg, bart_weight, loss_weights, sync_logging=sync_logging)
         self.speech_pretrain_criterion = SpeechPretrainCriterion(task, sentence_avg, pred_masked_weight, pred_nomask_weight,
                                                                  loss_weights, log_keys, use_masking, use_weighted_masking, loss_type,

@@ -17,6 +17,7 @@
 #include <stdint.h>
 #include <math.h>
 #include "common.h"
+#include "ctc_pack_index.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
@@ -207,6 +208,56 @@ __global__ __launch_bounds__(CTC_THREADS) void ctc_grad_kernel(const float* __re
   }
 }
 
+// ---- CTC labels packed per row (the device form of sample["target"].masked_select(target != pad & target != eos)) ---------------
+// One workgroup of CP_WAVES waves, one wave per row (rows dealt out wave by wave).  A wave walks its row in chunks of 64 columns: every lane reads its
+// column, the chunk's ballot of kept entries gives each kept lane its destination -- the running base plus the popcount of the
+// ballot below the lane (ctc_pack_index.h) -- and the base moves on by the ballot's popcount: a stable compaction without atomics,
+// the same on every launch.  The rest of the row is filled with `pad`, so every element of `packed` is written.  The waves' kept
+// counts are summed through LDS in a fixed order and `total` is WRITTEN (a replay needs no memset in front of the launch).
+__global__ __launch_bounds__(CP_THREADS) void ctc_pack_rows_kernel(const long long* __restrict__ target, long long pad, long long eos,
+                                                                   long long B, long long L, long long* __restrict__ packed,
+                                                                   long long* __restrict__ offsets, long long* __restrict__ kept,
+                                                                   long long* __restrict__ total) {
+  __shared__ long long wave_total[CP_WAVES];
+  const int lane = threadIdx.x & (CP_WAVE - 1), wave = threadIdx.x / CP_WAVE;
+  const long long chunks = cp_chunks(L);
+  long long mine = 0;                                   // (wave-uniform) kept entries of this wave's rows
+  for (long long b = wave; b < B; b += CP_WAVES) {
+    const long long row = cp_offset(b, L);
+    long long base = 0;
+    // CP_AHEAD chunks are loaded before the first of them is compacted: the loads do not depend on the running base, the launch is
+    // latency-bound (a row is a few chunks), and one round trip to memory then serves CP_AHEAD chunks
+    for (long long c0 = 0; c0 < chunks; c0 += CP_AHEAD) {
+      long long v[CP_AHEAD];
+#pragma unroll
+      for (int j = 0; j < CP_AHEAD; ++j) {
+        const long long col = cp_column(c0 + j, lane);
+        v[j] = col < L ? target[row + col] : pad;        // (a column behind the row reads nothing and counts as padding)
+      }
+#pragma unroll
+      for (int j = 0; j < CP_AHEAD; ++j) {
+        const bool keep = cp_column(c0 + j, lane) < L && cp_keep(v[j], pad, eos);
+        const uint64_t ballot = __ballot(keep);
+        if (keep) packed[row + cp_lane_dest(base, ballot, lane)] = v[j];
+        base = cp_next_base(base, ballot);
+      }
+    }
+    for (long long col = cp_tail_first(base, lane); col < L; col += CP_WAVE) packed[row + col] = pad;
+    if (lane == 0) {
+      offsets[b] = row;
+      kept[b] = base;
+    }
+    mine += base;
+  }
+  if (lane == 0) wave_total[wave] = mine;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    long long t = 0;
+    for (int w = 0; w < CP_WAVES; ++w) t += wave_total[w];
+    total[0] = t;
+  }
+}
+
 // ---- guided attention ------------------------------------------------------------------------------------------------------
 __device__ __forceinline__ float ga_weight(int to, int ti, float olen, float ilen, float inv_two_sigma_sq) {
   const float dlt = (float)ti / ilen - (float)to / olen;
@@ -322,6 +373,19 @@ extern "C" int st5_ctc_loss_bwd(const float* lprobs, const int64_t* targets, con
                      reinterpret_cast<const long long*>(targets), reinterpret_cast<const long long*>(target_offsets),
                      reinterpret_cast<const long long*>(input_lengths), reinterpret_cast<const long long*>(target_lengths), d, zero_infinity,
                      static_cast<const float*>(ws), nll, grad_out, grad);
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+
+extern "C" int st5_ctc_pack_rows(const int64_t* target, int64_t pad, int64_t eos, int32_t B, int32_t L, int64_t* packed, int64_t* offsets,
+                                 int64_t* kept, int64_t* total, void* stream) {
+  if (cp_check(B, L)) return ST5_ERR_ARG;
+  if (B == 0 || L == 0) return ST5_ERR_ARG;             // (nothing to pack: refused like the loss kernels' B <= 0, not launched)
+  if (!target || !packed || !offsets || !kept || !total) return ST5_ERR_ARG;
+  if ((const void*)target == (const void*)packed) return ST5_ERR_ARG;   // (not an in-place operation)
+  hipLaunchKernelGGL(ctc_pack_rows_kernel, dim3(1), dim3(CP_THREADS), 0, (hipStream_t)stream, reinterpret_cast<const long long*>(target),
+                     (long long)pad, (long long)eos, (long long)B, (long long)L, reinterpret_cast<long long*>(packed),
+                     reinterpret_cast<long long*>(offsets), reinterpret_cast<long long*>(kept), reinterpret_cast<long long*>(total));
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }

@@ -1571,6 +1571,36 @@ def ctc_loss_sum(lprobs, targets_flat, input_lengths, target_lengths, blank, zer
     return CTCLossFunction.apply(lprobs, targets_flat, offsets, input_lengths, target_lengths, max_target_len, blank, zero_infinity)
 
 
+def ctc_pack_rows(target, pad, eos):
+    """st5_ctc_pack_rows on the current stream: target int64 [B, L] (right-padded, label + </s>) -> (packed [B, L], offsets [B],
+    kept [B], total [1]), all int64 on the device.  Row b of `packed` holds the entries of target[b] that are neither `pad` nor `eos`,
+    in order, from column 0, the rest `pad`; offsets[b] = b * L; total = kept.sum(), written by the same launch.  No host read."""
+    if not (torch.is_tensor(target) and target.is_cuda and target.dtype == torch.int64 and target.dim() == 2):
+        raise ValueError("st5_ctc_pack_rows: target is an int64 [B, L] tensor on the GPU")
+    B, L = target.shape
+    if B == 0 or L == 0:
+        raise ValueError(f"st5_ctc_pack_rows: an empty target batch {tuple(target.shape)}")
+    target = target.contiguous()
+    packed = torch.empty_like(target)
+    meta = torch.empty(2 * B + 1, dtype=torch.int64, device=target.device)
+    offsets, kept, total = meta[:B], meta[B:2 * B], meta[2 * B:]
+    hip.check(hip.lib().st5_ctc_pack_rows(target.data_ptr(), int(pad), int(eos), B, L, packed.data_ptr(), offsets.data_ptr(),
+                                          kept.data_ptr(), total.data_ptr(), hip.stream()), "st5_ctc_pack_rows")
+    return packed, offsets, kept, total
+
+
+def ctc_loss_rows(lprobs, target, input_lengths, target_lengths, pad, eos, blank, zero_infinity=True, return_total=False):
+    """ctc_loss_sum for a right-padded target batch int64 [B, L] WITHOUT the masked_select in front of it: the labels are packed per
+    row on the device (ctc_pack_rows) and the CTC kernels read row b at offset b * L, with max_target_len = L.  Precondition (the
+    reference's masked_select + target_lengths - 1 has the same): the labels contain neither `pad` nor `eos`, and target_lengths[b]
+    is at most the number of labels of row b -- then both forms hand the same labels and lengths to the same kernels, and loss and
+    gradient are the same bits.  return_total: also the number of labels of the batch, an int64 device tensor of one element."""
+    packed, offsets, _, total = ctc_pack_rows(target, pad, eos)
+    loss = CTCLossFunction.apply(lprobs, packed, offsets, input_lengths, target_lengths.to(lprobs.device), target.size(1), blank,
+                                 zero_infinity)
+    return (loss, total) if return_total else loss
+
+
 class GuidedAttentionFunction(torch.autograd.Function):
     """alpha * mean of the guided-attention penalty over the valid (to, ti) region (csrc/ctc_loss.hip)."""
 

@@ -37,6 +37,10 @@ from . import functional as Fn
 HOST_VALUES_FREE = {
     "speech_pretrain": ("ntokens", "ntokens_list", "nsentences", "src_lengths"),
     "text_pretrain": ("nsentences",),
+    # ASR fine-tuning: `ntokens` is free because update.PretrainUpdate only takes an s2t micro-batch under a source when nothing
+    # captured reads it -- the criterion divides by B (sentence_avg=True) and logs the pack kernel's count (device_targets=True);
+    # DESIGN.md 4m has the audit of every host value of an s2t sample
+    "s2t": ("ntokens", "nsentences"),
 }
 # keys a criterion writes into the sample it is given (criterions.py: dec_weight == 0, ce_weight == 0): not part of a batch
 CRITERION_WRITTEN = ("net_input.only_hubert", "only_ctc")

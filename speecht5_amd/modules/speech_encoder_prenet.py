@@ -287,11 +287,16 @@ class SpeechEncoderPrenet(nn.Module):
             mask_indices = pre_mask if pre_mask is not None else self._sample_mask(B, T, padding_mask.cpu(), x.device)
             x = Fn.masked_fill_rows(x, mask_indices.reshape(-1), self.mask_emb)
         if self.mask_channel_prob > 0:
-            # same numpy draw as the reference (speech_encoder_prenet.py:253-263), taken right after the time mask
-            mc = compute_mask_indices((B, C), None, self.mask_channel_prob, self.mask_channel_length, self.mask_channel_selection,
-                                      self.mask_channel_other, no_overlap=self.no_mask_channel_overlap,
-                                      min_space=self.mask_channel_min_space)
-            x = Fn.mask_channels(x, torch.from_numpy(mc).to(x.device, non_blocking=True))
+            # same numpy draw as the reference (speech_encoder_prenet.py:253-263), taken right after the time mask.  A staged host
+            # input like the time mask: eagerly this is the draw + `.to(device, non_blocking=True)`; a recorded step keeps the
+            # producer and runs it again before every replay, behind the time mask's and in front of the LayerDrop draws -- the order
+            # of the eager forward, so numpy's stream stays where the eager loop leaves it and every replay has its own channel mask
+            def draw_channels():
+                return torch.from_numpy(compute_mask_indices((B, C), None, self.mask_channel_prob, self.mask_channel_length,
+                                                             self.mask_channel_selection, self.mask_channel_other,
+                                                             no_overlap=self.no_mask_channel_overlap,
+                                                             min_space=self.mask_channel_min_space))
+            x = Fn.mask_channels(x, Fn.stage_host(draw_channels, x.device))
         return x, mask_indices
 
     def set_num_updates(self, num_updates):

@@ -41,14 +41,46 @@ LOGGED_SAMPLE_VALUES = {
 }
 
 
-def check_feed_host_values(task_names, free):
+# Entries of LOGGED_SAMPLE_VALUES that a criterion OPTION takes off the host: {task name: {logging key: how}}.  The s2t criterion
+# with device_targets=True logs the pack kernel's label count as `ntokens` (a device cell), and with sentence_avg=True its
+# `sample_size` is B, a function of the batch signature.  check_feed_host_values skips exactly the keys its caller names.
+DEVICE_LOGGED_OPTIONS = {
+    "s2t": {"ntokens": "device_targets=True", "sample_size": "sentence_avg=True"},
+}
+
+
+def device_logged(task_name, criterion):
+    """The logging keys of LOGGED_SAMPLE_VALUES[task_name] that `criterion` (a SpeechT5Criterion, or the task's own criterion) does
+    not take from the sample's host value, as check_feed_host_values' `device_logged` entry for that task."""
+    if task_name != "s2t":
+        return ()
+    c = getattr(criterion, "text_criterion", criterion)
+    keys = []
+    if getattr(c, "device_targets", False):
+        keys.append("ntokens")
+    if getattr(c, "sentence_avg", False):
+        keys.append("sample_size")
+    return tuple(keys)
+
+
+def check_feed_host_values(task_names, free, device_logged=None):
     """Refuse, by name, a criterion whose log carries a sample's host value that the feed lets vary per batch (`free`:
-    graph.HOST_VALUES_FREE): a replay would report the captured pass's value for every batch."""
+    graph.HOST_VALUES_FREE): a replay would report the captured pass's value for every batch.  device_logged: {task name: logging
+    keys the criterion at hand does NOT take from the host} (DEVICE_LOGGED_OPTIONS names the options; device_logged() reads them off
+    a criterion) -- those keys are not checked; a key outside DEVICE_LOGGED_OPTIONS is refused."""
+    device_logged = device_logged or {}
+    for name, keys in device_logged.items():
+        for key in keys:
+            if key not in DEVICE_LOGGED_OPTIONS.get(name, {}):
+                raise ValueError(f"stats: no option of the {name} criterion is known to keep `{key}` off the host "
+                                 "(train_stats.DEVICE_LOGGED_OPTIONS)")
     for i, name in enumerate(task_names):
         if name not in LOGGED_SAMPLE_VALUES:
             raise ValueError(f"stats: micro_batches[{i}].task_name {name!r}: no audit of this criterion's host-valued logging entries "
                              "(train_stats.LOGGED_SAMPLE_VALUES); it cannot be replayed under a source with stats=True")
         for key, src in LOGGED_SAMPLE_VALUES[name].items():
+            if key in device_logged.get(name, ()):
+                continue
             if src in free.get(name, ()):
                 raise ValueError(f"stats: the {name} criterion logs `{key}` from the sample's host value `{src}`, which the batch feed lets "
                                  "differ from batch to batch; a replayed update cannot report it")

@@ -48,6 +48,14 @@ nonfinite_limit=k (needs stats=True) is a host policy on the harvested entries: 
 skipped updates they raise FloatingPointError naming the first of them -- the counterpart of fairseq giving up at its minimum loss
 scale, and always late by up to one harvest of the ring (stats_rows // 2 updates), during which further updates were skipped too.
 nonfinite=None (default): nothing of this exists; the update is built and launched exactly as before.
+
+ASR fine-tuning (an s2t micro-batch): under a source the criterion must run with sentence_avg=True and, with a CTC term,
+device_targets=True (check_s2t_source refuses by option name); the source is collate.SpeechToTextCollater(fixed_shape=...).
+Freeze boundaries: --freeze-encoder-updates / --freeze-decoder-updates are host decisions of the forward (`threshold <= num_updates`),
+so a captured step has the decision of the update it was captured with.  update() raises RuntimeError, before anything is enqueued or
+pulled, when the coming replay's update number lies on the other side of a threshold; recapture=True (needs prefetch_host=False)
+instead drops the graph there and runs prepare_graph() again -- that update() call executes two updates, as recording steps -- with
+source, statistics and optimizer carrying on; `captures` counts the graphs, `opt.t` the updates.
 """
 import os
 
@@ -57,15 +65,71 @@ import torch.distributed as dist
 from . import functional as Fn
 
 
+FREEZE_OPTIONS = ("freeze_encoder_updates", "freeze_decoder_updates")
+
+
+def freeze_thresholds(model):
+    """{option: sorted thresholds} over the modules of `model` that decide `threshold <= num_updates` on the host in their forward
+    (modules/encoder.py, modules/speech_encoder_prenet.py for --freeze-encoder-updates; the decoder's pre- / post-nets and layers for
+    --freeze-decoder-updates).  A captured step has that decision baked in."""
+    out = {}
+    for m in model.modules():
+        for opt in FREEZE_OPTIONS:
+            v = getattr(m, opt, None)
+            if isinstance(v, (int, float)) and not isinstance(v, bool):
+                out.setdefault(opt, set()).add(v)
+    return {k: sorted(v) for k, v in out.items()}
+
+
+def freeze_crossing(thresholds, n_captured, n):
+    """The first (option, threshold) whose decision `threshold <= num_updates` differs between update `n_captured` (the update number
+    the graph's forward was captured with) and update `n`; None when every module decides as captured."""
+    for opt in sorted(thresholds):
+        for thr in thresholds[opt]:
+            if (thr <= n_captured) != (thr <= n):
+                return opt, thr
+    return None
+
+
+def check_s2t_source(micro_batches, criterion, graph=True):
+    """An s2t micro-batch under a source of a replayed update (graph.HOST_VALUES_FREE lets its host `ntokens` differ from batch to
+    batch): refuse, naming the option, a criterion that puts that host value -- or a host read -- into the captured step."""
+    if not graph:
+        return
+    for i, s in enumerate(micro_batches):
+        if s.get("task_name") != "s2t":
+            continue
+        c = getattr(criterion, "text_criterion", criterion)
+        if not getattr(c, "sentence_avg", False):
+            raise ValueError(f"micro_batches[{i}] (s2t) under a source needs the criterion's sentence_avg=True: with sentence_avg=False the "
+                             "sample's host `ntokens` is the loss divisor, a launch argument of the captured step, and the batch feed "
+                             "lets it differ from batch to batch")
+        if getattr(c, "ctc_weight", 0) > 0 and not getattr(c, "device_targets", False):
+            raise ValueError(f"micro_batches[{i}] (s2t) under a source with ctc_weight > 0 needs the criterion's device_targets=True: "
+                             "device_targets=False builds the CTC targets with masked_select, a device-to-host read no capture survives")
+
+
 class PretrainUpdate:
     def __init__(self, task, model, criterion, micro_batches, *, lr=2e-4, betas=(0.9, 0.98), eps=1e-6, weight_decay=0.01, clip_norm=5.0,
                  graph=True, micro="side_by_side", wgrad_stream=None, prefetch_host=True, device=None, lr_fn=None, exchange="phased", exchange_payload="fp32",
-                 stats=False, stats_rows=64, nonfinite=None, nonfinite_limit=None):
+                 stats=False, stats_rows=64, nonfinite=None, nonfinite_limit=None, recapture=False):
         from .ddp import FlatGradDataParallel, FusedAdam
         assert micro in ("side_by_side", "in_turn_2buf", "in_turn")
         self.task, self.model, self.crit, self.micro = task, model, criterion, list(micro_batches)
         self.mode = micro
         self.use_graph = graph
+        # recapture=True: a replay that would cross a freeze boundary (--freeze-encoder-updates / --freeze-decoder-updates: host
+        # decisions of the forward, baked into the captured step) drops the graph and runs prepare_graph() again instead of raising.
+        # The helper thread prepares a replay one step ahead -- its host draws and the pulled batch would belong to a replay that
+        # never runs -- so this needs prefetch_host=False
+        if recapture and prefetch_host:
+            raise ValueError("recapture=True needs prefetch_host=False: under prefetch the next replay's batch is already pulled and its "
+                             "host random numbers are drawn when the freeze boundary is met")
+        self.recapture = bool(recapture)
+        self.captures = 0             # graphs captured so far (prepare_graph() calls that completed)
+        self._freeze = freeze_thresholds(model)
+        self._graph_n = None          # the update number the captured forward was traced with (= the first replay's)
+        self._graph_replays = 0       # replays of the current graph
         self.device = device if device is not None else next(model.parameters()).device
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         # (checked before anything is attached to the model)
@@ -369,6 +433,7 @@ class PretrainUpdate:
         if self.sg is not None and self.sg.feed is None:
             raise RuntimeError("set_source() after prepare_graph(): the batch load is the first node of the captured step and this "
                                "graph was captured without it")
+        check_s2t_source(self.micro, self.crit, graph=self.use_graph)
         if self.feed is None:
             self.feed = BatchFeed(self.micro, self.device)
         self.feed.set_source(iterable)
@@ -400,6 +465,14 @@ class PretrainUpdate:
     def prepare_graph(self):
         """Two recording updates + capture (three updates' worth of host random draws; two of them executed)."""
         from .graph import StepGraph
+        # the two recording steps and the captured pass run as updates n + 1, n + 2, n + 3: every module must take the same freeze
+        # decision in all three, or the captured step is not the recorded one
+        hit = freeze_crossing(self._freeze, self.n + 1, self.n + 3) or freeze_crossing(self._freeze, self.n + 2, self.n + 3)
+        if hit is not None:
+            raise RuntimeError(f"prepare_graph() at update {self.n + 1}: {hit[0]} = {hit[1]} lies inside the two recording steps and the "
+                               f"captured pass (updates {self.n + 1} to {self.n + 3}); run eager updates up to the boundary first")
+        if self.feed is not None:
+            check_s2t_source(self.micro, self.crit)
         if self.phased:
             phases, between = self.phase_fns() if self.mode == "in_turn" else self.phase_fns_side_by_side()
             self.sg = StepGraph(None, opt=self.opt, model=self.model, device=self.device, on_step=self.advance,
@@ -411,25 +484,60 @@ class PretrainUpdate:
                                 after_fn=self.exchange_and_update if self.split else None, stream=self.stream, feed=self.feed)
         if self.stats is not None and self.feed is not None:
             from .graph import HOST_VALUES_FREE
-            from .train_stats import check_feed_host_values
-            check_feed_host_values([s.get("task_name") for s in self.micro], HOST_VALUES_FREE)
+            from .train_stats import check_feed_host_values, device_logged
+            names = [s.get("task_name") for s in self.micro]
+            check_feed_host_values(names, HOST_VALUES_FREE, {n: device_logged(n, self.crit) for n in set(names) if device_logged(n, self.crit)})
         self.sg.record()
         self.sg.record()
         self.sg.capture()
+        self.captures += 1
+        self._graph_n, self._graph_replays = self.n, 0     # (capture() primed the first replay: advance() has counted it)
         if self.stats is not None:
             with torch.cuda.stream(self.sg.stream):
                 self.stats.capture_done()     # (the captured record node's source addresses, uploaded once: constant over replays)
         return self.sg
+
+    def _release_graph(self):
+        """Drop the captured graph: break the cycle update -> graph -> bound step function -> update (a HIP graph object must not wait
+        for the cyclic collector: a collection during a LATER capture destroys it mid-capture)."""
+        if self.sg is not None:
+            self.sg.step_fn = self.sg.after_fn = self.sg.on_step = self.sg.phases = self.sg.between = None
+            self.sg.graph = self.sg.graphs = None
+            self._ph = None
+            self._ph_sbs = None
+            self.sg = None
+
+    def _check_freeze(self):
+        """In front of a replay, before anything is enqueued or pulled: does update `n` decide its freezes as the captured step does?
+        Returns True when the graph was dropped and captured again (recapture=True: two updates ran, as recording steps)."""
+        n = self._graph_n + self._graph_replays
+        hit = freeze_crossing(self._freeze, self._graph_n, n)
+        if hit is None:
+            return False
+        if not self.recapture:
+            raise RuntimeError(f"{hit[0]} = {hit[1]}: the graph was captured at update {self._graph_n} and update {n} lies on the other "
+                               "side of the boundary -- the replay would run the captured freeze decision.  Capture again from here "
+                               "(PretrainUpdate(recapture=True, prefetch_host=False) does), or run eagerly")
+        # the replays enqueued so far finish before their graph goes (its pool holds their buffers); the host side -- update counter,
+        # random streams, source -- stands where an eager loop has it after update n - 1: prepare_graph() carries on from there
+        self.sg.drain()
+        self.sg.stream.synchronize()
+        self._release_graph()
+        self.prepare_graph()
+        return True
 
     def update(self):
         """The next update: a replay when a graph exists, else eager."""
         if self.sg is not None:
             if self.feed is not None:      # (the source runs on the caller's stream; the replay waits for an event behind it)
                 self.feed.caller_stream = torch.cuda.current_stream(self.device)
+            if self._freeze and self._check_freeze():
+                return                     # (recapture=True: this call ran the two recording updates of the new graph instead of a replay)
             with torch.cuda.stream(self.sg.stream):
                 if self.stats is not None:
                     self.stats.before_replay()
                 self.sg.replay()
+                self._graph_replays += 1
                 if self.stats is not None:
                     self.stats.replayed()     # (host bookkeeping; every stats_rows // 2 updates one asynchronous copy of the ring)
         else:
@@ -507,12 +615,7 @@ class PretrainUpdate:
         self.ddp.close()
         if self.stats is not None:
             self.stats.close()
-        if self.sg is not None:      # break the cycle update -> graph -> bound step function -> update: a HIP graph object must
-            self.sg.step_fn = self.sg.after_fn = self.sg.on_step = self.sg.phases = self.sg.between = None   # not wait for the cyclic
-            self.sg.graph = self.sg.graphs = None    # collector (a collection during a LATER capture destroys it mid-capture)
-            self._ph = None
-            self._ph_sbs = None
-            self.sg = None
+        self._release_graph()
 
     def state(self):
         torch.cuda.synchronize(self.device)
