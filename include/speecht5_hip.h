@@ -981,6 +981,24 @@ int st5_batch_load(const void* const* src, const void* const* dst, const int64_t
 int st5_stats_record(const void* const* src, const int32_t* types, void* ring, int64_t* counter, int32_t rows, int32_t n_cells,
                      void* stream);
 
+/* ---- state digest: one 64-bit digest per segment of a set of device segments, the check of a checkpoint's bytes on their way
+ *      from the device to a file (csrc/state_digest.hip, arithmetic in csrc/state_digest_index.h; speecht5_amd/checkpoint.py).
+ * Definition, all arithmetic mod 2^64, for a segment of n bytes: w_i its little-endian 8-byte words (the last one zero-padded),
+ *   digest = h((sum over i of h(w_i + (i + 1) * 0x9E3779B97F4A7C15)) + n), h the splitmix64 finaliser.  A wrapped integer sum: the
+ *   result does not depend on the order of the additions, so two calls on the same bytes always give the same cells.
+ * All four arrays live in DEVICE memory.  seg [n_seg] (segment addresses), bytes [n_seg] (byte counts >= 0), prefix [n_seg + 1]
+ *   (exclusive prefix of ceil(bytes / 256), prefix[0] = 0, prefix[n_seg] = total_chunks), out [n_seg] (the digests, 8-byte cells).
+ * Contract: read-only on the segments; the kernel trusts the table.  The caller guarantees that every segment is a device allocation
+ *   of at least bytes[i] bytes that stays alive and unwritten until the call's work has completed, and that prefix and total_chunks
+ *   follow from bytes as stated.  Any byte alignment of a segment is accepted: a lane reads 16 bytes at once when the segment's
+ *   base is 16-byte aligned, else (and in a segment's tail) byte by byte.  A segment of zero bytes has no chunk, its address is never
+ *   read and its digest is h(0).  The cells need no preparation: the call clears them itself (a memset node), accumulates with
+ *   64-bit integer atomics and finishes them with a second small kernel, all on `stream`; no allocation, no host synchronisation,
+ *   capturable.  No LDS, no barrier.  n_seg < 0, total_chunks < 0, n_seg == 0 with total_chunks > 0, a NULL array with n_seg > 0:
+ *   ST5_ERR_ARG, nothing enqueued.  n_seg == 0 and total_chunks == 0: nothing to do, ST5_OK. */
+int st5_state_digest(const void* const* seg, const int64_t* bytes, const int64_t* prefix, int32_t n_seg, int64_t total_chunks,
+                     uint64_t* out, void* stream);
+
 const char* st5_version(void);
 
 #ifdef __cplusplus

@@ -873,6 +873,20 @@ class FusedAdam:
             raise RuntimeError(f"guard block: the device's last step is {cells[GUARD_STEP]}, the host has counted {self.t}")
         return cells[GUARD_COUNT + (self.t & 1)]
 
+    def state_dict(self):
+        """The optimizer's part of a checkpoint (checkpoint.py): both moments as flat fp32 CPU tensors, the layout [(parameter name,
+        offset, numel)], t, lr, betas, eps, weight decay, clip norm and, with skip_nonfinite, the guard block's four cells.  Synchronous."""
+        from . import checkpoint
+        return checkpoint.optimizer_state_dict(self)
+
+    def load_state_dict(self, sd, params=None):
+        """Restore state_dict() into the existing buffers, matched by parameter name (ValueError naming a missing, extra or differently
+        sized parameter or a differing hyper-parameter); params {name: tensor} also restores the fp32 master.  Then rebuilds the bf16
+        image, the transposed copies and the fp8 images."""
+        from . import checkpoint
+        checkpoint.load_optimizer_state_dict(self, sd, params=params)
+        checkpoint.rebuild_images(self)
+
     def backward(self, loss):
         loss.backward()
 

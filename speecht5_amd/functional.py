@@ -284,6 +284,18 @@ def batch_load(src, dst, nbytes, prefix, n_leaves, total_chunks):
                                        hip.stream()), "st5_batch_load")
 
 
+def state_digest(seg, nbytes, prefix, n_seg, total_chunks, out):
+    """st5_state_digest on the current stream: out[i] = the 64-bit digest of the nbytes[i] bytes at address seg[i]
+    (csrc/state_digest_index.h has the definition, include/speecht5_hip.h the contract).  seg, nbytes and prefix (batch_load_plan of
+    the byte counts) are int64 device arrays, out an int64 device array of n_seg cells the call initialises itself."""
+    for t, n in ((seg, n_seg), (nbytes, n_seg), (prefix, n_seg + 1), (out, n_seg)):
+        if not (t.is_cuda and t.dtype == torch.int64 and t.is_contiguous() and t.numel() == n):
+            raise ValueError("st5_state_digest: the descriptor arrays and the cells are contiguous int64 device tensors of n_seg "
+                             "(prefix: n_seg + 1) entries")
+    hip.check(hip.lib().st5_state_digest(seg.data_ptr(), nbytes.data_ptr(), prefix.data_ptr(), n_seg, total_chunks, out.data_ptr(),
+                                         hip.stream()), "st5_state_digest")
+
+
 def stats_record(src, types, ring, counter, rows, n_cells):
     """st5_stats_record on the current stream: the n_cells scalars at the device addresses src[i], of type codes types[i], widened
     into row counter % rows of ring [rows, 1 + n_cells] behind the stamp `counter`; the counter then advances by one

@@ -56,6 +56,12 @@ so a captured step has the decision of the update it was captured with.  update(
 pulled, when the coming replay's update number lies on the other side of a threshold; recapture=True (needs prefetch_host=False)
 instead drops the graph there and runs prepare_graph() again -- that update() call executes two updates, as recording steps -- with
 source, statistics and optimizer carrying on; `captures` counts the graphs, `opt.t` the updates.
+
+Save and resume (checkpoint.py): state_dict() / load_state_dict() / snapshot() / save_checkpoint(path) -- everything that
+decides the next update's bits, as CPU data in a file that loads with weights_only=True; a resumed run continues bit for bit.  One rank;
+a replayed run saves with prefetch_host=False, after at least one replay since the capture; a load comes before prepare_graph().  The
+source's position is the caller's: after a load, set_source() gets an iterable positioned `batches_pulled` elements in.  A run that
+never calls these methods launches and allocates nothing for them.
 """
 import os
 
@@ -204,6 +210,11 @@ class PretrainUpdate:
         self.n = 0            # update counter (fairseq's num_updates)
         self.sg = None
         self.feed = None      # graph.BatchFeed once set_source() was called
+        # checkpoint.py: batches pulled before a loaded checkpoint was saved; the snapshot in flight; its device shadow (allocated by
+        # the first snapshot(), never freed while the update lives).  Nothing of it exists for a run that never saves.
+        self._pulled_base = 0
+        self._snapshot = None
+        self._shadow = None
         # Every update is enqueued on a stream of its own, never on the legacy NULL stream: on this runtime (ROCm 7.2) work issued
         # to the NULL stream from two host threads (the forward from the caller's thread, the backward from autograd's worker
         # thread) is NOT kept in issue order once another stream is busy -- measured: with the speech micro-batch on the NULL
@@ -620,3 +631,43 @@ class PretrainUpdate:
     def state(self):
         torch.cuda.synchronize(self.device)
         return self.opt.pflat.clone(), self.opt.m.clone(), self.opt.v.clone(), self.opt.t
+
+    # -- save and resume (checkpoint.py) ---------------------------------------------------------------------------
+    @property
+    def batches_pulled(self):
+        """Batches taken from the source since the start of the run, over every save and load."""
+        return self._pulled_base + (self.feed.pulls if self.feed is not None else 0)
+
+    def state_dict(self):
+        """Everything that decides the bits of the next update, as CPU data (checkpoint.py has the contents): {"model" (the
+        reference's key names), "optimizer", "extra_state", "digest"}.  Synchronous: waits for the update's stream; allocates no device
+        memory.  Legal where the host side stands where an eager loop has it after update n: after any eager update, and after a
+        replay of a graph built with prefetch_host=False once at least one replay has run since the capture (prepare_graph() stages
+        the first replay's batch and host draws).  Elsewhere it raises, naming the condition; so do snapshot() and save_checkpoint().
+        Statistics are not part of the state: take logging_outputs(wait=True) first."""
+        from . import checkpoint
+        return checkpoint.state_dict(self)
+
+    def load_state_dict(self, sd):
+        """Restore a state_dict() (checkpoint.load_checkpoint(path) returns one, digests checked) into this update, which must have
+        no captured graph: load before prepare_graph().  Parameters and moments are matched by name and written INTO the existing flat
+        buffers (every view the model holds stays valid); a missing, extra or differently shaped parameter and a saved hyper-parameter
+        that differs from the constructor's are refused with a ValueError naming it.  The bf16 image, the transposed copies and the
+        fp8 images are rebuilt, and the rebuilt bf16 image must have the saved digest.  The source is the caller's: after a load give
+        set_source() an iterable positioned `batches_pulled` (sd["extra_state"]["batches_pulled"]) elements in."""
+        from . import checkpoint
+        checkpoint.load_state_dict(self, sd)
+
+    def snapshot(self):
+        """state_dict() without stopping training: behind the newest update, on the update's stream, one st5_batch_load copies every
+        device segment of the state into a device shadow and one st5_state_digest digests the shadow; a side stream copies shadow and
+        digests into pinned memory.  Returns a handle at once -- done() never waits, result() waits for the copy, checks every host
+        segment against the device's digest (ValueError naming the segment) and returns the dictionary.  The next update may run as
+        soon as this returns.  One snapshot may be in flight: a second call before the first handle's result() raises."""
+        from . import checkpoint
+        return checkpoint.snapshot(self)
+
+    def save_checkpoint(self, path):
+        """snapshot().result() written to `path` through a temporary file in the same directory, fsync and os.replace."""
+        from . import checkpoint
+        checkpoint.save_checkpoint(self, path)
