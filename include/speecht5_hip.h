@@ -921,6 +921,49 @@ int st5_tts_step_tail_dev(const float* y, int64_t y_ld, int32_t B, int32_t r, in
                           void* stream);
 int st5_tts_pe_add_step(const void* x, int64_t x_ld, const float* table, int32_t table_rows, const float* alpha, const int32_t* step,
                         void* y, int64_t y_ld, int32_t B, int32_t C, int dtype, void* stream);
+/* Decode kernels with ONE POSITION PER ROW (the synthesis stream, speecht5_amd/tts_stream.py: a fixed set of rows whose finished rows
+ * are handed to waiting utterances).  pos int32 [rows] in device memory = steps completed by the current occupant of each row.  Every
+ * value read from pos is clamped or range-checked before it enters an address: a wrong pos gives a wrong row, never a store out of
+ * bounds.  Each form runs the kernels of its scalar form with the position looked up per row (once per workgroup, wave-uniform, or in
+ * the epilogue behind the product), so row b's bits are those of the scalar form run at the same row count with the step pos[b].
+ * st5_gemm_skinny_rows: st5_gemm_skinny whose row m lands at out + clamp(step_rows[row0 + m], 0, step_cap - 1) * step_stride +
+ *   m * out_ld (row chunks of 32 index step_rows through row0).  step_rows is required.
+ * st5_lm_decode_attn_rows: st5_lm_decode_attn_dev with t_b = clamp(pos[b] + t_add, 1, t_max) per row; grid and ws as for t_max (a row's
+ *   partial states sit at the grid's split stride in ws, so rows with different split counts never share a cell).
+ * st5_decode_cross_attn_rows: st5_decode_cross_attn_step whose record column of row b is clamp(pos[b], 0, cap - 1).  S is the buffers'
+ *   capacity; a row's own encoder length is expressed by kpm.
+ * st5_tts_pe_add_rows: st5_tts_pe_add_step with the positional row table[clamp(pos[b], 0, table_rows - 1)] per row.
+ * st5_tts_step_tail_rows: a row with done[b] == 0 and pos[b] in [0, cap) runs st5_tts_step_tail's row at idx_b = pos[b] + 1 (frames,
+ *   probabilities, next, the stop test against minlen[b] / maxlen[b]: done[b] = 1, steps[b] = idx_b) and pos[b] = idx_b; any other row
+ *   writes nothing and does not advance.  *active = the rows that ran this step and did not stop in it.  tick (int32 [1], or NULL):
+ *   *tick = (*tick + 1) mod table_rows (a value outside [0, table_rows) counts as -1), and with n_seeds > 0 seed_slots[k] =
+ *   seed_table[*tick * n_seeds + k]: the next tick's pre-net dropout seeds.  The host refills the table between groups of ticks, so a
+ *   stream of any length draws fresh seeds in tick order.  B <= 4096.
+ * st5_tts_rows_admit: one launch for the n_admit rows handed to new utterances; desc int32 [n_admit][4] in device memory =
+ *   {row b, encoder length T_b, minlen, maxlen}, rows distinct.  Per entry: pos[b] = done[b] = steps[b] = 0, minlen[b], maxlen[b],
+ *   next[b][:odim] = 0, kpm[b][j] = (j >= clamp(T_b, 0, S)) for all j < S, and with spk_src (compute dtype [n_admit][spk_src_ld])
+ *   spk_dst[b * spk_dst_ld + d] = spk_src[i * spk_src_ld + d] for d < D (the normalised speaker embedding into its columns of the
+ *   speaker-integration input; spk_dst points at the first such column of row 0).  An entry whose row is outside [0, rows) admits
+ *   nothing.  n_admit == 0: nothing is launched. */
+int st5_gemm_skinny_rows(const void* x, int64_t x_ld, const void* w, int64_t w_ld, const float* bias, const void* res, int64_t res_ld,
+                         void* out, int64_t out_ld, int32_t M, int32_t N, int32_t K, int32_t act, float dropout_p, uint64_t seed,
+                         int32_t row0, int32_t out_f32, const int32_t* step_rows, int64_t step_stride, int32_t step_cap, float* ws,
+                         int dtype, void* stream);
+int st5_lm_decode_attn_rows(const void* q, int64_t q_ld, const void* kv, int32_t rows_cap, int32_t Tmax, const int32_t* anc, int64_t anc_ld,
+                            int32_t rows, const int32_t* pos, int32_t t_add, int32_t t_max, int32_t H, int32_t head_dim, void* ctx,
+                            int64_t ctx_ld, float* ws, int dtype, void* stream);
+int st5_decode_cross_attn_rows(const void* q, int64_t q_ld, const void* kv, int64_t kv_ld, int64_t k_off, const uint8_t* kpm, int32_t B,
+                               int32_t S, int32_t H, int32_t head_dim, void* ctx, int64_t ctx_ld, float* probs, int64_t p_row,
+                               int64_t p_head, int64_t p_col, const int32_t* pos, int32_t cap, float* ws, int dtype, void* stream);
+int st5_tts_pe_add_rows(const void* x, int64_t x_ld, const float* table, int32_t table_rows, const float* alpha, const int32_t* pos,
+                        void* y, int64_t y_ld, int32_t B, int32_t C, int dtype, void* stream);
+int st5_tts_step_tail_rows(const float* y, int64_t y_ld, int32_t B, int32_t r, int32_t odim, const int32_t* minlen, const int32_t* maxlen,
+                           int32_t* done, int32_t* steps, int32_t* pos, int32_t cap, float threshold, float* mel, float* probs, void* next,
+                           int64_t next_ld, int32_t* active, int32_t* tick, const uint64_t* seed_table, int32_t table_rows,
+                           uint64_t* seed_slots, int32_t n_seeds, int dtype, void* stream);
+int st5_tts_rows_admit(const int32_t* desc, int32_t n_admit, int32_t rows, int32_t* pos, int32_t* done, int32_t* steps, int32_t* minlen,
+                       int32_t* maxlen, void* next, int64_t next_ld, int32_t odim, uint8_t* kpm, int32_t S, const void* spk_src,
+                       int64_t spk_src_ld, void* spk_dst, int64_t spk_dst_ld, int32_t D, int dtype, void* stream);
 
 /* ---- validation UER / WER of the ASR criterion (speech_to_text_loss.py:232-297), csrc/asr_metrics.hip ----
  * All arrays on the device; rows are int32 [B, L] with int32 lengths [B] unless said otherwise.  Every length is clamped to its row

@@ -15,7 +15,8 @@
 //     32 FMAs per weight element pair keep the VALU below the weight stream's cost at these sizes.
 // Epilogue (fused into the first kernel when nslices == 1): + bias, activation, dropout (seed by value or seed slot, element index
 // (row0 + m) * N + n as st5_gemm counts it), + residual, output in the compute dtype or fp32, and an optional DEVICE-side output
-// offset out + clamp(*step, 0, step_cap - 1) * step_stride (the K|V projection of a decode step writes slot `step` of the cache).
+// offset out + clamp(*step, 0, step_cap - 1) * step_stride (the K|V projection of a decode step writes slot `step` of the cache), or
+// with st5_gemm_skinny_rows one slot per output row, step_rows[row0 + m] (the synthesis stream: every row at its own position).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <stdint.h>
@@ -49,13 +50,20 @@ struct SkEpi {
   int64_t res_ld;
   void* out;
   int64_t out_ld;
-  const int32_t* step;      // nullptr: no offset
+  const int32_t* step;      // nullptr: no offset; with step_rows != 0 an array indexed by the output row (row0 + m)
   int64_t step_stride;
   int32_t step_cap;
   int32_t act, out_f32, row0;
+  int32_t step_rows;
   float dropout_p;
   unsigned long long seed;
 };
+
+// slot of output row m: the launch's one counter, or with step_rows the row's own (clamped either way)
+__device__ __forceinline__ int sk_slot(const SkEpi& ep, int m) {
+  int s0 = ep.step_rows ? ep.step[ep.row0 + m] : *ep.step;
+  return s0 < 0 ? 0 : (s0 >= ep.step_cap ? ep.step_cap - 1 : s0);   // no address depends on an unchecked value
+}
 
 template <typename T>
 __device__ __forceinline__ void sk_epilogue(const SkEpi& ep, int m, int n, int N, float s) {
@@ -68,11 +76,7 @@ __device__ __forceinline__ void sk_epilogue(const SkEpi& ep, int m, int n, int N
   }
   if (ep.res) v += Elem<T>::to_f(static_cast<const T*>(ep.res)[(int64_t)m * ep.res_ld + n]);
   int64_t off = (int64_t)m * ep.out_ld + n;
-  if (ep.step) {
-    int s0 = *ep.step;
-    s0 = s0 < 0 ? 0 : (s0 >= ep.step_cap ? ep.step_cap - 1 : s0);   // no address depends on an unchecked value
-    off += (int64_t)s0 * ep.step_stride;
-  }
+  if (ep.step) off += (int64_t)sk_slot(ep, m) * ep.step_stride;
   if (ep.out_f32) static_cast<float*>(ep.out)[off] = v;
   else static_cast<T*>(ep.out)[off] = Elem<T>::from_f(v);
 }
@@ -173,10 +177,10 @@ extern "C" int64_t st5_gemm_skinny_ws_bytes(int32_t N, int32_t K) {
   return pl.nslices > 1 ? (int64_t)pl.nslices * SK_MAX_M * N * 4 : 0;
 }
 
-extern "C" int st5_gemm_skinny(const void* x, int64_t x_ld, const void* w, int64_t w_ld, const float* bias, const void* res, int64_t res_ld,
-                               void* out, int64_t out_ld, int32_t M, int32_t N, int32_t K, int32_t act, float dropout_p, uint64_t seed,
-                               int32_t row0, int32_t out_f32, const int32_t* step, int64_t step_stride, int32_t step_cap, float* ws,
-                               int dtype, void* stream) {
+namespace {
+int skinny_entry(const void* x, int64_t x_ld, const void* w, int64_t w_ld, const float* bias, const void* res, int64_t res_ld, void* out,
+                 int64_t out_ld, int32_t M, int32_t N, int32_t K, int32_t act, float dropout_p, uint64_t seed, int32_t row0, int32_t out_f32,
+                 const int32_t* step, int32_t step_rows, int64_t step_stride, int32_t step_cap, float* ws, int dtype, void* stream) {
   if (!x || !w || !out) return ST5_ERR_ARG;
   if (dtype != ST5_F32 && dtype != ST5_BF16) return ST5_ERR_ARG;
   if (M < 1 || M > SK_MAX_M || N <= 0 || N > 65535 * SK_ROWS || K <= 0 || row0 < 0) return ST5_ERR_ARG;
@@ -189,9 +193,29 @@ extern "C" int st5_gemm_skinny(const void* x, int64_t x_ld, const void* w, int64
   if (!aligned16(x) || !aligned16(w) || x_ld % vec || w_ld % vec || K % vec) return ST5_ERR_ALIGN;
   SkEpi ep;
   ep.bias = bias; ep.res = res; ep.res_ld = res_ld; ep.out = out; ep.out_ld = out_ld;
-  ep.step = step; ep.step_stride = step_stride; ep.step_cap = step_cap;
+  ep.step = step; ep.step_rows = step_rows; ep.step_stride = step_stride; ep.step_cap = step_cap;
   ep.act = act; ep.out_f32 = out_f32; ep.row0 = row0; ep.dropout_p = dropout_p; ep.seed = seed;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (dtype == ST5_F32) return launch_skinny<float>(x, x_ld, w, w_ld, M, N, K, ws, ep, st);
   return launch_skinny<bf16_t>(x, x_ld, w, w_ld, M, N, K, ws, ep, st);
+}
+}  // namespace
+
+extern "C" int st5_gemm_skinny(const void* x, int64_t x_ld, const void* w, int64_t w_ld, const float* bias, const void* res, int64_t res_ld,
+                               void* out, int64_t out_ld, int32_t M, int32_t N, int32_t K, int32_t act, float dropout_p, uint64_t seed,
+                               int32_t row0, int32_t out_f32, const int32_t* step, int64_t step_stride, int32_t step_cap, float* ws,
+                               int dtype, void* stream) {
+  return skinny_entry(x, x_ld, w, w_ld, bias, res, res_ld, out, out_ld, M, N, K, act, dropout_p, seed, row0, out_f32, step, 0, step_stride,
+                      step_cap, ws, dtype, stream);
+}
+
+// The per-row form: row m of the launch lands in slot clamp(step_rows[row0 + m], 0, step_cap - 1).  The same kernels; only the
+// epilogue's slot lookup differs, so a row's bits are those of the scalar form at that row's slot.
+extern "C" int st5_gemm_skinny_rows(const void* x, int64_t x_ld, const void* w, int64_t w_ld, const float* bias, const void* res,
+                                    int64_t res_ld, void* out, int64_t out_ld, int32_t M, int32_t N, int32_t K, int32_t act,
+                                    float dropout_p, uint64_t seed, int32_t row0, int32_t out_f32, const int32_t* step_rows,
+                                    int64_t step_stride, int32_t step_cap, float* ws, int dtype, void* stream) {
+  if (!step_rows) return ST5_ERR_ARG;
+  return skinny_entry(x, x_ld, w, w_ld, bias, res, res_ld, out, out_ld, M, N, K, act, dropout_p, seed, row0, out_f32, step_rows, 1,
+                      step_stride, step_cap, ws, dtype, stream);
 }

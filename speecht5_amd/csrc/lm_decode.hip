@@ -54,8 +54,8 @@ template <typename T, int HD>
 __device__ __forceinline__ void lm_decode_attn_body(
     const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int Tmax, int rows_cap, const int32_t* __restrict__ anc,
     int64_t anc_ld, int t, int H, int chunk, float scale, T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ ws, const int r,
-    const int split, const int nsplit) {
-  constexpr int EPL = HD / 4;                 // elements per lane: 20 (hd 80) or 16 (hd 64)
+    const int split, const int nsplit, const int ws_ld) {   // ws_ld: split states per row in ws (nsplit, or the grid's with per-row t)
+  constexpr int EPL = HD / 4;                // elements per lane: 20 (hd 80) or 16 (hd 64)
   const int C = H * HD;
   const int tid = threadIdx.x, g = tid >> 2, sub = tid & 3;
   const int P = LM_GROUPS / H;                // positions in flight per pass
@@ -136,7 +136,7 @@ __device__ __forceinline__ void lm_decode_attn_body(
     if (ws == nullptr) {
       ctx[(int64_t)r * ctx_ld + c] = Elem<T>::from_f(A / L);
     } else {
-      float* w = ws + ((int64_t)r * nsplit + split) * (2 * H + C);
+      float* w = ws + ((int64_t)r * ws_ld + split) * (2 * H + C);
       if (c % HD == 0) { w[hh] = M; w[H + hh] = L; }
       w[2 * H + c] = A;
     }
@@ -148,7 +148,7 @@ __global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_kernel(
     const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int Tmax, int rows_cap, const int32_t* __restrict__ anc,
     int64_t anc_ld, int t, int H, int chunk, float scale, T* __restrict__ ctx, int64_t ctx_ld, float* __restrict__ ws) {
   lm_decode_attn_body<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, t, H, chunk, scale, ctx, ctx_ld, ws, blockIdx.y, blockIdx.x,
-                             gridDim.x);
+                             gridDim.x, gridDim.x);
 }
 
 // The same launch with t read from device memory (a decode step replayed from a graph): t = clamp(*step + t_add, 1, t_max); the grid is
@@ -168,7 +168,22 @@ __global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_dev_kernel(
   if ((int)blockIdx.x >= nsplit) return;
   const int chunk = (t + nsplit - 1) / nsplit;
   lm_decode_attn_body<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, t, H, chunk, scale, ctx, ctx_ld, nsplit > 1 ? ws : nullptr,
-                             blockIdx.y, blockIdx.x, nsplit);
+                             blockIdx.y, blockIdx.x, nsplit, nsplit);
+}
+// The same with one position per row: t_b = clamp(pos[b] + t_add, 1, t_max), read once per workgroup through the scalar cache
+// (blockIdx.y is uniform, so is t).  Rows differ in their split count, so a row's states sit at the GRID's stride in ws (row b
+// owns ws[b * gridDim.x ...]): no two rows' regions overlap whatever their positions.  Where the states sit does not enter the bits.
+template <typename T, int HD>
+__global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_rows_kernel(
+    const T* __restrict__ q, int64_t q_ld, const T* __restrict__ kv, int Tmax, int rows_cap, const int32_t* __restrict__ anc,
+    int64_t anc_ld, const int32_t* __restrict__ pos, int t_add, int t_max, int H, float scale, T* __restrict__ ctx, int64_t ctx_ld,
+    float* __restrict__ ws) {
+  const int t = lm_dev_t(pos + blockIdx.y, t_add, t_max);
+  const int nsplit = lm_splits((int)gridDim.y, t);
+  if ((int)blockIdx.x >= nsplit) return;
+  const int chunk = (t + nsplit - 1) / nsplit;
+  lm_decode_attn_body<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, t, H, chunk, scale, ctx, ctx_ld, nsplit > 1 ? ws : nullptr,
+                             blockIdx.y, blockIdx.x, nsplit, gridDim.x);
 }
 
 // grid (C / 64, rows), one thread per output column: ctx[r, c] = sum_s e^(M_s - M) A_s / sum_s e^(M_s - M) L_s over the nsplit
@@ -176,13 +191,13 @@ __global__ void __launch_bounds__(LM_THREADS) lm_decode_attn_dev_kernel(
 // row that walked its columns in turn took ~100 us per launch at 5 rows.)
 template <typename T>
 __device__ __forceinline__ void lm_decode_combine_body(const float* __restrict__ ws, int nsplit, int H, int HD, T* __restrict__ ctx,
-                                                       int64_t ctx_ld) {
+                                                       int64_t ctx_ld, int ws_ld) {
   const int r = blockIdx.y, C = H * HD;
   const int c = blockIdx.x * 64 + threadIdx.x;
   if (c >= C) return;
   const int h = c / HD;
   const int64_t stride = 2 * H + C;
-  const float* base = ws + (int64_t)r * nsplit * stride;
+  const float* base = ws + (int64_t)r * ws_ld * stride;
   float M = -INFINITY;
   bool nan = false;
 #pragma unroll 8
@@ -204,7 +219,7 @@ __device__ __forceinline__ void lm_decode_combine_body(const float* __restrict__
 template <typename T>
 __global__ void __launch_bounds__(64) lm_decode_combine_kernel(const float* __restrict__ ws, int nsplit, int H, int HD,
                                                               T* __restrict__ ctx, int64_t ctx_ld) {
-  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld);
+  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld, nsplit);
 }
 // device-t form: nothing to combine while the step's key range is one workgroup's (the attention kernel wrote ctx itself)
 template <typename T>
@@ -212,7 +227,16 @@ __global__ void __launch_bounds__(64) lm_decode_combine_dev_kernel(const float* 
                                                                   int t_max, int H, int HD, T* __restrict__ ctx, int64_t ctx_ld) {
   const int nsplit = lm_splits((int)gridDim.y, lm_dev_t(step, t_add, t_max));
   if (nsplit <= 1) return;
-  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld);
+  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld, nsplit);
+}
+// per-row form: row r's split count follows its own position; its states sit at the grid's stride (ws_ld = the launch's nsplit)
+template <typename T>
+__global__ void __launch_bounds__(64) lm_decode_combine_rows_kernel(const float* __restrict__ ws, const int32_t* __restrict__ pos, int t_add,
+                                                                   int t_max, int H, int HD, T* __restrict__ ctx, int64_t ctx_ld,
+                                                                   int ws_ld) {
+  const int nsplit = lm_splits((int)gridDim.y, lm_dev_t(pos + blockIdx.y, t_add, t_max));
+  if (nsplit <= 1) return;
+  lm_decode_combine_body<T>(ws, nsplit, H, HD, ctx, ctx_ld, ws_ld);
 }
 
 // anc_new[r, j] = anc[order[r], j] for j < t, = r for t <= j < Tmax (the row's own slots from position t on); an order entry
@@ -290,9 +314,44 @@ int launch_attn_dev(const void* q, int64_t q_ld, const void* kv, int Tmax, int r
   return ST5_OK;
 }
 
+template <typename T, int HD>
+int launch_attn_rows(const void* q, int64_t q_ld, const void* kv, int Tmax, int rows_cap, const int32_t* anc, int64_t anc_ld, int rows,
+                     const int32_t* pos, int t_add, int t_max, int H, void* ctx, int64_t ctx_ld, float* ws, hipStream_t st) {
+  const int nsplit = lm_splits(rows, t_max);
+  const float scale = 1.0f / sqrtf((float)HD);
+  hipLaunchKernelGGL((lm_decode_attn_rows_kernel<T, HD>), dim3(nsplit, rows), dim3(LM_THREADS), 0, st, static_cast<const T*>(q), q_ld,
+                     static_cast<const T*>(kv), Tmax, rows_cap, anc, anc_ld, pos, t_add, t_max, H, scale, static_cast<T*>(ctx), ctx_ld, ws);
+  if (hipGetLastError() != hipSuccess) return ST5_ERR_LAUNCH;
+  if (nsplit > 1) {
+    hipLaunchKernelGGL((lm_decode_combine_rows_kernel<T>), dim3((H * HD + 63) / 64, rows), dim3(64), 0, st, ws, pos, t_add, t_max, H, HD,
+                       static_cast<T*>(ctx), ctx_ld, nsplit);
+    if (hipGetLastError() != hipSuccess) return ST5_ERR_LAUNCH;
+  }
+  return ST5_OK;
+}
+
 bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
 }  // namespace
+
+extern "C" int st5_lm_decode_attn_rows(const void* q, int64_t q_ld, const void* kv, int32_t rows_cap, int32_t Tmax, const int32_t* anc,
+                                       int64_t anc_ld, int32_t rows, const int32_t* pos, int32_t t_add, int32_t t_max, int32_t H,
+                                       int32_t head_dim, void* ctx, int64_t ctx_ld, float* ws, int dtype, void* stream) {
+  if (!q || !kv || !anc || !ctx || !pos) return ST5_ERR_ARG;
+  if (head_dim != 64 && head_dim != 80) return ST5_ERR_ARG;
+  if (dtype != ST5_F32 && dtype != ST5_BF16) return ST5_ERR_ARG;
+  if (rows <= 0 || rows > rows_cap || rows > 65535 || t_max <= 0 || t_max > Tmax || H <= 0 || H > LM_GROUPS) return ST5_ERR_ARG;
+  const int64_t C = (int64_t)H * head_dim;
+  if (q_ld < C || ctx_ld < C || anc_ld < t_max) return ST5_ERR_ARG;
+  if (lm_splits(rows, t_max) > 1 && !ws) return ST5_ERR_ARG;
+  const int64_t vec = dtype == ST5_F32 ? 4 : 8;
+  if (!aligned16(q) || !aligned16(kv) || q_ld % vec || (ws && !aligned16(ws))) return ST5_ERR_ALIGN;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+#define ST5_LM_ROWS(T, HD) launch_attn_rows<T, HD>(q, q_ld, kv, Tmax, rows_cap, anc, anc_ld, rows, pos, t_add, t_max, H, ctx, ctx_ld, ws, st)
+  if (dtype == ST5_F32) return head_dim == 80 ? ST5_LM_ROWS(float, 80) : ST5_LM_ROWS(float, 64);
+  return head_dim == 80 ? ST5_LM_ROWS(bf16_t, 80) : ST5_LM_ROWS(bf16_t, 64);
+#undef ST5_LM_ROWS
+}
 
 extern "C" int64_t st5_lm_decode_attn_ws_bytes(int32_t rows, int32_t t, int32_t H, int32_t head_dim) {
   if (rows <= 0 || t <= 0 || H <= 0 || head_dim <= 0) return 0;

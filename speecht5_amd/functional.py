@@ -3650,6 +3650,115 @@ def tts_pe_add_step(x, table, alpha, step, y):
     return y
 
 
+# -------------------------------------------------------------------------------------------------
+# The same launches with ONE POSITION PER ROW (`pos` int32 [rows]: steps completed by each row's current occupant): the step of a
+# synthesis stream (tts_stream.py).  Row b's bits are those of the scalar forms above at step pos[b].
+# -------------------------------------------------------------------------------------------------
+def linear_skinny_rows(x, w, bias=None, *, out, step_rows, step_stride, step_cap, out_ld, act=ACT_NONE, residual=None, dropout_p=0.0,
+                       seed=0, out_f32=False, ws=None):
+    """linear_skinny whose row m lands in slot clamp(step_rows[m], 0, step_cap - 1) of `out` (step_rows int32 [M])."""
+    M, K = x.shape
+    N = w.shape[0]
+    assert x.stride(1) == 1 and w.stride(1) == 1 and w.shape[1] == K and w.dtype == x.dtype
+    assert out.dtype == (torch.float32 if out_f32 else x.dtype)
+    assert step_rows.dtype == torch.int32 and step_rows.is_contiguous() and step_rows.numel() >= M
+    if ws is None:
+        ws = gemm_skinny_ws(N, K, x.device)
+    L = hip.lib()
+    st = hip.stream()
+    es, eo = x.element_size(), out.element_size()
+    for m0 in range(0, M, SKINNY_MAX_M):
+        m = min(SKINNY_MAX_M, M - m0)
+        hip.check(L.st5_gemm_skinny_rows(x.data_ptr() + m0 * x.stride(0) * es, x.stride(0), w.data_ptr(), w.stride(0), hip.ptr(bias),
+                                         0 if residual is None else residual.data_ptr() + m0 * residual.stride(0) * es,
+                                         0 if residual is None else residual.stride(0), out.data_ptr() + m0 * out_ld * eo, out_ld, m, N,
+                                         K, int(act), float(dropout_p), int(seed), m0, int(bool(out_f32)), step_rows.data_ptr(),
+                                         int(step_stride), int(step_cap), hip.ptr(ws), _dt(x), st), "st5_gemm_skinny_rows")
+    return out
+
+
+def lm_decode_attn_rows(q, kv, anc, pos, t_add, t_max, H, hd, ctx, ws):
+    """lm_decode_attn_dev with t_b = clamp(pos[b] + t_add, 1, t_max) per row."""
+    rows = q.shape[0]
+    C = H * hd
+    assert kv.shape[2] == 2 * C and kv.is_contiguous() and anc.dtype == torch.int32 and anc.stride(1) == 1 and q.stride(1) == 1
+    assert kv.dtype == q.dtype == ctx.dtype and ctx.stride(1) == 1 and pos.dtype == torch.int32 and pos.numel() >= rows
+    hip.check(hip.lib().st5_lm_decode_attn_rows(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.shape[0], kv.shape[1], anc.data_ptr(),
+                                                anc.stride(0), rows, pos.data_ptr(), int(t_add), int(t_max), H, hd, ctx.data_ptr(),
+                                                ctx.stride(0), hip.ptr(ws), _dt(q), hip.stream()), "st5_lm_decode_attn_rows")
+    return ctx
+
+
+def decode_cross_attn_rows(q, kv, k_off, S, H, hd, ctx, pos, cap, kpm=None, rec=None, ws=None):
+    """decode_cross_attn_step whose record column of row b is clamp(pos[b], 0, cap - 1)."""
+    B = q.shape[0]
+    assert kv.stride(1) == 1 and q.stride(1) == 1 and kv.dtype == q.dtype == ctx.dtype and kv.shape[0] == B * S
+    assert pos.dtype == torch.int32 and pos.numel() >= B
+    p_row = p_head = p_col = 0
+    if rec is not None:
+        assert rec.dtype == torch.float32 and rec.shape == (B, H, cap, S) and rec.stride(3) == 1
+        p_row, p_head, p_col = rec.stride(0), rec.stride(1), rec.stride(2)
+    hip.check(hip.lib().st5_decode_cross_attn_rows(q.data_ptr(), q.stride(0), kv.data_ptr(), kv.stride(0), int(k_off), hip.ptr(kpm), B, S,
+                                                   H, hd, ctx.data_ptr(), ctx.stride(0), hip.ptr(rec), p_row, p_head, p_col,
+                                                   pos.data_ptr(), int(cap), hip.ptr(ws), _dt(q), hip.stream()),
+              "st5_decode_cross_attn_rows")
+    return ctx
+
+
+def tts_pe_add_rows(x, table, alpha, pos, y):
+    """tts_pe_add_step with the positional row table[clamp(pos[b], 0, rows - 1)] per row."""
+    B, C = x.shape
+    assert table.dtype == torch.float32 and table.is_contiguous() and table.shape[1] == C and x.stride(1) == 1 and y.stride(1) == 1
+    assert pos.dtype == torch.int32 and pos.numel() >= B
+    hip.check(hip.lib().st5_tts_pe_add_rows(x.data_ptr(), x.stride(0), table.data_ptr(), table.shape[0], alpha.data_ptr(),
+                                            pos.data_ptr(), y.data_ptr(), y.stride(0), B, C, _dt(x), hip.stream()),
+              "st5_tts_pe_add_rows")
+    return y
+
+
+def tts_step_tail_rows(y, r, odim, minlen, maxlen, done, steps, pos, threshold, mel, probs, nxt, active, tick=None, seed_table=None,
+                       seed_slots=None):
+    """The step tail with one position per row: live rows (done == 0, pos in [0, cap)) write at idx_b = pos[b] + 1 and advance.
+    tick int32 [1]: advanced modulo the seed table's rows; seed_table int64 [R, n] / seed_slots int64 [n]: the next tick's seeds."""
+    B = y.shape[0]
+    cap = probs.shape[1] // r
+    assert y.dtype == torch.float32 and y.stride(1) == 1 and nxt.stride(1) == 1
+    assert mel.is_contiguous() and probs.is_contiguous() and mel.shape == (B, cap * r, odim) and probs.shape == (B, cap * r)
+    for t in (minlen, maxlen, done, steps, pos, active):
+        assert t.dtype == torch.int32 and t.is_contiguous()
+    n, R = 0, 1
+    if seed_table is not None:
+        n, R = seed_slots.numel(), seed_table.shape[0]
+        assert seed_table.dtype == seed_slots.dtype == torch.int64 and seed_table.is_contiguous() and seed_table.shape == (R, n)
+        assert tick is not None
+    hip.check(hip.lib().st5_tts_step_tail_rows(y.data_ptr(), y.stride(0), B, r, odim, minlen.data_ptr(), maxlen.data_ptr(),
+                                               done.data_ptr(), steps.data_ptr(), pos.data_ptr(), cap, float(threshold), mel.data_ptr(),
+                                               probs.data_ptr(), nxt.data_ptr(), nxt.stride(0), active.data_ptr(), hip.ptr(tick),
+                                               hip.ptr(seed_table), R, hip.ptr(seed_slots), n, _dt(nxt), hip.stream()),
+              "st5_tts_step_tail_rows")
+
+
+def tts_rows_admit(desc, n_admit, pos, done, steps, minlen, maxlen, nxt, kpm, spk_src=None, spk_dst=None):
+    """Hands the rows named by desc (int32 [>= n_admit, 4] on the device: row, encoder length, minlen, maxlen) to new utterances: state
+    reset, next input zeroed, key-padding bytes over the whole capacity, and spk_src [>= n_admit, D] rows copied into spk_dst [rows, D]
+    (a column view of the speaker-integration input)."""
+    rows, S = kpm.shape
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.shape[1] == 4 and desc.shape[0] >= n_admit
+    assert kpm.dtype == torch.uint8 and kpm.is_contiguous() and nxt.stride(1) == 1 and nxt.shape[0] == rows
+    for t in (pos, done, steps, minlen, maxlen):
+        assert t.dtype == torch.int32 and t.is_contiguous() and t.numel() == rows
+    D = 0
+    if spk_src is not None:
+        D = spk_dst.shape[1]
+        assert spk_src.dtype == spk_dst.dtype == nxt.dtype and spk_src.stride(1) == 1 and spk_dst.stride(1) == 1
+        assert spk_src.shape[1] == D and spk_src.shape[0] >= n_admit and spk_dst.shape[0] == rows
+    hip.check(hip.lib().st5_tts_rows_admit(desc.data_ptr(), int(n_admit), rows, pos.data_ptr(), done.data_ptr(), steps.data_ptr(),
+                                           minlen.data_ptr(), maxlen.data_ptr(), nxt.data_ptr(), nxt.stride(0), nxt.shape[1],
+                                           kpm.data_ptr(), S, hip.ptr(spk_src), 0 if spk_src is None else spk_src.stride(0),
+                                           hip.ptr(spk_dst), 0 if spk_dst is None else spk_dst.stride(0), D, _dt(nxt), hip.stream()),
+              "st5_tts_rows_admit")
+
+
 def layer_norm_into(x, weight, bias, eps, y, stats):
     """y = LayerNorm(x) into the caller's buffer (inference; stats: fp32 [2, rows] scratch for the kernel's mean / rstd)."""
     rows, cols = x.shape

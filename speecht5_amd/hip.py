@@ -247,6 +247,21 @@ _SIGS = {
                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_int, c_void_p]),
     "st5_tts_pe_add_step": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int,
                                     c_void_p]),
+    "st5_gemm_skinny_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32,
+                                     c_int32, c_int32, c_float, c_uint64, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int,
+                                     c_void_p]),
+    "st5_lm_decode_attn_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_int32, c_void_p, c_int64, c_int32, c_void_p, c_int32, c_int32,
+                                        c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int, c_void_p]),
+    "st5_decode_cross_attn_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int32, c_int32, c_int32, c_int32,
+                                           c_void_p, c_int64, c_void_p, c_int64, c_int64, c_int64, c_void_p, c_int32, c_void_p, c_int,
+                                           c_void_p]),
+    "st5_tts_pe_add_rows": (c_int, [c_void_p, c_int64, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int,
+                                    c_void_p]),
+    "st5_tts_step_tail_rows": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p, c_int32, c_void_p,
+                                       c_int32, c_int, c_void_p]),
+    "st5_tts_rows_admit": (c_int, [c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int32,
+                                   c_void_p, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int, c_void_p]),
     "st5_beam_cross_attn_ws_bytes": (c_int64, [c_int32, c_int32, c_int32, c_int32]),
     "st5_beam_cross_attn": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32,
                                     c_int32, c_int32, c_void_p, c_int64, c_void_p, c_int64, c_int64, c_void_p, c_int, c_void_p]),

@@ -717,6 +717,64 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
             out.append((wavs[b], mels[b], prob_rec[b, :lengths[b]].clone(), attn))
         return out
 
+    # ---- streaming synthesis: a fixed set of decoder rows, finished rows refilled in the decode loop (speecht5_amd/tts_stream.py) ----
+    def generate_speech_stream(self, requests, *, rows, max_src_len, decode="graph", need_attn=False, **kwargs):
+        """generate_speech for utterances as they arrive.  requests: an iterable of (key, src_tokens [n] or source waveform [n],
+        spkembs [D]); yields (key, mel, probs, attn), each what generate_speech_batch returns for a row, in completion order (rows
+        that finish at the same poll in row order).  `rows` decoder rows are stepped by one program ("device": kernel by kernel,
+        "graph": captured once and replayed); every TTS_POLL_STEPS steps the finished rows are copied out and handed to the next
+        waiting utterances, which were encoded alone, as generate_speech encodes them.  max_src_len: the most encoder positions an
+        utterance may have (a longer one is refused by key when the stream ends; the others complete).  `threshold` and the length
+        ratios are read per row by tts_row_limits."""
+        from . import tts_stream
+        post = self.speech_decoder_postnet
+
+        def finish(raw):
+            out = []
+            for key, mel, probs, attn in raw:
+                mel = mel.unsqueeze(0)
+                if post.postnet is not None:
+                    mel = post.postnet(Fn.as_compute(mel.contiguous()))
+                out.append((key, mel.squeeze(0), probs, attn))
+            return out
+        return tts_stream.run_stream(self, requests, rows, max_src_len, decode, need_attn, finish, **kwargs)
+
+    def synthesize_stream(self, requests, *, rows, max_src_len, vocoder=None, decode="graph", max_frames=None, **kwargs):
+        """generate_speech_stream through the mel post-net and the HiFi-GAN `vocoder`: yields (key, wav fp32 [hop * L] or None without
+        a vocoder, mel [L, odim], probs [L]).  The rows that completed at one poll go together through the packed post-net / vocoder
+        path of synthesize_batch."""
+        from . import ragged, tts_stream
+        post = self.speech_decoder_postnet
+
+        def finish(raw):
+            if not raw:
+                return []
+            odim = raw[0][1].shape[1]
+            lengths = [m.shape[0] for _, m, _, _ in raw]
+            starts = [sum(lengths[:i]) for i in range(len(raw))]
+            src = torch.cat([m for _, m, _, _ in raw], 0)
+            gap = max(ragged.postnet_gap(post.postnet) if post.postnet is not None else 0, vocoder.ragged_gap() if vocoder is not None else 0)
+            mf = max_frames
+            if vocoder is not None:
+                mf = min(vocoder.default_max_frames() if max_frames is None else int(max_frames), vocoder.frame_limit())
+                hop = vocoder._packed_rate()
+            wavs, mels = [None] * len(raw), [None] * len(raw)
+            for idx in ragged.plan_chunks(lengths, gap, mf):
+                lay = ragged.PackedLayout([lengths[b] for b in idx], gap, [starts[b] for b in idx], src.device)
+                if post.postnet is not None:
+                    after = Fn.postnet_ragged(lay.pack_rows(src, Fn.compute_dtype()), post.postnet.postnet, lay)
+                else:
+                    after = lay.pack_rows(src, torch.float32)
+                _, per_row = lay.unpack_rows(after, odim)
+                for b, m in zip(idx, per_row):
+                    mels[b] = m
+                if vocoder is not None:
+                    _, per_row = lay.unpack_rows(vocoder.forward_packed(Fn.to_compute(after), lay), hop)
+                    for b, w in zip(idx, per_row):
+                        wavs[b] = w.reshape(-1)
+            return [(raw[b][0], wavs[b], mels[b], raw[b][2]) for b in range(len(raw))]
+        return tts_stream.run_stream(self, requests, rows, max_src_len, decode, False, finish, **kwargs)
+
     # ---- checkpoint compatibility (speecht5.py:1022-1058): non-strict per-submodule load ----
     def load_state_dict(self, state_dict, strict=True, model_cfg=None, args=None):
         """Never strict (as the reference): a checkpoint trained with another dictionary loses its dictionary-sized tensors

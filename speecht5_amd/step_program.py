@@ -65,7 +65,8 @@ class StepProgram:
         biases = list(biases)
         b = None if any(b is None for b in biases) else Fn.fused_bias(biases)
         self.shapes.append(tuple(w.shape))
-        self.ops.append(lambda: Fn.linear_skinny(x, w, b, out=out, ws=self.ws, **epi))   # (self.ws: looked up at call time, see finish)
+        fn = Fn.linear_skinny_rows if "step_rows" in epi else Fn.linear_skinny     # (one slot per row: the synthesis stream)
+        self.ops.append(lambda: fn(x, w, b, out=out, ws=self.ws, **epi))   # (self.ws: looked up at call time, see finish)
         return out
 
     def norm(self, ln, x, y):
@@ -82,13 +83,14 @@ class StepProgram:
             op()
 
 
-def append_layers(prog, x, layers, caches, Tmax, counter, self_attn, cross_attn=None, final_norm=None):
+def append_layers(prog, x, layers, caches, Tmax, counter, self_attn, cross_attn=None, final_norm=None, per_row=False):
     """Appends to `prog` the launches that take x [rows, C] (the newest position of every row) through the decoder `layers` and the
     optional final LayerNorm; returns the buffer that holds the result.  Position = the int32 device scalar `counter`: layer i's K|V go
     to slot `counter` of caches[i] [rows, Tmax, 2C] through the skinny GEMM's device-side output offset.  The attentions are the
     caller's launches, called at step time: self_attn(q, slots, ctx, H, hd) reads positions 0 .. counter of the layer's cache;
     cross_attn(i, q, ctx), when given, is layer i's encoder attention (without it the layers run none: the LM).  Pre- or post-LN per
-    layer (normalize_before; a layer without the attribute is pre-LN)."""
+    layer (normalize_before; a layer without the attribute is pre-LN).  per_row: `counter` is int32 [rows], one position per row (the
+    synthesis stream): row b's K|V go to slot counter[b]."""
     lin, norm, new, rows = prog.lin, prog.norm, prog.new, prog.rows
     C = layers[0].self_attn.embed_dim
     for idx, (layer, slots) in enumerate(zip(layers, caches)):
@@ -100,8 +102,8 @@ def append_layers(prog, x, layers, caches, Tmax, counter, self_attn, cross_attn=
         # self-attention
         h = before(layer.self_attn_layer_norm, x)
         q = lin(h, [sa.q_proj.weight], [sa.q_proj.bias], new(rows, C))
-        lin(h, [sa.k_proj.weight, sa.v_proj.weight], [sa.k_proj.bias, sa.v_proj.bias], slots, step=counter, step_stride=2 * C,
-            step_cap=Tmax, out_ld=Tmax * 2 * C)
+        lin(h, [sa.k_proj.weight, sa.v_proj.weight], [sa.k_proj.bias, sa.v_proj.bias], slots, step_stride=2 * C, step_cap=Tmax,
+            out_ld=Tmax * 2 * C, **({"step_rows": counter} if per_row else {"step": counter}))
         ctx = new(rows, C)
         prog.add(lambda q=q, slots=slots, ctx=ctx, H=H, hd=hd: self_attn(q, slots, ctx, H, hd))
         x = after(layer.self_attn_layer_norm, lin(ctx, [sa.out_proj.weight], [sa.out_proj.bias], new(rows, C), residual=x))

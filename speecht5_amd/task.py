@@ -291,6 +291,14 @@ class SpeechT5Task(LegacyFairseqTask):
             encoder_input.update(kwargs)
             return models[0].synthesize_batch(vocoder=vocoder, **encoder_input)
 
+    def generate_speech_stream(self, models, requests, **kwargs):
+        """Streaming generate_speech (T5TransformerModel.generate_speech_stream): (key, mel, probs, attn) in completion order."""
+        return models[0].generate_speech_stream(requests, **kwargs)
+
+    def synthesize_stream(self, models, requests, vocoder=None, **kwargs):
+        """Streaming text (or speech) to waveform (T5TransformerModel.synthesize_stream): (key, wav, mel, probs) in completion order."""
+        return models[0].synthesize_stream(requests, vocoder=vocoder, **kwargs)
+
     @property
     def source_dictionary(self):
         return None
