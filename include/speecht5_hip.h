@@ -542,6 +542,28 @@ int st5_batchnorm_act_bwd(const float* x, const float* dy, const float* stats, c
                           float* dbeta, int32_t training, int32_t act, float dropout_p, uint64_t seed, void* dx, void* ws,
                           int64_t rows, int32_t C, int64_t out_L, int64_t out_bstride, int64_t out_off, int32_t halo, int dtype,
                           void* stream);
+/* Live-frame variants for a FIXED-SHAPE batch (csrc/batchnorm_live_index.h): x is [B, Lx, C] and only the first *live rows of every
+ * batch element exist in the batch the reference would have collated; `live` is ONE int32 cell in device memory, clamped by the
+ * kernels to [0, Lx], so a captured launch serves every batch (the grid comes from the physical `rows` = B * Lx; nothing reads the
+ * cell on the host).  Row r is live iff r % Lx < *live.  Statistics (and the running-statistics update, unbiased variance over
+ * B * live - 1) range over the live rows; dead rows of y -- the next convolution's operand, or the fp32 output, the residual NOT
+ * added -- and of dx are exact zeros; dy of a dead row counts as zero, so dgamma / dbeta take nothing from it.  training = 0: running
+ * statistics plus the same zeroing.  Dropout counters stay the physical row * C + c: at *live == Lx every output is the bits of the
+ * entry point above.  *live == 0: every output row zero, running statistics untouched.  out_L, when given, must equal Lx. */
+int st5_batchnorm_act_fwd_live(const float* x, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                               int64_t* num_batches_tracked, float momentum, float eps, int32_t training, int32_t act,
+                               float dropout_p, uint64_t seed, const void* residual, void* y, int32_t y_f32, float* stats, void* ws,
+                               int64_t rows, int32_t C, int64_t out_L, int64_t out_bstride, int64_t out_off, int32_t halo,
+                               const int32_t* live, int64_t Lx, int dtype, void* stream);
+int st5_batchnorm_act_bwd_live(const float* x, const float* dy, const float* stats, const float* gamma, const float* beta, float* dgamma,
+                               float* dbeta, int32_t training, int32_t act, float dropout_p, uint64_t seed, void* dx, void* ws,
+                               int64_t rows, int32_t C, int64_t out_L, int64_t out_bstride, int64_t out_off, int32_t halo,
+                               const int32_t* live, int64_t Lx, int dtype, void* stream);
+/* st5_pad_time with rows t >= *live of every batch element written as zeros (the post-net's first operand on a fixed-shape batch), and
+ * x[b, t, :] = 0 for t >= *live on an fp32 [B, Lx, C] buffer (the post-net's input gradient); `live` as above. */
+int st5_pad_time_live(const void* src, void* dst, int32_t B, int32_t T, int32_t C, int32_t pad_l, int32_t pad_r, const int32_t* live,
+                      int dtype, void* stream);
+int st5_zero_rows_live(float* x, int32_t B, int32_t Lx, int32_t C, const int32_t* live, void* stream);
 
 /* ---- losses ---- */
 /* Row-wise (label-smoothed) cross entropy on logits [rows, ld] (dtype, first V cols valid).

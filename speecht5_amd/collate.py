@@ -159,10 +159,45 @@ def _pad_tokens(items, lens, B, T, pad, device, order=None, shift=False):
 
 class TextToSpeechCollater:
     """TextToSpeechDataset.collater (data/text_to_speech_dataset.py:228-281) + _collate_frames (:27-45) + collater_label (:289-298).
-    samples: [{"id", "audio_name", "source": [int64 [n] (device)], "target": fp32 [L, odim] (device), "spkembs": fp32 [D] (device)}]."""
+    samples: [{"id", "audio_name", "source": [int64 [n] (device)], "target": fp32 [L, odim] (device), "spkembs": fp32 [D] (device)}].
+    fixed_shape=(N, L): every batch has the same tensor shapes -- what a replayed update (graph.BatchFeed) needs of its source:
+    `src_tokens` is padded to N columns with `pad`, `dec_target` / `labels` to L frames (zero frames, labels 1.0 in the tail) and
+    `prev_output_tokens` to L // r steps, exactly as the own-length batch is padded, only further; L % r == 0.  The batch then
+    carries one more key, net_input["tgt_live"] = int32 [1] on the device = (longest utterance) // r: the decoder steps the
+    own-length batch would have had, which the mel post-net needs (its batch statistics and convolutions are the one part of the
+    t2s step that lengths do not mask; T5TransformerModel.forward(tgt_live=...)).  An item with more than N tokens or more than
+    L frames, or an utterance of fewer than r frames, is refused with a ValueError naming it.  None (default): padded to the
+    batch's own maxima, the reference's batch, without the key."""
 
-    def __init__(self, device, *, pad_idx=1, reduction_factor=2):
+    def __init__(self, device, *, pad_idx=1, reduction_factor=2, fixed_shape=None):
         self.device, self.pad_idx, self.reduction_factor = device, pad_idx, reduction_factor
+        if fixed_shape is not None:
+            if not (isinstance(fixed_shape, (tuple, list)) and len(fixed_shape) == 2
+                    and all(isinstance(v, int) and not isinstance(v, bool) and v >= 1 for v in fixed_shape)):
+                raise ValueError(f"fixed_shape = {fixed_shape!r}: (text columns, mel frames), both at least 1")
+            fixed_shape = tuple(fixed_shape)
+            if fixed_shape[1] % reduction_factor or fixed_shape[1] < reduction_factor:
+                raise ValueError(f"fixed_shape = {fixed_shape!r}: the mel frames are a positive multiple of reduction_factor = {reduction_factor}")
+        self.fixed_shape = fixed_shape
+
+    @staticmethod
+    def plan(ids, n_tokens, n_frames, reduction_factor, fixed_shape=None):
+        """The batch's padded shape from host ints (no device work): (text columns N, mel frames L, live decoder steps).  Without
+        fixed_shape the batch's own maxima; with it the fixed pair, and a ValueError naming the first item that does not fit or whose
+        utterance is shorter than one decoder step."""
+        r = reduction_factor
+        live = max(n_frames) // r if r > 1 else max(n_frames)
+        if fixed_shape is None:
+            return max(n_tokens), max(n_frames), live
+        N, L = fixed_shape
+        for i, k, f in zip(ids, n_tokens, n_frames):
+            if k > N:
+                raise ValueError(f"item {i!r}: {k} tokens, fixed_shape pads `src_tokens` to {N} columns")
+            if f > L:
+                raise ValueError(f"item {i!r}: {f} frames, fixed_shape pads `dec_target` to {L} frames")
+            if f < r:
+                raise ValueError(f"item {i!r}: {f} frames, fewer than reduction_factor = {r}: the utterance has no decoder step")
+        return N, L, live
 
     def collater(self, samples):
         samples = [s for s in samples if s["source"] is not None]
@@ -171,22 +206,27 @@ class TextToSpeechCollater:
         dev, B, r = self.device, len(samples), self.reduction_factor
         fbanks = [s["target"].contiguous() for s in samples]
         sizes = [int(f.shape[0]) for f in fbanks]
-        odim, Lmax = int(fbanks[0].shape[1]), max(sizes)
+        odim = int(fbanks[0].shape[1])
+        toks = [s["source"][0].contiguous() for s in samples]
+        tlen = [int(t.shape[0]) for t in toks]
+        N, Lmax, live = self.plan([s["id"] for s in samples], tlen, sizes, r, self.fixed_shape)      # (refuses before anything is launched)
         dec_target = _ragged(fbanks, [0] * B, sizes, B, Lmax, odim, 1, 0, torch.float32, 0.0, dev)
         dec_lengths = _lengths(sizes, dev)
         # decoder input (:239-248): frames r-1, 2r-1, ... of the PADDED batch, shifted right by one behind a zero frame
         Lin = len(range(r - 1, Lmax, r)) if r > 1 else Lmax
-        prev = _ragged(fbanks, [-1] * B, sizes, B, Lin, odim, r, 1, torch.float32, 0.0, dev)
+        # (a fixed shape has steps behind the own-length batch's last one, step `live`: they stay zero frames, as padding is)
+        prev_hi = sizes if self.fixed_shape is None else [min(l, live * r - 1) for l in sizes]
+        prev = _ragged(fbanks, [-1] * B, prev_hi, B, Lin, odim, r, 1, torch.float32, 0.0, dev)
         tgt_lengths = _lengths([l // r for l in sizes], dev) if r > 1 else dec_lengths
         labels = _tail([l - 1 for l in sizes], B, Lmax, True, dev)                 # (:251-253: 1.0 from the last frame on)
         spk = [s["spkembs"].contiguous() for s in samples]
         spkembs = _ragged(spk, [0] * B, [int(v.shape[0]) for v in spk], B, max(int(v.shape[0]) for v in spk), 1, 1, 0, torch.float32, 0.0, dev)
-        toks = [s["source"][0].contiguous() for s in samples]
-        tlen = [int(t.shape[0]) for t in toks]
-        src_tokens = _pad_tokens(toks, tlen, B, max(tlen), self.pad_idx, dev)
+        src_tokens = _pad_tokens(toks, tlen, B, N, self.pad_idx, dev)
         src_lengths = _lengths(tlen, dev)
         net_input = {"src_tokens": src_tokens, "src_lengths": src_lengths, "prev_output_tokens": prev, "tgt_lengths": tgt_lengths,
                      "spkembs": spkembs, "task_name": "t2s"}
+        if self.fixed_shape is not None:
+            net_input["tgt_live"] = _i32([live], dev)
         return {"id": torch.LongTensor([s["id"] for s in samples]), "name": [s.get("audio_name") for s in samples], "net_input": net_input,
                 "labels": labels, "dec_target": dec_target, "dec_target_lengths": dec_lengths, "src_lengths": src_lengths, "task_name": "t2s",
                 "ntokens": int(sum(tlen)), "target": dec_target}

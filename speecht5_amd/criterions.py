@@ -100,14 +100,18 @@ class GuidedMultiHeadAttentionLoss(nn.Module):
 
 
 class TexttoSpeechLoss(nn.Module):
-    """text_to_speech_loss.py:53-257."""
+    """text_to_speech_loss.py:53-257.
+    device_ntokens=True (not in the reference): the logged `ntokens` is sample["src_lengths"].sum(), a device scalar, instead of the
+    sample's host count -- the same number, and the one a replayed update fed with a new batch per replay can report
+    (train_stats.DEVICE_LOGGED_OPTIONS).  Loss and gradients do not read it."""
 
     def __init__(self, task, sentence_avg=False, use_masking=True, use_weighted_masking=False, loss_type="L1",
                  bce_pos_weight=5.0, bce_loss_lambda=1.0, use_guided_attn_loss=False, guided_attn_loss_sigma=0.4,
                  guided_attn_loss_lambda=1.0, num_layers_applied_guided_attn=2, num_heads_applied_guided_attn=2,
-                 modules_applied_guided_attn=("encoder-decoder",), sync_logging=True):
+                 modules_applied_guided_attn=("encoder-decoder",), sync_logging=True, device_ntokens=False):
         super().__init__()
         self.task = task
+        self.device_ntokens = bool(device_ntokens)
         self.loss_type = loss_type
         self.bce_loss_lambda = bce_loss_lambda
         self.use_guided_attn_loss = use_guided_attn_loss
@@ -125,6 +129,8 @@ class TexttoSpeechLoss(nn.Module):
         s = self.sync_logging
         log = {"loss": _item(loss, s), "l1_loss": _item(l1, s), "l2_loss": _item(l2, s), "bce_loss": _item(bce, s),
                "sample_size": 1, "ntokens": sample["ntokens"], "nsentences": sample["target"].size(0)}
+        if self.device_ntokens:
+            log["ntokens"] = _item(torch.as_tensor(sample["src_lengths"]).sum(), s)
         if ga is not None:
             log["enc_dec_attn_loss"] = _item(ga, s)
         # (:142-146) the scaled positional encodings' alphas, what reduce_metrics reports as <task>_encoder_alpha / _decoder_alpha
@@ -457,11 +463,12 @@ class SpeechT5Criterion(FairseqCriterion):
                  use_masking=True, use_weighted_masking=False, loss_type="L1", bce_pos_weight=5.0, bce_loss_lambda=1.0,
                  use_guided_attn_loss=False, num_heads_applied_guided_attn=2, ce_weight=1.0, ctc_weight=0.0, hubert_weight=1.0,
                  dec_weight=1.0, bart_weight=1.0, pred_masked_weight=1.0, pred_nomask_weight=0.0, loss_weights=None, cfg=None,
-                 sync_logging=True, guided_attn_loss_lambda=1.0, guided_attn_loss_sigma=0.4, log_keys=None, device_targets=False):
+                 sync_logging=True, guided_attn_loss_lambda=1.0, guided_attn_loss_sigma=0.4, log_keys=None, device_targets=False,
+                 device_ntokens=False):
         super().__init__(task)
         self.speech_criterion = TexttoSpeechLoss(task, sentence_avg, use_masking, use_weighted_masking, loss_type, bce_pos_weight,
                                                  bce_loss_lambda, use_guided_attn_loss, guided_attn_loss_sigma, guided_attn_loss_lambda,
-                                                 2, num_heads_applied_guided_attn, sync_logging=sync_logging)
+                                                 2, num_heads_applied_guided_attn, sync_logging=sync_logging, device_ntokens=device_ntokens)
         self.text_criterion = SpeechtoTextLoss(cfg, task, sentence_avg, label_smoothing, ignore_prefix_size, report_accuracy,
                                                ce_weight, ctc_weight, sync_logging=sync_logging, device_targets=device_targets)
         self.text_pretrain_criterion = TextPretrainCriterion(task, sentence_avg, bart_weight, loss_weights, sync_logging=sync_logging)

@@ -3,6 +3,7 @@
 #include <initializer_list>
 #include "common.h"
 #include "stream_scratch.h"
+#include "batchnorm_live_index.h"
 #include "../../include/speecht5_hip.h"
 
 namespace {
@@ -475,6 +476,34 @@ __global__ void pad_time_kernel(const T* __restrict__ src, T* __restrict__ dst, 
   for (int c = threadIdx.x & 63; c < C; c += 64) d[c] = in ? s[c] : zero;
 }
 
+// pad_time_kernel with the rows t >= *live (one device cell, clamped to [0, Tn]) written as zeros too: the first convolution's operand
+// of the mel post-net on a fixed-shape batch (batchnorm_live_index.h).  The grid covers the physical rows; the cell is read here.
+template <typename T>
+__global__ void pad_time_live_kernel(const T* __restrict__ src, T* __restrict__ dst, int B, int Tn, int C, int pad_l, int pad_r,
+                                     const int32_t* __restrict__ live_cell) {
+  const int Tp = pad_l + Tn + pad_r;
+  const long long nrow = (long long)B * Tp;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nrow) return;
+  const long long live = bnl_clamp((long long)live_cell[0], Tn);
+  const int b = (int)(row / Tp), t = (int)(row % Tp) - pad_l;
+  const bool in = t >= 0 && t < Tn && bnl_row_live(t, Tn, live);
+  const T* s = src + ((long long)b * Tn + (in ? t : 0)) * C;
+  T* d = dst + row * C;
+  const T zero = Elem<T>::from_f(0.f);
+  for (int c = threadIdx.x & 63; c < C; c += 64) d[c] = in ? s[c] : zero;
+}
+// x[b, t, :] = 0 for t >= *live (x fp32 [B, Lx, C]): the dead rows of the post-net's input gradient.  One wave per physical row; a
+// live row's wave leaves at once.
+__global__ __launch_bounds__(256) void zero_rows_live_kernel(float* __restrict__ x, int B, int Lx, int C, const int32_t* __restrict__ live_cell) {
+  const long long nrow = (long long)B * Lx;
+  const long long row = (long long)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (row >= nrow) return;
+  if (bnl_row_live(row, Lx, bnl_clamp((long long)live_cell[0], Lx))) return;
+  float* d = x + row * C;
+  for (int c = threadIdx.x & 63; c < C; c += 64) d[c] = 0.f;
+}
+
 // dst[b, t', :] = act(src[b, t' - pad_l, :]) inside, 0 in the halo (every activation used here maps 0 to 0, so this is the padded
 // copy of act(src)); one 16-byte vector per thread -- with narrow rows (HiFi-GAN's late stages: 32 channels = 64 bytes per row) a
 // wave-per-row copy moves 64 bytes per wave.  Requires C * sizeof(T) % 16 == 0.
@@ -902,6 +931,24 @@ extern "C" int st5_pad_time(const void* src, void* dst, int32_t B, int32_t T, in
   dim3 grid((unsigned)((nrow + 3) / 4));
   DISPATCH(dtype, hipLaunchKernelGGL(pad_time_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)dst, B, T, C, pad_l, pad_r),
            hipLaunchKernelGGL(pad_time_kernel<float>, grid, dim3(256), 0, s, (const float*)src, (float*)dst, B, T, C, pad_l, pad_r));
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+extern "C" int st5_pad_time_live(const void* src, void* dst, int32_t B, int32_t T, int32_t C, int32_t pad_l, int32_t pad_r,
+                                 const int32_t* live, int dtype, void* stream) {
+  if (!src || !dst || !live || B <= 0 || T <= 0 || C <= 0 || pad_l < 0 || pad_r < 0) return ST5_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  const long long nrow = (long long)B * (pad_l + T + pad_r);
+  dim3 grid((unsigned)((nrow + 3) / 4));
+  DISPATCH(dtype, hipLaunchKernelGGL(pad_time_live_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)src, (bf16_t*)dst, B, T, C, pad_l, pad_r, live),
+           hipLaunchKernelGGL(pad_time_live_kernel<float>, grid, dim3(256), 0, s, (const float*)src, (float*)dst, B, T, C, pad_l, pad_r, live));
+  HIP_CHECK_LAUNCH();
+  return ST5_OK;
+}
+extern "C" int st5_zero_rows_live(float* x, int32_t B, int32_t Lx, int32_t C, const int32_t* live, void* stream) {
+  if (!x || !live || B <= 0 || Lx <= 0 || C <= 0) return ST5_ERR_ARG;
+  const long long nrow = (long long)B * Lx;
+  hipLaunchKernelGGL(zero_rows_live_kernel, dim3((unsigned)((nrow + 3) / 4)), dim3(256), 0, (hipStream_t)stream, x, B, Lx, C, live);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }

@@ -3258,8 +3258,13 @@ class PostnetFunction(torch.autograd.Function):
     def forward(ctx, before, cfg, bufs, *params):
         """before [B, L, odim] (compute dtype); cfg = (training, dropout_p, [(eps, momentum)] per layer); bufs = per layer
         (running_mean, running_var, num_batches_tracked); params = per layer (conv_weight [Cout,Cin,k], bn_weight, bn_bias).
-        Returns after fp32 [B, L, odim]."""
-        training, p_drop, bn_cfg = cfg
+        Returns after fp32 [B, L, odim].
+        cfg may carry a fourth entry `live`: int32 [1] on the device, the frames per batch element that exist in the own-length
+        batch (a fixed-shape batch is padded further).  Convolutions and statistics then range over the frames t < live alone --
+        the st5_*_live entry points read the cell on the device, so a captured step serves every batch -- and rows t >= live of
+        `after` and of the gradient are exact zeros."""
+        training, p_drop, bn_cfg = cfg[:3]
+        live = cfg[3] if len(cfg) > 3 else None
         dtype = before.dtype
         dev = before.device
         B, Lx, odim = before.shape
@@ -3269,7 +3274,11 @@ class PostnetFunction(torch.autograd.Function):
         k0 = params[0].shape[2]
         pad = (k0 - 1) // 2
         xp = torch.empty(B, Lx + 2 * pad, odim, dtype=dtype, device=dev)
-        hip.check(L.st5_pad_time(before.data_ptr(), xp.data_ptr(), B, Lx, odim, pad, pad, _dt(dtype), hip.stream()), "st5_pad_time")
+        if live is None:
+            hip.check(L.st5_pad_time(before.data_ptr(), xp.data_ptr(), B, Lx, odim, pad, pad, _dt(dtype), hip.stream()), "st5_pad_time")
+        else:
+            hip.check(L.st5_pad_time_live(before.data_ptr(), xp.data_ptr(), B, Lx, odim, pad, pad, live.data_ptr(), _dt(dtype), hip.stream()),
+                      "st5_pad_time_live")
         saved, seeds = [], []
         after = None
         for i in range(n):
@@ -3288,7 +3297,21 @@ class PostnetFunction(torch.autograd.Function):
             p = p_drop if training else 0.0
             seed = next_seed() if p > 0 else 0
             mom_eff = mom if mom is not None else 0.1
-            if last:
+            if live is not None:
+                head = (x32.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hip.ptr(rm), hip.ptr(rv), hip.ptr(nbt), mom_eff, eps,
+                        1 if training else 0)
+                if last:
+                    after = torch.empty(B, Lx, Cout, dtype=torch.float32, device=dev)
+                    hip.check(L.st5_batchnorm_act_fwd_live(*head, ACT_NONE, p, seed, before.data_ptr(), after.data_ptr(), 1, stats.data_ptr(),
+                                                           ws.data_ptr(), B * Lx, Cout, 0, 0, 0, 0, live.data_ptr(), Lx, _dt(dtype), hip.stream()),
+                              "st5_batchnorm_act_fwd_live")
+                    nxt = None
+                else:
+                    nxt = torch.empty(B, Lx + 2 * pad, Cout, dtype=dtype, device=dev)
+                    hip.check(L.st5_batchnorm_act_fwd_live(*head, ACT_TANH, p, seed, 0, nxt.data_ptr(), 0, stats.data_ptr(), ws.data_ptr(),
+                                                           B * Lx, Cout, Lx, (Lx + 2 * pad) * Cout, pad * Cout, pad, live.data_ptr(), Lx,
+                                                           _dt(dtype), hip.stream()), "st5_batchnorm_act_fwd_live")
+            elif last:
                 after = torch.empty(B, Lx, Cout, dtype=torch.float32, device=dev)
                 hip.check(L.st5_batchnorm_act_fwd(x32.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hip.ptr(rm), hip.ptr(rv), hip.ptr(nbt),
                                                   mom_eff, eps, 1 if training else 0, ACT_NONE, p, seed, before.data_ptr(), after.data_ptr(),
@@ -3306,11 +3329,13 @@ class PostnetFunction(torch.autograd.Function):
             xp = nxt
         ctx.save_for_backward(*saved)
         ctx.meta = (params, training, seeds, B, Lx, pad, dtype)
+        ctx.live = live
         return after
 
     @staticmethod
     def backward(ctx, d_after):
         params, training, seeds, B, Lx, pad, dtype = ctx.meta
+        live = ctx.live
         saved = ctx.saved_tensors
         n = len(params) // 3
         dev = d_after.device
@@ -3327,10 +3352,17 @@ class PostnetFunction(torch.autograd.Function):
             ws = hip.workspace(L.st5_batchnorm_ws_bytes(Cout), dev)
             gg = grad_buffer(gamma) if gamma.requires_grad else None
             gb = grad_buffer(beta) if beta.requires_grad else None
-            hip.check(L.st5_batchnorm_act_bwd(x32.data_ptr(), dy.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hip.ptr(gg),
-                                              hip.ptr(gb), 1 if training else 0, ACT_NONE if i == n - 1 else ACT_TANH, p, seed, dxp.data_ptr(),
-                                              ws.data_ptr(), B * Lx, Cout, Lx, (Lx + 2 * pad) * Cout, pad * Cout, pad, _dt(dtype), hip.stream()),
-                      "st5_batchnorm_act_bwd")
+            if live is None:
+                hip.check(L.st5_batchnorm_act_bwd(x32.data_ptr(), dy.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(), hip.ptr(gg),
+                                                  hip.ptr(gb), 1 if training else 0, ACT_NONE if i == n - 1 else ACT_TANH, p, seed, dxp.data_ptr(),
+                                                  ws.data_ptr(), B * Lx, Cout, Lx, (Lx + 2 * pad) * Cout, pad * Cout, pad, _dt(dtype), hip.stream()),
+                          "st5_batchnorm_act_bwd")
+            else:      # dy of rows t >= live counts as zero (they reach here non-zero near the edge, out of the data-gradient GEMM)
+                hip.check(L.st5_batchnorm_act_bwd_live(x32.data_ptr(), dy.data_ptr(), stats.data_ptr(), gamma.data_ptr(), beta.data_ptr(),
+                                                       hip.ptr(gg), hip.ptr(gb), 1 if training else 0, ACT_NONE if i == n - 1 else ACT_TANH,
+                                                       p, seed, dxp.data_ptr(), ws.data_ptr(), B * Lx, Cout, Lx, (Lx + 2 * pad) * Cout,
+                                                       pad * Cout, pad, live.data_ptr(), Lx, _dt(dtype), hip.stream()),
+                          "st5_batchnorm_act_bwd_live")
             for q in (gamma, beta):
                 if q.requires_grad:
                     _grad_done(q)
@@ -3353,20 +3385,29 @@ class PostnetFunction(torch.autograd.Function):
                 dy = din
                 if i == 0:
                     d_before = din
+                    if live is not None:      # rows t >= live of `before` were read as zeros and their `after` rows written as zeros
+                        hip.check(L.st5_zero_rows_live(din.data_ptr(), B, Lx, Cin, live.data_ptr(), hip.stream()), "st5_zero_rows_live")
         gx = None
         if ctx.needs_input_grad[0]:
             gx = (d_before if dtype == torch.float32 else to_compute(d_before)).view(B, Lx, -1)
         return (gx, None, None) + (None,) * len(params)
 
 
-def postnet(before, blocks, training, dropout_p):
-    """blocks: the nn.Sequential blocks of espnet's Postnet (block[0] = Conv1d without bias, block[1] = BatchNorm1d)."""
+def postnet(before, blocks, training, dropout_p, live=None):
+    """blocks: the nn.Sequential blocks of espnet's Postnet (block[0] = Conv1d without bias, block[1] = BatchNorm1d).
+    live: None, or an int32 [1] device tensor = the frames per batch element the own-length batch would hold (PostnetFunction)."""
+    if live is not None:
+        if not (torch.is_tensor(live) and live.dtype == torch.int32 and live.numel() == 1 and live.device == before.device):
+            raise ValueError("postnet: `live` is an int32 tensor of one element on the device of `before`")
+        live = live.contiguous()
     params, bufs, cfg = [], [], []
     for blk in blocks:
         conv, bn = blk[0], blk[1]
         params += [conv.weight, bn.weight, bn.bias]
         bufs.append((bn.running_mean, bn.running_var, bn.num_batches_tracked))
         cfg.append((float(bn.eps), bn.momentum))
+    if live is not None:
+        return PostnetFunction.apply(before, (bool(training), float(dropout_p), cfg, live), bufs, *params)
     return PostnetFunction.apply(before, (bool(training), float(dropout_p), cfg), bufs, *params)
 
 

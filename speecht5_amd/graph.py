@@ -42,6 +42,18 @@ HOST_VALUES_FREE = {
     # DESIGN.md 4m has the audit of every host value of an s2t sample
     "s2t": ("ntokens", "nsentences"),
 }
+# TTS fine-tuning, in a table of its own: HOST_VALUES_FREE keeps the entries it had (tests/test_ctc_pack_cpu.py pins that it does not
+# name t2s).  `ntokens` only feeds the log; with the criterion's device_ntokens=True the log takes src_lengths.sum() off the device
+# instead (update.check_t2s_source).  `nsentences` is B, a function of the signature.  DESIGN.md 4p has the audit
+HOST_VALUES_FREE_T2S = {
+    "t2s": ("ntokens",),
+}
+
+
+def host_values_free():
+    """{task name: host values of a sample that may differ from batch to batch}: both tables, what BatchFeed.check and the statistics
+    audit (train_stats.check_feed_host_values) go by."""
+    return {**HOST_VALUES_FREE, **HOST_VALUES_FREE_T2S}
 # keys a criterion writes into the sample it is given (criterions.py: dec_weight == 0, ce_weight == 0): not part of a batch
 CRITERION_WRITTEN = ("net_input.only_hubert", "only_ctc")
 
@@ -200,7 +212,7 @@ class BatchFeed:
                     raise ValueError(f"{_path(i, k)}: {what}, the recorded signature has {tuple(ref.shape)} {ref.dtype} on {ref.device}")
             elif torch.is_tensor(v):
                 raise ValueError(f"{_path(i, k)}: a tensor, the recorded signature has a {type(ref).__name__}")
-            elif k != ("task_name",) and not (len(k) == 1 and k[0] in HOST_VALUES_FREE.get(self.static[i].get("task_name"), ())) \
+            elif k != ("task_name",) and not (len(k) == 1 and k[0] in host_values_free().get(self.static[i].get("task_name"), ())) \
                     and not _same_host_value(v, ref):
                 raise ValueError(f"{_path(i, k)}: {v!r}, the step was recorded with {ref!r} -- a host value that reaches "
                                  "a captured launch (for text_pretrain's ntokens: the loss divisor) cannot change between replays")

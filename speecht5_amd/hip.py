@@ -298,6 +298,14 @@ _SIGS = {
                                       c_int64, c_int64, c_int32, c_int, c_void_p]),
     "st5_batchnorm_act_bwd": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float,
                                       c_uint64, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_int32, c_int, c_void_p]),
+    "st5_batchnorm_act_fwd_live": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_float, c_float, c_int32, c_int32,
+                                           c_float, c_uint64, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_int64, c_int32, c_int64,
+                                           c_int64, c_int64, c_int32, c_void_p, c_int64, c_int, c_void_p]),
+    "st5_batchnorm_act_bwd_live": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32, c_float,
+                                           c_uint64, c_void_p, c_void_p, c_int64, c_int32, c_int64, c_int64, c_int64, c_int32, c_void_p,
+                                           c_int64, c_int, c_void_p]),
+    "st5_pad_time_live": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p, c_int, c_void_p]),
+    "st5_zero_rows_live": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p]),
     "st5_ctc_greedy_rows": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
     "st5_tokens_to_words": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32,
                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),

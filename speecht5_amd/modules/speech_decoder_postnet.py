@@ -25,12 +25,16 @@ class Postnet(nn.Module):
             mods.append(nn.Dropout(dropout_rate))
             self.postnet.append(nn.Sequential(*mods))
 
-    def forward(self, x):
+    def forward(self, x, live=None):
         """x = `before` [B, L, odim] channels-last (compute dtype) -> `after` = before + postnet(before), fp32 [B, L, odim].
         Convolutions on the implicit-GEMM kernel (fp32 accumulators handed over), BatchNorm (batch statistics, running
-        statistics update) + tanh + dropout + the final residual on st5_batchnorm_act_* (functional.PostnetFunction)."""
+        statistics update) + tanh + dropout + the final residual on st5_batchnorm_act_* (functional.PostnetFunction).
+        live: None, or int32 [1] on the device = the FRAMES per batch element that the own-length batch holds (a fixed-shape batch):
+        convolutions and statistics see the frames t < live alone and `after` is zero behind them."""
         training = self.postnet[0][1].training
-        return Fn.postnet(x, self.postnet, training, self.dropout_rate if self.training else 0.0)
+        if live is None:
+            return Fn.postnet(x, self.postnet, training, self.dropout_rate if self.training else 0.0)
+        return Fn.postnet(x, self.postnet, training, self.dropout_rate if self.training else 0.0, live=live)
 
     @torch.no_grad()
     def forward_ragged(self, mels, max_frames=None, lengths=None):
@@ -67,10 +71,13 @@ class SpeechDecoderPostnet(nn.Module):
             idim=0, odim=odim, n_layers=args.postnet_layers, n_chans=args.postnet_chans, n_filts=args.postnet_filts,
             use_batch_norm=args.use_batch_norm, dropout_rate=args.postnet_dropout_rate)
         self.odim = odim
+        self.reduction_factor = args.reduction_factor
         self.num_updates = 0
         self.freeze_decoder_updates = args.freeze_decoder_updates
 
-    def forward(self, zs):
+    def forward(self, zs, live=None):
+        """live: None, or int32 [1] on the device = the decoder STEPS the own-length batch holds (the collater's `tgt_live`); the
+        post-net takes it in frames, steps * reduction_factor, multiplied on the device."""
         ft = self.freeze_decoder_updates <= self.num_updates
         with torch.no_grad() if not ft else contextlib.ExitStack():
             zs = Fn.as_compute(zs)
@@ -82,6 +89,8 @@ class SpeechDecoderPostnet(nn.Module):
             logits = both[..., nf:].reshape(B, -1)
             if self.postnet is None:
                 after = Fn.as_float(before.contiguous())
+            elif live is not None:
+                after = self.postnet(before.contiguous(), live=(live * self.reduction_factor).to(torch.int32))
             else:
                 after = self.postnet(before.contiguous())   # fp32: before + post-net residual (fused into the last BatchNorm kernel)
         return Fn.as_float(before.contiguous()), after, Fn.as_float(logits.contiguous())

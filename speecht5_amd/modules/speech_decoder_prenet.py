@@ -64,7 +64,8 @@ class SpeechDecoderPrenet(nn.Module):
             tgt_frames_mask = None
             if tgt_lengths_in is not None:
                 lens = torch.as_tensor(tgt_lengths_in, device=x.device)
-                # the batch is padded to its longest target, so max(lens) == T: no host read needed
+                # the mask is as wide as the padded batch -- its longest target, or further for a fixed-shape batch (a step behind
+                # every length is masked either way): no host read needed
                 tgt_frames_mask = torch.arange(x.size(1), device=x.device)[None, :] >= lens[:, None]
             return x, tgt_frames_mask
 

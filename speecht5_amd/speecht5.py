@@ -244,8 +244,13 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
     # ---- forward (speecht5.py:786-963) ----
     def forward(self, source=None, src_tokens=None, src_lengths=None, prev_output_tokens=None, tgt_lengths=None, spkembs=None,
                 target_list=None, task_name=None, padding_mask=None, only_hubert=False, only_ctc=False, feature_only=False,
-                tgt_enc_layer=None, mask=True):
+                tgt_enc_layer=None, mask=True, tgt_live=None):
+        """tgt_live (not in the reference): int32 [1] on the device, the decoder steps of the batch the own-length collater would have
+        built (collate.TextToSpeechCollater(fixed_shape=...) sets it: max length // reduction factor).  t2s only: the mel post-net's
+        convolutions and batch statistics then range over those steps' frames alone."""
         assert source is not None or src_tokens is not None
+        if tgt_live is not None and task_name != "t2s":
+            raise ValueError(f"tgt_live is the t2s route's (task_name {task_name!r}): only the text-to-speech fixed-shape batch has it")
         input_type = "text" if (source is None and padding_mask is None and not feature_only) else "speech"
         if prev_output_tokens is not None and len(prev_output_tokens.size()) == 2:
             output_type = "text"
@@ -354,6 +359,8 @@ class T5TransformerModel(FairseqEncoderDecoderModel):
             return (self.text_decoder_postnet(decoder_output), None), codebook_out, encoder_output
         if target_list is not None:
             return hubert_results, (self.speech_decoder_postnet(decoder_output) + (extra["attn"][0],))
+        if tgt_live is not None:
+            return self.speech_decoder_postnet(decoder_output, live=tgt_live) + (extra["attn"][0],)
         return self.speech_decoder_postnet(decoder_output) + (extra["attn"][0],)
 
     # ---- inference entry points (speecht5.py:1112-1249) ----

@@ -43,15 +43,20 @@ LOGGED_SAMPLE_VALUES = {
 
 # Entries of LOGGED_SAMPLE_VALUES that a criterion OPTION takes off the host: {task name: {logging key: how}}.  The s2t criterion
 # with device_targets=True logs the pack kernel's label count as `ntokens` (a device cell), and with sentence_avg=True its
-# `sample_size` is B, a function of the batch signature.  check_feed_host_values skips exactly the keys its caller names.
+# `sample_size` is B, a function of the batch signature.  The t2s criterion with device_ntokens=True logs src_lengths.sum(), a device
+# scalar.  check_feed_host_values skips exactly the keys its caller names.
 DEVICE_LOGGED_OPTIONS = {
     "s2t": {"ntokens": "device_targets=True", "sample_size": "sentence_avg=True"},
+    "t2s": {"ntokens": "device_ntokens=True"},
 }
 
 
 def device_logged(task_name, criterion):
     """The logging keys of LOGGED_SAMPLE_VALUES[task_name] that `criterion` (a SpeechT5Criterion, or the task's own criterion) does
     not take from the sample's host value, as check_feed_host_values' `device_logged` entry for that task."""
+    if task_name == "t2s":
+        c = getattr(criterion, "speech_criterion", criterion)
+        return ("ntokens",) if getattr(c, "device_ntokens", False) else ()
     if task_name != "s2t":
         return ()
     c = getattr(criterion, "text_criterion", criterion)

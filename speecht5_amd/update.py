@@ -51,6 +51,9 @@ nonfinite=None (default): nothing of this exists; the update is built and launch
 
 ASR fine-tuning (an s2t micro-batch): under a source the criterion must run with sentence_avg=True and, with a CTC term,
 device_targets=True (check_s2t_source refuses by option name); the source is collate.SpeechToTextCollater(fixed_shape=...).
+TTS fine-tuning (a t2s micro-batch): the source is collate.TextToSpeechCollater(fixed_shape=...), whose batches carry
+net_input["tgt_live"] -- the mel post-net then ranges over the frames of the own-length batch (st5_batchnorm_act_*_live) -- and with
+stats=True the criterion runs with device_ntokens=True (check_t2s_source refuses by option name).  s2s and s2c stay refused.
 Freeze boundaries: --freeze-encoder-updates / --freeze-decoder-updates are host decisions of the forward (`threshold <= num_updates`),
 so a captured step has the decision of the update it was captured with.  update() raises RuntimeError, before anything is enqueued or
 pulled, when the coming replay's update number lies on the other side of a threshold; recapture=True (needs prefetch_host=False)
@@ -113,6 +116,28 @@ def check_s2t_source(micro_batches, criterion, graph=True):
         if getattr(c, "ctc_weight", 0) > 0 and not getattr(c, "device_targets", False):
             raise ValueError(f"micro_batches[{i}] (s2t) under a source with ctc_weight > 0 needs the criterion's device_targets=True: "
                              "device_targets=False builds the CTC targets with masked_select, a device-to-host read no capture survives")
+
+
+def check_t2s_source(micro_batches, criterion, graph=True, stats=False):
+    """A t2s micro-batch under a source of a replayed update: refuse, naming the option, a batch without the live step count -- the mel
+    post-net's batch statistics and convolutions would range over the fixed shape's padding, another model than the reference's,
+    silently -- and, with stats=True, a criterion that logs the sample's host `ntokens` (graph.HOST_VALUES_FREE_T2S lets it differ from
+    batch to batch; a replay would report the captured pass's)."""
+    if not graph:
+        return
+    for i, s in enumerate(micro_batches):
+        if s.get("task_name") != "t2s":
+            continue
+        ni = s.get("net_input")
+        if not isinstance(ni, dict) or ni.get("tgt_live") is None:
+            raise ValueError(f"micro_batches[{i}] (t2s) under a source needs net_input['tgt_live'], the device count of decoder steps "
+                             "collate.TextToSpeechCollater(fixed_shape=...) adds: without it the post-net's BatchNorm statistics and "
+                             "convolutions take in the frames a fixed shape pads with")
+        c = getattr(criterion, "speech_criterion", criterion)
+        if stats and not getattr(c, "device_ntokens", False):
+            raise ValueError(f"micro_batches[{i}] (t2s) under a source with stats=True needs the criterion's device_ntokens=True: with "
+                             "device_ntokens=False the log carries the sample's host `ntokens`, which the batch feed lets differ from "
+                             "batch to batch")
 
 
 class PretrainUpdate:
@@ -445,6 +470,7 @@ class PretrainUpdate:
             raise RuntimeError("set_source() after prepare_graph(): the batch load is the first node of the captured step and this "
                                "graph was captured without it")
         check_s2t_source(self.micro, self.crit, graph=self.use_graph)
+        check_t2s_source(self.micro, self.crit, graph=self.use_graph, stats=self.stats is not None)
         if self.feed is None:
             self.feed = BatchFeed(self.micro, self.device)
         self.feed.set_source(iterable)
@@ -484,6 +510,7 @@ class PretrainUpdate:
                                f"captured pass (updates {self.n + 1} to {self.n + 3}); run eager updates up to the boundary first")
         if self.feed is not None:
             check_s2t_source(self.micro, self.crit)
+            check_t2s_source(self.micro, self.crit, stats=self.stats is not None)
         if self.phased:
             phases, between = self.phase_fns() if self.mode == "in_turn" else self.phase_fns_side_by_side()
             self.sg = StepGraph(None, opt=self.opt, model=self.model, device=self.device, on_step=self.advance,
@@ -494,10 +521,10 @@ class PretrainUpdate:
                                 on_step=self.advance, prefetch_host=self.prefetch_host,
                                 after_fn=self.exchange_and_update if self.split else None, stream=self.stream, feed=self.feed)
         if self.stats is not None and self.feed is not None:
-            from .graph import HOST_VALUES_FREE
+            from .graph import host_values_free
             from .train_stats import check_feed_host_values, device_logged
             names = [s.get("task_name") for s in self.micro]
-            check_feed_host_values(names, HOST_VALUES_FREE, {n: device_logged(n, self.crit) for n in set(names) if device_logged(n, self.crit)})
+            check_feed_host_values(names, host_values_free(), {n: device_logged(n, self.crit) for n in set(names) if device_logged(n, self.crit)})
         self.sg.record()
         self.sg.record()
         self.sg.capture()
