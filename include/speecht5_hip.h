@@ -98,7 +98,9 @@ typedef struct st5_gemm_params {
  * speech_encoder_prenet.py:177; F.conv1d at speech_encoder_prenet.py:300 (layers 1..6) and :107
  * (pos_conv); torch.bmm at multihead_attention.py:340,389; and their autograd backward passes. */
 int st5_gemm(const st5_gemm_params* p, int dtype, void* stream);
-/* 1 (default): plain NT GEMMs use the LDS-DMA pipelined kernel; 0: always the register-staged kernel (A/B testing). */
+/* 1 (default): plain NT GEMMs use the LDS-DMA pipelined kernel; 0: always the register-staged kernel (A/B testing).
+ * The same kernels take B k-strided ("NN": bf16, batch 1, no asum, A not k-strided, B without row split / segments and 16-byte aligned with a
+ * leading dimension that is a multiple of 8, N % 8 == 0, K % 64 == 0, K >= 128) -- same bits as the NT call on a transposed copy of B. */
 /* Stream ordering for the host side (no torch types): everything enqueued on `to` after this call runs after everything
  * enqueued on `from` before it.  Used to run the weight-gradient GEMMs of a backward pass (off the critical path: only the
  * optimizer / gradient all-reduce needs them) on a second stream beside the data-gradient chain. */

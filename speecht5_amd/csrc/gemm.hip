@@ -961,6 +961,10 @@ int nt_feat_of(const st5_gemm_params& p, int c_vec_ok) {
 template <int... FS> struct FeatSet {};
 typedef FeatSet<0, F_GELU | F_PRE, F_DROP | F_RES, F_DACT, F_BETA, F_RES> NtFeats;   // nt_feat_of's hot combinations: the bf16 NT families
 typedef FeatSet<0, F_BETA> TnFeats;                                                  // weight gradients: store or accumulate
+// the B k-major ("NN") forms of the NT families run data gradients only: no forward fc1 epilogue (a launch with it takes the run-time form)
+typedef FeatSet<0, F_DROP | F_RES, F_DACT, F_BETA, F_RES> NnFeats;
+template <bool BNN> struct NtFeatsOf { typedef NtFeats type; };
+template <> struct NtFeatsOf<true> { typedef NnFeats type; };
 template <int... FS, typename Fn>
 int with_feat(const int feat, FeatSet<FS...>, Fn&& fn) {
   int rc = ST5_OK;
@@ -998,6 +1002,53 @@ __device__ __forceinline__ F lds_read128_asm(const unsigned lds_addr) {
   return v;
 }
 
+typedef __attribute__((ext_vector_type(4))) short s16x4;
+typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
+
+// Transpose-read fragment as inline asm.  The builtin form makes hipcc treat the read as a possible alias of the in-flight LDS-DMA
+// writes and put s_waitcnt vmcnt(0) in front of it -- in the 128^2 kernel that serialised a k-tile's fragment reads and MFMAs behind the NEXT
+// tile's DMA (no overlap inside a block), in the phased kernel it drained the DMA queue twice per k-tile (4.5 us per k-tile against
+// 1.8 us for the NT kernel's plain ds_read_b128).  The asm read is invisible to that analysis; the kernels'
+// own vmcnt + barrier order the DMA against it, and their lgkmcnt waits (tied to the fragment registers) sit in front of the MFMAs.
+template <int OFF>
+__device__ __forceinline__ bf16x8 tr_frag_asm(const unsigned lds_addr) {
+  s16x4 lo, hi;
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(lds_addr), "n"(OFF) : "memory");
+  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(lds_addr), "n"(OFF + 1024) : "memory");
+  union { struct { s16x4 a, b; } s; bf16x8 v; } u;
+  u.s.a = lo; u.s.b = hi;
+  return u.v;
+}
+
+// Byte offset, inside a [64 k][128 m] transpose-read tile (gemm_tn_glds_kernel's image: rows of 256 B, 16-byte chunk position XOR
+// 4 * (k & 3)), of this lane's first 8-byte source for the 32-row fragment block starting at mbase: lane group g = m sub-block of 16,
+// h = k half, j = k row inside a 4-row group, q = 4-column step.  + 1024: the second read; + 4096 per 16-deep k-group.
+__device__ __forceinline__ int tr_frag_off(const int lane, const int mbase) {
+  const int g = (lane >> 4) & 1, h = lane >> 5, j = (lane & 15) >> 2, q = lane & 3;
+  const int m = mbase + 16 * g + 4 * q;
+  const int pos = (m >> 3) ^ (4 * j);
+  return (8 * h + j) * 256 + pos * 16 + ((m >> 2) & 1) * 8;
+}
+
+// ------------------------------------------------------------------------------------------------------
+// B k-major ("NN") form of the bf16 NT kernels (template switch BNN): C = epilogue(A . B) with B [K x N] row-major, the data gradient
+// dX = G . W on the weight as the forward reads it -- no transposed copy.  Only the B operand changes: its tile is staged as
+// [64 k][128 n] by LDS-DMA in rows of n and read as MFMA fragments with ds_read_b64_tr_b16, i.e. the image, swizzle and transpose
+// reads of the TN kernels (tr_frag_off / tr_frag_asm), in the 16 KB slot the NT form's [128 n][64 k] tile takes.  A lane receives
+// the same eight k-consecutive values of the same column as from the NT tile of the transposed copy, the k order and the MFMA chain
+// are the NT kernel's: bit-identical results.  Two transpose reads replace one ds_read_b128 (same LDS bytes).
+// A DMA instruction covers 4 k-rows: lane l -> row + (l >> 4), physical chunk l & 15 = logical chunk (l & 15) ^ 4 * (l >> 4).
+// The host admits N % 8 == 0 and K % 64 == 0 only, so a 16-byte chunk is wholly inside or outside the matrix and there is no k
+// tail; chunks past N are clamped onto the last one (as the NT form clamps rows past N: their columns are never stored), which
+// keeps the k-step a scalar.
+// ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ const bf16_t* nn_b_src(const bf16_t* Bp, const long long ldb, const int krow0, const int col0, const int N, const int lane) {
+  const int lrow = lane >> 4;
+  int col = col0 + (((lane & 15) ^ (4 * lrow)) << 3);
+  col = col < N ? col : N - 8;
+  return Bp + (long long)(krow0 + lrow) * ldb + col;
+}
+
 // (cache-policy bits of the operand LDS-DMA loads, an A/B knob: 0 = default, 1 = sc0, 2 = nt, 16 = sc1; tools/r6/build_aux_lib.sh)
 #ifndef GLDS_AUX_A
 #define GLDS_AUX_A 0
@@ -1005,8 +1056,9 @@ __device__ __forceinline__ F lds_read128_asm(const unsigned lds_addr) {
 #ifndef GLDS_AUX_B
 #define GLDS_AUX_B 0
 #endif
-template <typename T, int NBUF, int FEAT = -1>
+template <typename T, int NBUF, int FEAT = -1, bool BNN = false>
 __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gemm_params p, const int c_vec_ok) {
+  static_assert(!BNN || sizeof(T) == 2, "B k-major form: bf16 only");
   if (st5_gate_dropped(p.gate)) return;
   ST5_PAD_TO_256_VGPRS();
 #ifdef GEMM_TIMING
@@ -1040,17 +1092,22 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gem
     const int c = pc ^ ((row >> 1) & 7);
     int gr = m0 + row; gr = gr < p.M ? gr : p.M - 1;
     asrc[i] = Ap + aa.outer(gr) + c * VEC;
-    int gc = n0 + row; gc = gc < p.N ? gc : p.N - 1;
-    bsrc[i] = Bp + ab.outer(gc) + c * VEC;
+    if constexpr (BNN) {
+      bsrc[i] = nn_b_src(Bp, p.B.ld, (i * 4 + wave) * 4, n0, p.N, lane);
+    } else {
+      int gc = n0 + row; gc = gc < p.N ? gc : p.N - 1;
+      bsrc[i] = Bp + ab.outer(gc) + c * VEC;
+    }
   }
   const int dst0 = wave * 1024;  // byte offset of this wave's 8-row slab inside a 4-slab group
+  const long long bkstep = BNN ? (long long)BK * p.B.ld : (long long)BK;   // elements from one k-tile of B to the next
 
   auto issue = [&](int kt, int buf) {
     char* base = dsm + buf * 2 * TILE_BYTES + dst0;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(asrc[i] + (long long)kt * BK), (lds_ptr_t)(base + i * 4096), 16, 0, GLDS_AUX_A);
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[i] + (long long)kt * BK), (lds_ptr_t)(base + TILE_BYTES + i * 4096), 16, 0, GLDS_AUX_B);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[i] + kt * bkstep), (lds_ptr_t)(base + TILE_BYTES + i * 4096), 16, 0, GLDS_AUX_B);
     }
   };
   // (NBUF == 5: five 16 KB operand slots instead of whole stages, see the k-loop)
@@ -1064,7 +1121,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gem
     char* base = dsm + slot * TILE_BYTES + dst0;
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[i] + (long long)kt * BK), (lds_ptr_t)(base + i * 4096), 16, 0, GLDS_AUX_B);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[i] + kt * bkstep), (lds_ptr_t)(base + i * 4096), 16, 0, GLDS_AUX_B);
   };
 
   f32x16 acc00, acc01, acc10, acc11;
@@ -1083,7 +1140,9 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gem
   const int frow = lane & 31, fhalf = lane >> 5;
   const int arow0 = wr * 64 + frow, brow0 = wc * 64 + frow;
   const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)dsm;
-  const unsigned a_addr0 = lds_off(arow0, fhalf), b_addr0 = lds_off(brow0, fhalf);
+  // (BNN: the B fragments of the wave's two 32-column blocks come from two transpose-read addresses)
+  const unsigned a_addr0 = lds_off(arow0, fhalf), b_addr0 = BNN ? tr_frag_off(lane, wc * 64) : lds_off(brow0, fhalf);
+  const unsigned b_addr1 = BNN ? tr_frag_off(lane, wc * 64 + 32) : 0u;
   GPROBE(0);
   // NBUF == 5 ("2.5 stages", 80 KB: two blocks still share a CU): operand tiles go through a ring of five 16 KB slots in the order
   // A(0) B(0) A(1) B(1) A(2) ..., tile number s in slot s % 5.  At the top of k-tile t the tiles 2t, 2t+1, 2t+2 are in flight; the wait
@@ -1121,21 +1180,27 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gem
     // keeps the source order "read, wait for everything, multiply" per group otherwise (and, given both sets, still waits with
     // lgkmcnt(0)) -- one exposed LDS round trip per k-group instead of one per k-tile.  addr(kg) = addr(0) ^ (kg << 5): the swizzle
     // XORs the chunk index, the k-group is bits 1-2 of it.
-    unsigned pa, pb;
+    unsigned pa, pb, pb1 = 0;
     if constexpr (NBUF == 5) {
       const int sb = sa + 1 >= 5 ? 0 : sa + 1;
       pa = lds_base + sa * TILE_BYTES + a_addr0; pb = lds_base + sb * TILE_BYTES + b_addr0;
+      if constexpr (BNN) pb1 = lds_base + sb * TILE_BYTES + b_addr1;
       sa = sa + 2 >= 5 ? sa - 3 : sa + 2;
     } else {
       const unsigned cb = lds_base + (kt % NBUF) * 2 * TILE_BYTES;
       pa = cb + a_addr0; pb = cb + TILE_BYTES + b_addr0;
+      if constexpr (BNN) pb1 = cb + TILE_BYTES + b_addr1;
     }
     frag_t fa0[2], fa1[2], fb0[2], fb1[2];
+    // (BNN: a k-group is 2 + 4 LDS reads instead of 4, so "all but the newest group" is lgkmcnt(6))
 #define NT_READ(S, KG)                                                                                      \
-  fa0[S] = lds_read128_asm<frag_t, 0>(pa ^ ((KG) << 5)); fb0[S] = lds_read128_asm<frag_t, 0>(pb ^ ((KG) << 5));          \
-  fa1[S] = lds_read128_asm<frag_t, 4096>(pa ^ ((KG) << 5)); fb1[S] = lds_read128_asm<frag_t, 4096>(pb ^ ((KG) << 5));
+  fa0[S] = lds_read128_asm<frag_t, 0>(pa ^ ((KG) << 5));                                                    \
+  if constexpr (BNN) fb0[S] = tr_frag_asm<(KG) * 4096>(pb); else fb0[S] = lds_read128_asm<frag_t, 0>(pb ^ ((KG) << 5));   \
+  fa1[S] = lds_read128_asm<frag_t, 4096>(pa ^ ((KG) << 5));                                                 \
+  if constexpr (BNN) fb1[S] = tr_frag_asm<(KG) * 4096>(pb1); else fb1[S] = lds_read128_asm<frag_t, 4096>(pb ^ ((KG) << 5));
 #define NT_WAIT(S, CNT)                                                                                     \
-  asm volatile("s_waitcnt lgkmcnt(" #CNT ")" : "+v"(fa0[S]), "+v"(fa1[S]), "+v"(fb0[S]), "+v"(fb1[S]) :: "memory");
+  if constexpr (BNN && CNT != 0) asm volatile("s_waitcnt lgkmcnt(6)" : "+v"(fa0[S]), "+v"(fa1[S]), "+v"(fb0[S]), "+v"(fb1[S]) :: "memory"); \
+  else asm volatile("s_waitcnt lgkmcnt(" #CNT ")" : "+v"(fa0[S]), "+v"(fa1[S]), "+v"(fb0[S]), "+v"(fb1[S]) :: "memory");
 #if GEMM_ABL == 3
 #define NT_MMA(S) asm volatile("" :: "v"(fa0[S]), "v"(fa1[S]), "v"(fb0[S]), "v"(fb1[S]));
 #else
@@ -1211,7 +1276,7 @@ __global__ __launch_bounds__(NTHREADS, 2) void gemm_nt_glds_kernel(const st5_gem
 // ------------------------------------------------------------------------------------------------------
 constexpr int M64_A_BYTES = 64 * 128, M64_STAGE = M64_A_BYTES + TILE_BYTES;
 
-template <int FEAT>
+template <int FEAT, bool BNN = false>
 __global__ __launch_bounds__(NTHREADS, 3) void gemm_nt_m64_kernel(const st5_gemm_params p, const int c_vec_ok) {
   if (st5_gate_dropped(p.gate)) return;
   typedef bf16_t T;
@@ -1243,10 +1308,15 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_nt_m64_kernel(const st5_gemm
       int gr = m0 + row; gr = gr < p.M ? gr : p.M - 1;
       asrc[i] = Ap + aa.outer(gr) + c * VEC;
     }
-    int gc = n0 + row; gc = gc < p.N ? gc : p.N - 1;
-    bsrc[i] = Bp + ab.outer(gc) + c * VEC;
+    if constexpr (BNN) {
+      bsrc[i] = nn_b_src(Bp, p.B.ld, (i * 4 + wave) * 4, n0, p.N, lane);
+    } else {
+      int gc = n0 + row; gc = gc < p.N ? gc : p.N - 1;
+      bsrc[i] = Bp + ab.outer(gc) + c * VEC;
+    }
   }
   const int dst0 = wave * 1024;
+  const long long bkstep = BNN ? (long long)BK * p.B.ld : (long long)BK;
   auto issue = [&](int kt, int buf) {
     char* base = dsm + buf * M64_STAGE + dst0;
 #pragma unroll
@@ -1254,7 +1324,7 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_nt_m64_kernel(const st5_gemm
       __builtin_amdgcn_global_load_lds((gbl_ptr_t)(asrc[i] + (long long)kt * BK), (lds_ptr_t)(base + i * 4096), 16, 0, 0);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[i] + (long long)kt * BK), (lds_ptr_t)(base + M64_A_BYTES + i * 4096), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(bsrc[i] + kt * bkstep), (lds_ptr_t)(base + M64_A_BYTES + i * 4096), 16, 0, 0);
   };
 
   f32x16 acc0, acc1;
@@ -1265,19 +1335,24 @@ __global__ __launch_bounds__(NTHREADS, 3) void gemm_nt_m64_kernel(const st5_gemm
   issue(0, 0);
   const int frow = lane & 31, fhalf = lane >> 5;
   const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)dsm;
-  const unsigned a_addr0 = lds_off(wr * 32 + frow, fhalf), b_addr0 = M64_A_BYTES + lds_off(wc * 64 + frow, fhalf);
+  const unsigned a_addr0 = lds_off(wr * 32 + frow, fhalf);
+  const unsigned b_addr0 = M64_A_BYTES + (BNN ? tr_frag_off(lane, wc * 64) : lds_off(wc * 64 + frow, fhalf));
+  const unsigned b_addr1 = BNN ? M64_A_BYTES + tr_frag_off(lane, wc * 64 + 32) : 0u;
   for (int kt = 0; kt < nk; ++kt) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // tile kt has landed (this wave's pieces; the barrier publishes everybody's)
     __builtin_amdgcn_s_barrier();
     if (kt + 1 < nk) issue(kt + 1, (kt + 1) & 1);
     const unsigned cb = lds_base + (kt & 1) * M64_STAGE;
-    const unsigned pa = cb + a_addr0, pb = cb + b_addr0;
+    const unsigned pa = cb + a_addr0, pb = cb + b_addr0, pb1 = cb + b_addr1;
     frag_t fa[2], fb0[2], fb1[2];
+    // (BNN: a k-group is 1 + 4 LDS reads instead of 3)
 #define M64_READ(S, KG)                                                                                     \
-  fa[S] = lds_read128_asm<frag_t, 0>(pa ^ ((KG) << 5)); fb0[S] = lds_read128_asm<frag_t, 0>(pb ^ ((KG) << 5));           \
-  fb1[S] = lds_read128_asm<frag_t, 4096>(pb ^ ((KG) << 5));
+  fa[S] = lds_read128_asm<frag_t, 0>(pa ^ ((KG) << 5));                                                     \
+  if constexpr (BNN) { fb0[S] = tr_frag_asm<(KG) * 4096>(pb); fb1[S] = tr_frag_asm<(KG) * 4096>(pb1); }     \
+  else { fb0[S] = lds_read128_asm<frag_t, 0>(pb ^ ((KG) << 5)); fb1[S] = lds_read128_asm<frag_t, 4096>(pb ^ ((KG) << 5)); }
 #define M64_WAIT(S, CNT)                                                                                    \
-  asm volatile("s_waitcnt lgkmcnt(" #CNT ")" : "+v"(fa[S]), "+v"(fb0[S]), "+v"(fb1[S]) :: "memory");
+  if constexpr (BNN && CNT != 0) asm volatile("s_waitcnt lgkmcnt(5)" : "+v"(fa[S]), "+v"(fb0[S]), "+v"(fb1[S]) :: "memory"); \
+  else asm volatile("s_waitcnt lgkmcnt(" #CNT ")" : "+v"(fa[S]), "+v"(fb0[S]), "+v"(fb1[S]) :: "memory");
 #define M64_MMA(S) mma<T>(fa[S], fb0[S], acc0); mma<T>(fa[S], fb1[S], acc1);
     M64_READ(0, 0)
     M64_READ(1, 1)
@@ -1532,7 +1607,7 @@ __global__ __launch_bounds__(NT2) void gemm_nt256_kernel(const st5_gemm_params p
 // (w and w + 4 = the two m-halves): with STAGGER the second half runs one barrier behind, so one wave of every SIMD is in its MFMA
 // section while the other issues reads / DMA, and s_setprio(1) around the MFMA sections has something to arbitrate.
 // ------------------------------------------------------------------------------------------------------
-template <int FEAT, bool STAGGER>
+template <int FEAT, bool STAGGER, bool BNN = false>
 __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p, const int c_vec_ok) {
   if (st5_gate_dropped(p.gate)) return;
   typedef bf16_t T;
@@ -1567,16 +1642,21 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
       for (int h = 0; h < 2; ++h) {
         int gr = m0 + h * 128 + row; gr = gr < p.M ? gr : p.M - 1;
         src[h][i] = Ap + aa.outer(gr) + c * 8;
-        int gc = n0 + h * 128 + row; gc = gc < p.N ? gc : p.N - 1;
-        src[2 + h][i] = Bp + ab.outer(gc) + c * 8;
+        if constexpr (BNN) {   // (B k-major: the half-tile is [64 k][128 n], instruction i covers its k-rows (i * 8 + wave) * 4 .. +3)
+          src[2 + h][i] = nn_b_src(Bp, p.B.ld, (i * 8 + wave) * 4, n0 + h * 128, p.N, lane);
+        } else {
+          int gc = n0 + h * 128 + row; gc = gc < p.N ? gc : p.N - 1;
+          src[2 + h][i] = Bp + ab.outer(gc) + c * 8;
+        }
       }
     }
   }
+  const long long bkstep = BNN ? (long long)BK * p.B.ld : (long long)BK;
   auto stage = [&](const int h, const int kt) {        // half-tile h of k-tile kt -> buffer kt & 1
     char* base = dsm + (kt & 1) * BUF + h * HALF + wave * 1024;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
-      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src[h][i] + (long long)kt * BK), (lds_ptr_t)(base + i * 8192), 16, 0, 0);
+      __builtin_amdgcn_global_load_lds((gbl_ptr_t)(src[h][i] + kt * (h < 2 ? (long long)BK : bkstep)), (lds_ptr_t)(base + i * 8192), 16, 0, 0);
   };
 
   f32x16 acc[4][2];
@@ -1595,6 +1675,10 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
   for (int kg = 0; kg < 4; ++kg) foff[kg] = lds_off(frow, 2 * kg + fhalf);
   const int a_half = wr * HALF;                                    // this wave's A half-tile
   const int b_base = (2 + (wc >> 1)) * HALF + (wc & 1) * 64 * 128; // its 64 B rows inside its B half-tile
+  // (BNN: transpose-read offsets of the wave's two 32-column blocks inside its B half-tile)
+  const int boff0 = BNN ? (2 + (wc >> 1)) * HALF + tr_frag_off(lane, (wc & 1) * 64) : 0;
+  const int boff1 = BNN ? (2 + (wc >> 1)) * HALF + tr_frag_off(lane, (wc & 1) * 64 + 32) : 0;
+  const unsigned lds_base = (unsigned)(size_t)(lds_ptr_t)dsm;
 
   // prologue: all of k-tile 0, the A halves of k-tile 1
   stage(0, 0); stage(1, 0); stage(2, 0); stage(3, 0);
@@ -1607,8 +1691,13 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
   for (int t = 0; t < nk; ++t) {
     const char* cur = dsm + (t & 1) * BUF;
     // ---- phase 1 ----
+    if constexpr (BNN) {
+      const unsigned pb = lds_base + (t & 1) * BUF + boff0;
+      bfr[0] = tr_frag_asm<0>(pb); bfr[1] = tr_frag_asm<4096>(pb); bfr[2] = tr_frag_asm<8192>(pb); bfr[3] = tr_frag_asm<12288>(pb);
+    } else {
 #pragma unroll
-    for (int kg = 0; kg < 4; ++kg) bfr[kg] = *reinterpret_cast<const bf16x8*>(cur + b_base + foff[kg]);
+      for (int kg = 0; kg < 4; ++kg) bfr[kg] = *reinterpret_cast<const bf16x8*>(cur + b_base + foff[kg]);
+    }
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int i = 0; i < 4; ++i)
@@ -1632,8 +1721,13 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
     __builtin_amdgcn_s_setprio(0);
     __builtin_amdgcn_s_barrier();
     // ---- phase 3 ----
+    if constexpr (BNN) {
+      const unsigned pb = lds_base + (t & 1) * BUF + boff1;
+      bfr[0] = tr_frag_asm<0>(pb); bfr[1] = tr_frag_asm<4096>(pb); bfr[2] = tr_frag_asm<8192>(pb); bfr[3] = tr_frag_asm<12288>(pb);
+    } else {
 #pragma unroll
-    for (int kg = 0; kg < 4; ++kg) bfr[kg] = *reinterpret_cast<const bf16x8*>(cur + b_base + 4096 + foff[kg]);
+      for (int kg = 0; kg < 4; ++kg) bfr[kg] = *reinterpret_cast<const bf16x8*>(cur + b_base + 4096 + foff[kg]);
+    }
     if (t + 2 < nk) stage(0, t + 2);
     __builtin_amdgcn_s_barrier();
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -1682,15 +1776,16 @@ __global__ __launch_bounds__(512) void gemm_nt8p_kernel(const st5_gemm_params p,
   run_epilogue<T, FEAT>(ea, stg, acc[2][0], acc[2][1], acc[3][0], acc[3][1], m0 + wr * 128 + 64, n0 + wc * 64, lane);
 }
 
-// (stagger: the two m-halves half a phase apart; st5_gemm_set_nt_tile(4) turns it off)
+// (stagger: the two m-halves half a phase apart; st5_gemm_set_nt_tile(4) turns it off.  BNN: B k-major, see nn_b_src)
+template <bool BNN = false>
 int launch_nt8p(const st5_gemm_params& p, int c_vec_ok, bool stagger, hipStream_t s) {
   const int tiles = ((p.M + 255) / 256) * ((p.N + 255) / 256);
   const dim3 grid(tiles, 1, p.batch), block(512);
   const size_t lds = (size_t)8 * TILE_BYTES;
-  return with_feat(nt_feat_of(p, c_vec_ok), NtFeats(), [&](auto f) -> int {
+  return with_feat(nt_feat_of(p, c_vec_ok), typename NtFeatsOf<BNN>::type(), [&](auto f) -> int {
     constexpr int F = decltype(f)::value;
-    return stagger ? launch_lds<gemm_nt8p_kernel<F, true>>(grid, block, lds, s, p, c_vec_ok)
-                   : launch_lds<gemm_nt8p_kernel<F, false>>(grid, block, lds, s, p, c_vec_ok);
+    return stagger ? launch_lds<gemm_nt8p_kernel<F, true, BNN>>(grid, block, lds, s, p, c_vec_ok)
+                   : launch_lds<gemm_nt8p_kernel<F, false, BNN>>(grid, block, lds, s, p, c_vec_ok);
   });
 }
 
@@ -1711,21 +1806,22 @@ namespace {
 #endif
 
 
-template <typename T, int NBUF>
+template <typename T, int NBUF, bool BNN = false>
 int launch_glds_feat(const st5_gemm_params& p, int c_vec_ok, dim3 grid, hipStream_t s) {
   auto go = [&](auto f) -> int {
-    return launch_lds<gemm_nt_glds_kernel<T, NBUF, decltype(f)::value>>(grid, dim3(NTHREADS), (size_t)(NBUF == 5 ? 5 : NBUF * 2) * TILE_BYTES, s, p, c_vec_ok);
+    return launch_lds<gemm_nt_glds_kernel<T, NBUF, decltype(f)::value, BNN>>(grid, dim3(NTHREADS), (size_t)(NBUF == 5 ? 5 : NBUF * 2) * TILE_BYTES, s, p, c_vec_ok);
   };
   // (bf16: the training step; the fp32 parity mode keeps the one run-time form)
-  if constexpr (sizeof(T) == 2) return with_feat(rt_epilogue_only() ? -1 : nt_feat_of(p, c_vec_ok), NtFeats(), go);
+  if constexpr (sizeof(T) == 2) return with_feat(rt_epilogue_only() ? -1 : nt_feat_of(p, c_vec_ok), typename NtFeatsOf<BNN>::type(), go);
   else return go(std::integral_constant<int, -1>());
 }
 
+template <bool BNN = false>
 int launch_m64(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
   const int tiles = ((p.M + 63) / 64) * ((p.N + BN - 1) / BN);
   const dim3 grid(tiles, 1, p.batch);
-  return with_feat(nt_feat_of(p, c_vec_ok), NtFeats(), [&](auto f) -> int {
-    return launch_lds<gemm_nt_m64_kernel<decltype(f)::value>>(grid, dim3(NTHREADS), (size_t)2 * M64_STAGE, s, p, c_vec_ok);
+  return with_feat(nt_feat_of(p, c_vec_ok), typename NtFeatsOf<BNN>::type(), [&](auto f) -> int {
+    return launch_lds<gemm_nt_m64_kernel<decltype(f)::value, BNN>>(grid, dim3(NTHREADS), (size_t)2 * M64_STAGE, s, p, c_vec_ok);
   });
 }
 // Which NT launches take the half-height tiles: bf16, and at most g_m64_max_tiles tiles of 128^2 (st5_gemm_set_m64_max_tiles; 0 = never)
@@ -1736,18 +1832,18 @@ bool nt_m64_pays(const st5_gemm_params& p) {
   return t128 <= lim && p.M > 64;
 }
 
-template <typename T>
+template <typename T, bool BNN = false>
 int launch_glds(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
   const int tiles = ((p.M + BM - 1) / BM) * ((p.N + BN - 1) / BN);
   dim3 grid(tiles, 1, p.batch);
   const int nk = p.K / (128 / (int)sizeof(T));
   const bool deep = sizeof(T) == 2 && (long long)tiles * p.batch <= g_deep_blocks && nk >= 4 && g_deep_nbuf > 2;
   if constexpr (sizeof(T) == 2) {
-    if (deep && g_deep_nbuf == 4) return launch_glds_feat<T, 4>(p, c_vec_ok, grid, s);
-    if (deep) return launch_glds_feat<T, 3>(p, c_vec_ok, grid, s);
-    if (g_nt_slots5 && nk >= 2) return launch_glds_feat<T, 5>(p, c_vec_ok, grid, s);
+    if (deep && g_deep_nbuf == 4) return launch_glds_feat<T, 4, BNN>(p, c_vec_ok, grid, s);
+    if (deep) return launch_glds_feat<T, 3, BNN>(p, c_vec_ok, grid, s);
+    if (g_nt_slots5 && nk >= 2) return launch_glds_feat<T, 5, BNN>(p, c_vec_ok, grid, s);
   }
-  return launch_glds_feat<T, 2>(p, c_vec_ok, grid, s);
+  return launch_glds_feat<T, 2, BNN>(p, c_vec_ok, grid, s);
 }
 
 // ------------------------------------------------------------------------------------------------------
@@ -1761,28 +1857,10 @@ int launch_glds(const st5_gemm_params& p, int c_vec_ok, hipStream_t s) {
 // 4x4 shuffle per fragment).  Rows past K and columns past M/N read from a zero page.  Split-K as gemm_kernel.
 // ------------------------------------------------------------------------------------------------------
 __device__ __attribute__((aligned(256))) char g_zero_page[256];
-typedef __attribute__((ext_vector_type(4))) short s16x4;
-typedef __attribute__((address_space(3))) s16x4* lds_s16x4_ptr;
-
 __device__ __forceinline__ bf16x8 tr_frag(const char* tile_row, int off0, int off1) {
   // tile_row + off: this lane's 8-byte source for the two 4-row halves of the fragment
   const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile_row + off0));
   const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_s16x4_ptr)(tile_row + off1));
-  union { struct { s16x4 a, b; } s; bf16x8 v; } u;
-  u.s.a = lo; u.s.b = hi;
-  return u.v;
-}
-
-// Transpose-read fragment as inline asm.  The builtin form makes hipcc treat the read as a possible alias of the in-flight LDS-DMA
-// writes and put s_waitcnt vmcnt(0) in front of it -- in the 128^2 kernel that serialised a k-tile's fragment reads and MFMAs behind the NEXT
-// tile's DMA (no overlap inside a block), in the phased kernel it drained the DMA queue twice per k-tile (4.5 us per k-tile against
-// 1.8 us for the NT kernel's plain ds_read_b128).  The asm read is invisible to that analysis; the kernels'
-// own vmcnt + barrier order the DMA against it, and their lgkmcnt waits (tied to the fragment registers) sit in front of the MFMAs.
-template <int OFF>
-__device__ __forceinline__ bf16x8 tr_frag_asm(const unsigned lds_addr) {
-  s16x4 lo, hi;
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(lo) : "v"(lds_addr), "n"(OFF) : "memory");
-  asm volatile("ds_read_b64_tr_b16 %0, %1 offset:%2" : "=v"(hi) : "v"(lds_addr), "n"(OFF + 1024) : "memory");
   union { struct { s16x4 a, b; } s; bf16x8 v; } u;
   u.s.a = lo; u.s.b = hi;
   return u.v;
@@ -2820,6 +2898,18 @@ extern "C" int st5_gemm(const st5_gemm_params* pp, int dtype, void* stream) {
       if (dtype != ST5_BF16) return launch_nt256<float>(p, c_vec_ok, s);
     }
     return dtype == ST5_BF16 ? launch_glds<bf16_t>(p, c_vec_ok, s) : launch_glds<float>(p, c_vec_ok, s);
+  }
+  // The same pipeline with B k-major ("NN": C = A . B, B [K x N] row-major -- the data gradient on the weight as stored, nn_b_src):
+  // bf16, one batch, B a plain matrix of whole 16-byte column chunks, no k tail.  A function of the problem alone; the tile policy is
+  // the NT branch's (the first 256^2 kernel has no such form: st5_gemm_set_nt_tile(2) runs these on 128^2).
+  if (g_use_glds && dtype == ST5_BF16 && p.batch == 1 && !p.asum && (p.flags & ST5_GEMM_B_KSTRIDED) && !(p.flags & ST5_GEMM_A_KSTRIDED) &&
+      !p.A.seg && !p.B.seg && !p.B.rpb && aligned(p.B.ptr, 16) && p.B.ld % 8 == 0 && p.N % 8 == 0 && p.K % 64 == 0 && p.K >= 128)
+  {
+    if (g_nt_tile == 3 || g_nt_tile == 4) return launch_nt8p<true>(p, c_vec_ok, g_nt_tile == 3, s);
+    if (g_nt_tile == 5) return launch_m64<true>(p, c_vec_ok, s);
+    if (g_nt_tile == 0 && nt_m64_pays(p) && !nt256_pays(p.M, p.N, p.K / 64, p.batch)) return launch_m64<true>(p, c_vec_ok, s);
+    if (g_nt_tile == 0 && nt256_pays(p.M, p.N, p.K / 64, p.batch)) return launch_nt8p<true>(p, c_vec_ok, true, s);
+    return launch_glds<bf16_t, true>(p, c_vec_ok, s);
   }
   return launch_general(p, dtype, use8p, c_vec_ok, nsplit, s);
 }

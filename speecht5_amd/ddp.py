@@ -816,15 +816,14 @@ class FusedAdam:
             n = p.numel()
             self.pflat[off:off + n].copy_(p.data.reshape(-1))
             p.data = self.pflat[off:off + n].view_as(p)
-        # bf16 image of the parameters, written by the Adam kernel itself (no per-weight cast launches), plus a pool for
-        # the transposed copies of the >= 2-D ones (refreshed by one batched transpose per step)
+        # bf16 image of the parameters, written by the Adam kernel itself (no per-weight cast launches), plus the size of a pool for
+        # transposed copies of the >= 2-D ones (refreshed by one batched transpose per step; the bf16 update asks for none)
         self.mirror = None
         if dev.type == "cuda" and Fn._S.dtype == torch.bfloat16:
             self.wflat = self.pflat.to(torch.bfloat16)
             Fn.bf16_mirror.attach(self.wflat, ddp.params, offsets)
             cap = sum(p.numel() + 64 for p in ddp.params if p.dim() >= 2)
-            Fn.bf16_mirror.tflat = torch.empty(cap, dtype=torch.bfloat16, device=dev)
-            Fn.bf16_mirror.tcap = cap
+            Fn.bf16_mirror.tcap = cap     # (the pool itself: _Bf16Mirror.transposed, on first use)
             self.mirror = Fn.bf16_mirror
         self.m = torch.zeros_like(self.pflat)
         self.v = torch.zeros_like(self.pflat)

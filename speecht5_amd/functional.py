@@ -400,15 +400,15 @@ def _cast_into(src, dst, transpose=False):
 
 class _Bf16Mirror:
     """bf16 copies of the parameters kept current by the fused optimizer step (ddp.FusedAdam): the Adam kernel writes the
-    updated fp32 master AND its bf16 image in one pass, and every transposed weight copy the data-gradient GEMMs need
-    is refreshed by ONE batched transpose launch per step -- instead of ~300 cast / transpose launches per step.
+    updated fp32 master AND its bf16 image in one pass.  The data-gradient GEMMs read that image in place (_nt_gemm); the
+    transposed weight copies that are still asked for (fused_weight_t) are refreshed by ONE batched transpose launch per step.
     A parameter's image is used only while `p._version` still equals the version recorded at the last refresh."""
 
     def __init__(self):
         if globals().get("fp8_mirror") is not None:
             fp8_mirror.reset()  # (its jobs point into this mirror's pools)
         self.flat = None        # bf16 [total], same element layout as the optimizer's flat fp32 buffer
-        self.tflat = None       # bf16 pool of transposed copies
+        self.tflat = None       # bf16 pool of transposed copies (tcap elements, allocated on first use)
         self.tcap = 0
         self.tused = 0
         self.jobs = {}          # (src_off, rows, cols) -> (dst_off, view [cols, rows])
@@ -482,6 +482,10 @@ class _Bf16Mirror:
         need = (self.tused + n + 63) // 64 * 64
         if need > self.tcap:
             return None   # pool exhausted (sized for every >= 2-D parameter once): caller falls back to the cast path
+        if self.tflat is None:
+            # allocated by the first weight that needs a copy: with the data gradients on the B k-major kernels (DGRAD_NN) the bf16
+            # update needs none
+            self.tflat = torch.empty(self.tcap, dtype=torch.bfloat16, device=self.flat.device)
         view = self.tflat[self.tused:self.tused + n].view(cols, rows)
         self.jobs[key] = (self.tused, view)
         self.tused = need
@@ -548,7 +552,8 @@ def fused_weight(weights, dtype):
 
 def fused_weight_t(weights, dtype):
     """[K, sum N_i] compute-dtype TRANSPOSE of the stacked weights (cached): the B operand of the data-gradient GEMM
-    dX = G . W in K-major form, so that dgrad runs on the same LDS-DMA NT kernel as the forward."""
+    dX = G . W in K-major form, for the data gradients that cannot read the weights in place (_nt_gemm: fp8 images, weights outside the
+    bf16 mirror, the fp32 parity mode, ST5_DGRAD_NN=0)."""
     if dtype == torch.bfloat16:
         hit = bf16_mirror.stacked(weights)
         if hit is not None:
@@ -696,11 +701,25 @@ def _q8_buffers(rows, cols, device):
     return (torch.empty(rows, cols, dtype=torch.uint8, device=device), torch.empty(rows, cols // 32, dtype=torch.uint8, device=device))
 
 
+# A/B switch: 0 = every data gradient reads a transposed copy of its weights (the batched refresh of _Bf16Mirror), as before DESIGN.md 4q
+DGRAD_NN = os.environ.get("ST5_DGRAD_NN", "1") != "0"
+
+
 def _nt_gemm(a2, weights, transposed, C, M, N, K, dtype, quant_out=None, **epi):
     """C = epilogue(a2 . W^T) with W = stacked weights [N, K] (transposed: W = stack^T, the data-gradient form) -- on the MX-fp8
     kernel when the mode is on and the shapes allow, else st5_gemm in the compute dtype.  quant_out = the output TENSOR when its
     consumer is another fp8 GEMM over all N columns (the FFN's hidden activations and their gradients): the epilogue then writes the
     output's fp8 image too."""
+    if transposed and DGRAD_NN and dtype == torch.bfloat16 and N % 8 == 0 and not _fp8_ok(M, N, K, dtype):
+        hit = bf16_mirror.stacked(weights)
+        if hit is not None:
+            # the weights as the forward reads them, [K, N] row-major with the reduction index slow: the NT kernels' B k-major form
+            # (DESIGN.md 4q) -- no transposed copy, no refresh job.  (A reduction that is no multiple of 64 -- the 80-wide mel
+            # projections -- runs on the general kernel from either form; it reads the same matrix k-strided.)
+            W = hit[1]
+            hip.gemm(hip.operand(a2, a2.stride(0)), hip.operand(W, W.shape[1]), C, M, N, K, _dt(dtype),
+                     **dict(epi, flags=epi.get("flags", 0) | hip.B_KSTRIDED))
+            return
     W = fused_weight_t(weights, dtype) if transposed else fused_weight(weights, dtype)
     if _fp8_ok(M, N, K, dtype) and W.is_contiguous() and a2.is_contiguous():
         Wq, Ws = _quant_cached("qt" if transposed else "q", weights, W)

@@ -45,6 +45,24 @@ def nt_cases():
             print(f"   asserted row {M}x{N}x{K}: plain {2*M*N*K/t_plain/1e12:4.0f} TF against hipBLASLt {2*M*N*K/t/1e12:4.0f} TF -- {verdict}", flush=True)
 
 
+def nn_cases():
+    """The data-gradient GEMMs dX = G . W of the update with their epilogues, NT on a transposed copy of W beside the B k-major
+    ("NN") form on W itself; every arm timed twice, the second figure is the tool's own noise."""
+    shapes = [(M, N, K) for M in (8192, 3992, 2504) for (N, K) in ((768, 768), (768, 2304), (768, 1536), (768, 3072), (3072, 768))]
+    for (M, N, K) in shapes:
+        A = torch.randn(M, K, device=dev).to(bf); W = (torch.randn(K, N, device=dev) / K ** 0.5).to(bf); Wt = W.t().contiguous()
+        C = torch.empty(M, N, device=dev, dtype=bf); R = torch.randn(M, N, device=dev).to(bf)
+        oA, oW, oWt, oC, oR = hip.operand(A, K), hip.operand(W, N), hip.operand(Wt, K), hip.operand(C, N), hip.operand(R, N)
+        epis = (("act'", dict(P=oR, act=hip.ACT_GELU, flags=hip.DACT)),) if N == 3072 else (("plain", dict()), ("res", dict(R=oR)))
+        line = f"NN M={M:5d} N={N:5d} K={K:5d}"
+        for name, kw in epis:
+            nt = lambda: hip.gemm(oA, oWt, oC, M, N, K, hip.BF16, **kw)
+            nn = lambda: hip.gemm(oA, oW, oC, M, N, K, hip.BF16, **dict(kw, flags=kw.get("flags", 0) | hip.B_KSTRIDED))
+            t = [timeit(f) * 1e6 for f in (nt, nn, nt, nn)]
+            line += f" | {name}: NT {t[0]:6.1f} {t[2]:6.1f}us  NN {t[1]:6.1f} {t[3]:6.1f}us  NN/NT {(t[1] + t[3]) / (t[0] + t[2]):5.3f}"
+        print(line, flush=True)
+
+
 def tn_cases():
     for (M, N, K) in ((768, 768, 8192), (768, 3072, 8192), (3072, 768, 8192), (2304, 768, 8192), (768, 768, 3992), (768, 3072, 3992),
                       (3072, 768, 3992), (2304, 768, 3992), (768, 768, 2504), (512, 1536, 127992)):
@@ -76,3 +94,5 @@ if __name__ == "__main__":
         nt_cases()
     if which in ("all", "tn"):
         tn_cases()
+    if which in ("all", "nn"):
+        nn_cases()
