@@ -219,8 +219,7 @@ def rebuild_images(opt):
     Fn._cast_into(opt.pflat.view(1, -1), opt.wflat.view(1, -1))
     for p in opt.ddp.params:
         p._st5_mver = p._version
-    opt.mirror.refresh_transposes()
-    Fn.fp8_mirror.refresh()
+    Fn.refresh_weight_images()
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

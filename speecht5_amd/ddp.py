@@ -816,14 +816,12 @@ class FusedAdam:
             n = p.numel()
             self.pflat[off:off + n].copy_(p.data.reshape(-1))
             p.data = self.pflat[off:off + n].view_as(p)
-        # bf16 image of the parameters, written by the Adam kernel itself (no per-weight cast launches), plus the size of a pool for
+        # bf16 image of the parameters, written by the Adam kernel itself (no per-weight cast launches); the mirror sizes a pool for
         # transposed copies of the >= 2-D ones (refreshed by one batched transpose per step; the bf16 update asks for none)
         self.mirror = None
         if dev.type == "cuda" and Fn._S.dtype == torch.bfloat16:
             self.wflat = self.pflat.to(torch.bfloat16)
             Fn.bf16_mirror.attach(self.wflat, ddp.params, offsets)
-            cap = sum(p.numel() + 64 for p in ddp.params if p.dim() >= 2)
-            Fn.bf16_mirror.tcap = cap     # (the pool itself: _Bf16Mirror.transposed, on first use)
             self.mirror = Fn.bf16_mirror
         self.m = torch.zeros_like(self.pflat)
         self.v = torch.zeros_like(self.pflat)
@@ -948,12 +946,4 @@ class FusedAdam:
         if self.mirror is not None:
             for p in self.ddp.params:
                 p._st5_mver = p._version
-            if os.environ.get("ST5_LAZY_TRANSPOSES") == "1":
-                # (A/B, round 6: leave the refresh to the first data-gradient GEMM of the next update -- off the serial tail, onto the
-                #  shorter micro-batch chain.  Measured: 30.5 against 30.15 ms per update, same box, alternating: the one extra
-                #  cross-stream event inside the replayed graph costs more than the 0.24 ms it moves.  Off.)
-                self.mirror.mark_stale()
-                Fn.fp8_mirror.off = True
-            else:
-                self.mirror.refresh_transposes()
-                Fn.fp8_mirror.refresh()     # (fp8 mode: every weight's e4m3 image + block scales in one launch; no-op otherwise)
+            Fn.refresh_weight_images()      # (one launch each for the transposed copies and the fp8 images; none without jobs)

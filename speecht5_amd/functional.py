@@ -13,6 +13,7 @@ import math
 from types import SimpleNamespace
 
 import os
+import struct
 import threading
 
 import torch
@@ -350,6 +351,24 @@ def _dt(t):
 # -------------------------------------------------------------------------------------------------
 # parameter handling: compute-dtype weight cache + direct gradient accumulation
 # -------------------------------------------------------------------------------------------------
+class _FirstUse:
+    """Something was just produced on the current stream (a cached weight form, a transposed copy, an fp8 image): the event behind
+    it and the raw stream.  wait() orders a reader on ANOTHER stream behind it, once per stream -- the two micro-batches of an update
+    run side by side on two streams, and the second must not read what the first one's kernel has not written yet."""
+
+    def __init__(self):
+        self.event = torch.cuda.Event()
+        self.event.record()
+        self.stream = hip.stream()
+        self.waited = set()
+
+    def wait(self):
+        cur = hip.stream()
+        if cur != self.stream and cur not in self.waited:
+            torch.cuda.current_stream().wait_event(self.event)
+            self.waited.add(cur)
+
+
 class _WeightCache:
     """Compute-dtype (optionally fused / re-laid-out) copies of fp32 parameters, rebuilt when any
     source parameter changes (torch's in-place version counter)."""
@@ -360,19 +379,12 @@ class _WeightCache:
     def get(self, key, params, build):
         ver = tuple((p.data_ptr(), p._version) for p in params)
         hit = self.store.get(key)
-        cur = hip.stream() if params and params[0].is_cuda else None
         if hit is not None and hit[0] == ver:
-            if hit[2] is not None and cur != hit[3] and cur not in hit[4]:
-                # built on another stream (two micro-batches forward side by side): this stream waits for the build once
-                torch.cuda.current_stream().wait_event(hit[2])
-                hit[4].add(cur)
+            if hit[2] is not None:
+                hit[2].wait()
             return hit[1]
         val = build()
-        ev = None
-        if cur is not None:
-            ev = torch.cuda.Event()
-            ev.record()
-        self.store[key] = (ver, val, ev, cur, set())
+        self.store[key] = (ver, val, _FirstUse() if params and params[0].is_cuda else None)
         return val
 
     def clear(self):
@@ -398,35 +410,105 @@ def _cast_into(src, dst, transpose=False):
                                           _dt(dst), hip.stream()), "st5_cast_from_f32")
 
 
+_TABLE_FLOOR = 256      # records in a job table's first device buffer
+
+
+def _capturing(device):
+    """Is the current stream of `device` being captured into a graph?  (Asked for CUDA devices only: without a GPU the query raises.)"""
+    return device.type == "cuda" and torch.cuda.is_current_stream_capturing()
+
+
+def _table_copy(dst, src):
+    """Every host -> device copy of a job table goes through here."""
+    dst.copy_(src)
+
+
+class _JobTable:
+    """Device array of the fixed-size job records of a batched launch (st5_multi_transpose_bf16, st5_multi_quant_mxfp8), under the rule of
+    csrc/stream_scratch.h and hip.workspace: a captured graph replays the launch with the (address, njobs, units) it was captured
+    with, so nothing such a launch can read ever changes.
+
+    Records are immutable once appended: neither their bytes nor their order change, a later append only adds a suffix.  A record's
+    start unit (the kernels binary-search on it) is the running total of the units before it, so it is monotone by construction.
+    The device buffer only grows, to max(need, 2 x old, _TABLE_FLOOR records); growth uploads the whole image into the new buffer and
+    keeps the old one on `retired` for the life of the table, never written again.  Without growth an upload writes the appended
+    suffix in place.  Either way a queued or captured launch with a frozen (address, njobs, units) reads a prefix of a buffer this
+    table still holds, and no upload changes a byte of that prefix: it keeps refreshing exactly the jobs it knew.
+
+    append() and a pending upload() raise RuntimeError while the current stream is capturing, before they change, allocate or launch
+    anything: first use and growth happen outside capture."""
+
+    def __init__(self, name, device, record):
+        self.name, self.device = name, device
+        self.nbytes = struct.calcsize(record)   # of one record (`record`: its struct format)
+        self.host = bytearray()     # every record appended so far
+        self.units = 0              # their units in total = the next record's start unit
+        self.dev = None             # uint8 device buffer
+        self.retired = []           # outgrown device buffers
+        self.args = None            # (address, njobs, units) as of the last upload
+
+    def __len__(self):
+        return len(self.host) // self.nbytes
+
+    def refuse_capture(self, what, key=None):
+        if _capturing(self.device):
+            raise RuntimeError(f"job table '{self.name}': {what}{'' if key is None else f' of {key}'} while the stream is capturing -- register "
+                               "and refresh every weight image in an eager step before the capture")
+
+    def append(self, pack, units, key=None):
+        """One more record: pack(start unit) -> its bytes; `units` = the tiles / blocks of the launch's grid it takes."""
+        self.refuse_capture("append", key)
+        rec = pack(self.units)
+        assert len(rec) == self.nbytes and units > 0
+        self.host += rec
+        self.units += units
+
+    def upload(self):
+        """Bring the device buffer up to the host image; nothing is copied when nothing was appended since the last upload."""
+        done = self.args[1] if self.args is not None else 0
+        if done == len(self):
+            return
+        self.refuse_capture(f"upload of records {done}..{len(self) - 1}")
+        if self.dev is None or self.dev.numel() < len(self.host):
+            old = 0
+            if self.dev is not None:
+                self.retired.append(self.dev)
+                old = self.dev.numel()
+            self.dev = torch.empty(max(len(self.host), 2 * old, _TABLE_FLOOR * self.nbytes), dtype=torch.uint8, device=self.device)
+            done = 0
+        a = done * self.nbytes
+        _table_copy(self.dev[a:len(self.host)], torch.frombuffer(bytearray(self.host[a:]), dtype=torch.uint8))
+        self.args = (self.dev.data_ptr(), len(self), self.units)
+
+    def launch_args(self):
+        """(device address, njobs, units) of the last upload."""
+        return self.args
+
+
 class _Bf16Mirror:
     """bf16 copies of the parameters kept current by the fused optimizer step (ddp.FusedAdam): the Adam kernel writes the
     updated fp32 master AND its bf16 image in one pass.  The data-gradient GEMMs read that image in place (_nt_gemm); the
     transposed weight copies that are still asked for (fused_weight_t) are refreshed by ONE batched transpose launch per step.
     A parameter's image is used only while `p._version` still equals the version recorded at the last refresh."""
 
-    def __init__(self):
-        if globals().get("fp8_mirror") is not None:
-            fp8_mirror.reset()  # (its jobs point into this mirror's pools)
-        self.flat = None        # bf16 [total], same element layout as the optimizer's flat fp32 buffer
+    JOB = "<qqiiii"     # TrJob of csrc/optim.hip: src and dst element offsets, rows, cols, first 64 x 64 tile, pad
+
+    def __init__(self, flat=None):
+        """Without `flat`: detached from everything."""
+        device = flat.device if flat is not None else None
+        fp8_mirror.reset(device)   # (its jobs point into this mirror's pools)
+        self.flat = flat        # bf16 [total], same element layout as the optimizer's flat fp32 buffer
         self.tflat = None       # bf16 pool of transposed copies (tcap elements, allocated on first use)
         self.tcap = 0
         self.tused = 0
-        self.jobs = {}          # (src_off, rows, cols) -> (dst_off, view [cols, rows])
-        self.first = {}         # key -> (event, stream) of a copy produced by a first-use transpose since the last batched refresh
-        self.jobs_dev = None
-        self.ntiles = 0
-        self.dirty = False      # job table changed since it was last uploaded
-        # Round 6, an A/B mode (ddp.FusedAdam, ST5_LAZY_TRANSPOSES=1; measured slower, off): the batched refresh can be LAZY.  Only the
-        # data-gradient GEMMs read the transposed copies, i.e. nothing before the first backward of the NEXT update -- the optimizer step
-        # then only marks them stale (mark_stale) and the first reader refreshes them, on its stream, at the head of that update's
-        # backward.  A reader on another stream waits for that refresh's event once.
-        self.stale = False
-        self.refreshed = None   # (event, raw stream) of the last lazy refresh
-        self.waited = set()     # raw streams already ordered behind it
+        self.jobs = {}          # (src_off, rows, cols) -> (dst_off, view [cols, rows]), in the order of the table's records
+        self.first = {}         # key -> _FirstUse of a copy produced by a first-use transpose since the last batched refresh
+        self.table = _JobTable("transposed copies", device, self.JOB)
 
     def attach(self, flat_bf16, params, offsets):
-        self.__init__()
-        self.flat = flat_bf16
+        self.__init__(flat_bf16)
+        # room for one transposed copy of every >= 2-D parameter (each copy starts on a multiple of 64 elements)
+        self.tcap = sum(p.numel() + 64 for p in params if p.dim() >= 2)
         for p, off in zip(params, offsets):
             p._st5_moff = off
             p._st5_mver = p._version
@@ -450,79 +532,50 @@ class _Bf16Mirror:
             return None
         return off, self.flat[off:nxt].view(-1, K)
 
-    def mark_stale(self):
-        """The parameters (and their bf16 image) changed: every transposed copy is out of date until the next reader refreshes them."""
-        self.stale = True
-
-    def _sync_transposes(self):
-        if self.stale:
-            self.stale = False
-            self.refresh_transposes()
-            ev = torch.cuda.Event()
-            ev.record()
-            self.refreshed, self.waited = (ev, hip.stream()), {hip.stream()}
-        elif self.refreshed is not None and hip.stream() not in self.waited:
-            torch.cuda.current_stream().wait_event(self.refreshed[0])
-            self.waited.add(hip.stream())
-
     def transposed(self, off, rows, cols):
-        self._sync_transposes()
         key = (off, rows, cols)
         hit = self.jobs.get(key)
         if hit is not None:
-            ev = self.first.get(key)
-            if ev is not None and ev[1] != hip.stream():
+            if key in self.first:
                 # produced by a single-job transpose on ANOTHER stream earlier in this very step (the two micro-batches of an
                 # update backward side by side: the second stream's data-gradient GEMM must not read the copy before the first
                 # stream's transpose kernel has written it); from the next optimizer step on the batched refresh produces
                 # every copy on the main stream before the streams fork
-                torch.cuda.current_stream().wait_event(ev[0])
+                self.first[key].wait()
             return hit[1]
         n = rows * cols
         need = (self.tused + n + 63) // 64 * 64
         if need > self.tcap:
             return None   # pool exhausted (sized for every >= 2-D parameter once): caller falls back to the cast path
+        doff = self.tused
+        self.table.append(lambda tile0: struct.pack(self.JOB, off, doff, rows, cols, tile0, 0),
+                          ((rows + 63) // 64) * ((cols + 63) // 64), key)
         if self.tflat is None:
             # allocated by the first weight that needs a copy: with the data gradients on the B k-major kernels (DGRAD_NN) the bf16
             # update needs none
             self.tflat = torch.empty(self.tcap, dtype=torch.bfloat16, device=self.flat.device)
-        view = self.tflat[self.tused:self.tused + n].view(cols, rows)
-        self.jobs[key] = (self.tused, view)
+        view = self.tflat[doff:doff + n].view(cols, rows)
+        self.jobs[key] = (doff, view)
         self.tused = need
-        self.dirty = True
         # first use: produce this copy now (the batched refresh only runs after optimizer steps)
         _cast_free_transpose(self.flat[off:off + n].view(rows, cols), view)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.first[key] = (ev, hip.stream())
+        self.first[key] = _FirstUse()
         return view
 
     def refresh_transposes(self):
         self.first = {}         # (the caller -- the optimizer step -- runs after the micro-batch streams have joined)
         if not self.jobs:
             return
-        if self.dirty or self.jobs_dev is None:
-            import struct
-            recs, tile0 = [], 0
-            for (off, rows, cols), (doff, _v) in self.jobs.items():
-                recs.append(struct.pack("<qqiiii", off, doff, rows, cols, tile0, 0))
-                tile0 += ((rows + 63) // 64) * ((cols + 63) // 64)
-            self.ntiles = tile0
-            raw = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8)
-            self.jobs_dev = raw.to(self.flat.device)
-            self.dirty = False
-        hip.check(hip.lib().st5_multi_transpose_bf16(self.flat.data_ptr(), self.tflat.data_ptr(), self.jobs_dev.data_ptr(),
-                                                     len(self.jobs), self.ntiles, hip.stream()), "st5_multi_transpose_bf16")
-
-
-bf16_mirror = _Bf16Mirror()
+        self.table.upload()
+        jobs_dev, njobs, ntiles = self.table.launch_args()
+        hip.check(hip.lib().st5_multi_transpose_bf16(self.flat.data_ptr(), self.tflat.data_ptr(), jobs_dev, njobs, ntiles, hip.stream()),
+                  "st5_multi_transpose_bf16")
 
 
 def _cast_free_transpose(src_bf16, dst_bf16):
     """dst [cols, rows] <- src [rows, cols]^T for one bf16 matrix (single-job batched transpose)."""
-    import struct
     rows, cols = src_bf16.shape
-    rec = struct.pack("<qqiiii", 0, 0, rows, cols, 0, 0)
+    rec = struct.pack(_Bf16Mirror.JOB, 0, 0, rows, cols, 0, 0)
     job = torch.frombuffer(bytearray(rec), dtype=torch.uint8).to(src_bf16.device)
     hip.check(hip.lib().st5_multi_transpose_bf16(src_bf16.data_ptr(), dst_bf16.data_ptr(), job.data_ptr(), 1,
                                                  ((rows + 63) // 64) * ((cols + 63) // 64), hip.stream()), "st5_multi_transpose_bf16")
@@ -612,20 +665,19 @@ class _Fp8Mirror:
     inside the replayed graph).  Only matrices that live in the bf16 mirror's two pools (stable addresses, refreshed by the optimizer
     step) are registered; everything else keeps the per-step cache."""
 
-    def __init__(self):
-        self.reset()
+    JOB = "<QQQqii"     # QuantJob of csrc/gemm.hip: addresses of source, e4m3 bytes and scales, elements, cols, first block of 2048 elements
 
-    def reset(self):
-        self.jobs = {}          # (address, rows, cols) -> (source view, q, scales)
-        self.first = {}         # key -> (event, raw stream) of an image produced by a first-use launch since the last batched refresh
-        self.jobs_dev = None
-        self.nblocks = 0
-        self.dirty = False
-        self.off = False        # (set when the optimizer step does not refresh: lazy-transpose A/B mode)
+    def __init__(self):
+        self.reset(None)
+
+    def reset(self, device):
+        self.jobs = {}          # (address, rows, cols) -> (source view, q, scales), in the order of the table's records
+        self.first = {}         # key -> _FirstUse of an image produced by a first-use launch since the last batched refresh
+        self.table = _JobTable("fp8 images", device, self.JOB)
 
     def quantised(self, W):
         m = bf16_mirror
-        if self.off or m.flat is None or m.stale or not W.is_cuda or W.dtype != torch.bfloat16:
+        if m.flat is None or not W.is_cuda or W.dtype != torch.bfloat16:
             return None
         st = W.untyped_storage().data_ptr()
         if st != m.flat.untyped_storage().data_ptr() and (m.tflat is None or st != m.tflat.untyped_storage().data_ptr()):
@@ -635,42 +687,40 @@ class _Fp8Mirror:
         key = (W.data_ptr(), W.shape[0], W.shape[1])
         hit = self.jobs.get(key)
         if hit is not None:
-            ev = self.first.get(key)
-            if ev is not None and ev[1] != hip.stream():
+            if key in self.first:
                 # produced on ANOTHER stream earlier in this very update (first use, before any batched refresh has covered it)
-                torch.cuda.current_stream().wait_event(ev[0])
+                self.first[key].wait()
             return hit[1], hit[2]
+        self.table.refuse_capture("append", key)    # (before the images below are allocated and written)
         q, sc = hip.quant_mxfp8(W)
-        ev = torch.cuda.Event()
-        ev.record()
-        self.first[key] = (ev, hip.stream())
+        self.first[key] = _FirstUse()
         self.jobs[key] = (W, q, sc)
-        self.dirty = True
+        n = W.numel()
+        self.table.append(lambda blk0: struct.pack(self.JOB, W.data_ptr(), q.data_ptr(), sc.data_ptr(), n, W.shape[1], blk0),
+                          (n + 2047) // 2048, key)
         return q, sc
 
     def refresh(self):
         """Re-quantise every registered matrix from its (just refreshed) bf16 source: one launch, on the optimizer's stream."""
         self.first = {}
-        if self.off or not self.jobs or not _FP8.enabled:
-            if self.jobs and not _FP8.enabled:
-                self.reset()    # (mode switched off: the images would go stale)
+        if not self.jobs or not _FP8.enabled:
+            if self.jobs:
+                self.reset(self.table.device)   # (mode switched off: the images would go stale)
             return
-        if self.dirty or self.jobs_dev is None:
-            import struct
-            recs, blk0 = [], 0
-            for (W, q, sc) in self.jobs.values():
-                n = W.numel()
-                recs.append(struct.pack("<QQQqii", W.data_ptr(), q.data_ptr(), sc.data_ptr(), n, W.shape[1], blk0))
-                blk0 += (n + 2047) // 2048
-            self.nblocks = blk0
-            dev = next(iter(self.jobs.values()))[0].device
-            self.jobs_dev = torch.frombuffer(bytearray(b"".join(recs)), dtype=torch.uint8).to(dev)
-            self.dirty = False
-        hip.check(hip.lib().st5_multi_quant_mxfp8(self.jobs_dev.data_ptr(), len(self.jobs), self.nblocks, hip.stream()),
-                  "st5_multi_quant_mxfp8")
+        self.table.upload()
+        jobs_dev, njobs, nblocks = self.table.launch_args()
+        hip.check(hip.lib().st5_multi_quant_mxfp8(jobs_dev, njobs, nblocks, hip.stream()), "st5_multi_quant_mxfp8")
 
 
 fp8_mirror = _Fp8Mirror()
+bf16_mirror = _Bf16Mirror()
+
+
+def refresh_weight_images():
+    """What an optimizer step owes the images derived from the bf16 mirror: the batched transpose, then the batched quantisation
+    (whose data-gradient sources are the transposed copies).  Each launches nothing when it has no job."""
+    bf16_mirror.refresh_transposes()
+    fp8_mirror.refresh()
 
 
 # fp8 images made by a PRODUCER (round 6): the LayerNorm forward of a pre-LN layer, the fc1 GEMM's GELU epilogue and the data gradient

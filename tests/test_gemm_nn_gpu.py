@@ -211,7 +211,6 @@ def _mirror_backward(cuda, nn_on, monkeypatch):
     monkeypatch.setattr(Fn, "DGRAD_NN", nn_on)
     Fn.weight_cache.clear()
     Fn.bf16_mirror.attach(flat, list(params.values()), offsets)
-    Fn.bf16_mirror.tcap = off + 64 * len(shapes)
     P = params
     y = Fn.linear(x, [P["wa"], P["wb"]], [P["ba"], P["bb"]])                       # [2, T, 128]: the stacked pair, K = 128 = N
     y = Fn.ffn(y, y, SimpleNamespace(weight=P["w1"], bias=P["b1"]), SimpleNamespace(weight=P["w2"], bias=P["b2"]))
