@@ -340,8 +340,15 @@ __device__ __forceinline__ void epilogue_rows(const EpiArgs& ea, const float* st
       }
       if (ea.dropout_p > 0.f) {
         const unsigned long long ctr = ea.ctr_base + (unsigned long long)gm * (unsigned long long)ea.N + gn;
-        float dsc[8];  // ctr is a multiple of 8 (N % 8 == 0, gn % 8 == 0)
-        dropout_scale8(ea.seed, ctr, thresh, inv_keep, dsc);
+        // This layout is also the one of N % 8 != 0, where a row's first counter gm * N is not a multiple of 8: dropout_scale8 takes the
+        // pair parity and the 64-element block from an aligned counter, so an unaligned 8-vector evaluates the rule element by element
+        // (same bits at aligned counters; this layout's cost does not matter).
+        float dsc[8];
+        if ((ctr & 7ull) == 0) dropout_scale8(ea.seed, ctr, thresh, inv_keep, dsc);
+        else {
+#pragma unroll
+          for (int e = 0; e < 8; ++e) dsc[e] = dropout_scale(ea.seed, ctr + (unsigned long long)e, thresh, inv_keep);
+        }
 #pragma unroll
         for (int e = 0; e < 8; ++e) v[e] *= dsc[e];
       }

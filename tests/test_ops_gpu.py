@@ -5,6 +5,7 @@ bf16 mode is compared with the same math evaluated on bf16-rounded inputs, toler
 output scale (bf16 has 8 mantissa bits; accumulation is fp32)."""
 import math
 
+import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
@@ -13,6 +14,7 @@ pytestmark = pytest.mark.gpu
 
 from speecht5_amd import hip  # noqa: E402
 from speecht5_amd import functional as Fn  # noqa: E402
+from tests.attention_reference import keep_mask_flat  # noqa: E402
 
 DTYPES = [torch.float32, torch.bfloat16]
 
@@ -197,14 +199,18 @@ def test_gemm_dact_and_dropout(cuda, dtype):
         hip.gemm(hip.operand(A, K), hip.operand(W, K), hip.operand(out, N), M, N, K, hip.dt(dtype), dropout_p=0.25, seed=seed)
     assert torch.equal(C1, C2) and not torch.equal(C1, C3)
     full = rt(a, dtype) @ rt(w, dtype).t()
-    keep = (C1 != 0).float().cpu()
+    # the kept set is the header's rule (element counter = row * N + col) restated in tests/attention_reference.py, not what came out
+    keep_b = torch.from_numpy(keep_mask_flat(7, 0.25, np.arange(M * N, dtype=np.uint64).reshape(M, N)))
+    keep = keep_b.float()
     assert abs(keep.mean().item() - 0.75) < 0.03
+    assert full.abs().min().item() > 0 and torch.equal((C1 != 0).cpu(), keep_b), "the epilogue's mask is not the counter rule's"
     close(C1.float().cpu(), full * keep / 0.75, dtype, what="dropout survivors")
-    # the standalone dropout kernel uses the same generator/counter as the epilogue
+    # the standalone dropout kernel uses the same generator/counter as the epilogue: the same mask, bit for bit
     Y = torch.zeros(M, N, dtype=dtype, device=cuda)
     Fd = dev(full, dtype, cuda)
+    assert Fd.float().abs().min().item() > 0
     hip.check(hip.lib().st5_dropout(Fd.data_ptr(), Y.data_ptr(), M * N, 0.25, 7, hip.dt(dtype), hip.stream()), "dropout")
-    assert torch.equal((Y != 0), (C1 != 0)) or ((Y != 0) ^ (C1 != 0)).float().mean().item() < 1e-3
+    assert torch.equal((Y != 0).cpu(), keep_b) and torch.equal((Y != 0), (C1 != 0))
 
 
 @pytest.mark.parametrize("dtype", [torch.float32, torch.bfloat16])
