@@ -873,6 +873,40 @@ int st5_beam_step_logprobs(const float* lp, int64_t ld, float* lprobs_out, int64
                            int32_t* sent_done, int32_t* n_finished, uint32_t* ticket, int32_t* counter, const uint8_t* never,
                            const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty, int32_t min_len, int32_t max_len,
                            void* stream);
+/* ---- the beam step PER SENTENCE (csrc/beam_step.hip, index arithmetic in csrc/beam_stream_index.h): the step of a beam-search stream
+ * (SequenceGenerator.generate_stream, speecht5_amd/beam_stream.py), in which n_slots sentence slots of `beam` rows each are stepped by
+ * one launch sequence and a slot whose sentence has finished is handed to the next waiting request between two groups of steps.
+ * State, beside tok / score / anc / ignore / parent / the records of st5_beam_step (rows = n_slots * beam, Tmax >= cap + 2 columns,
+ * rec_ld >= cap + 1, cap = the largest step limit):
+ *   pos int32 [n_slots]: steps done by the slot's occupant;  maxlen int32 [n_slots]: its step limit (clamped into [0, cap] wherever it
+ *   is read);  done int32 [n_slots]: 1 = finished or idle;  moved int32 [n_slots]: 1 = the last step advanced the slot;
+ *   pos_rows int32 [rows]: pos_rows[r] = pos[r / beam], what st5_gemm_skinny_rows and st5_lm_decode_attn_rows take.
+ *   There is no counter, no ticket and no n_finished: no workgroup reads another slot's pos, so the hand-off between two launches is
+ *   the kernel boundary.  len_div is one fp32 table over 0 .. cap.
+ * st5_beam_step_sents: workgroup s runs st5_beam_step's stages (the same kernel body, selection and tie rule) for step = pos[s] and
+ *   max_len = maxlen[s].  A slot with done[s] != 0 (or pos[s] outside 0 .. maxlen[s]) writes moved[s] = 0 and nothing else, before any
+ *   load of logits.  Otherwise, behind the stages: pos[s] = step + 1, the slot's pos_rows, moved[s] = 1; done[s] = 1 at `beam`
+ *   hypotheses or at step == maxlen[s].
+ * st5_beam_reorder_sents, launched behind it: st5_beam_reorder_dev for t = pos[s], only where moved[s] != 0.
+ * st5_beam_embed_sents: st5_beam_embed_step at position pos[r / beam] + pos_off for row r; y holds n_slots * beam rows.
+ * st5_beam_sents_admit: one launch for n_admit slots; desc int32 [n_admit][4] in device memory = (slot, max_len, frames, bos).  For the
+ *   slot's rows: anc = identity over all Tmax columns, tok[r][0] = bos, score[r][0] = 0, ignore = 0, rec_len = 0; n_hyp[slot] = 0;
+ *   pos = 0, pos_rows = 0, maxlen = clamp(max_len, 0, cap), done = 0; kpm uint8 [n_slots][S]: byte j of the slot = (j >= clamp(frames,
+ *   0, S)).  A slot outside [0, n_slots) admits nothing; nothing of another slot is written (moved is left alone). */
+int st5_beam_step_sents(const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_slots, int32_t beam, int32_t V,
+                        float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax, uint8_t* ignore,
+                        int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score, int32_t* rec_len,
+                        int32_t* n_hyp, int32_t* pos, const int32_t* maxlen, int32_t* done, int32_t* moved, int32_t* pos_rows,
+                        const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                        int32_t min_len, int32_t cap, void* stream);
+int st5_beam_reorder_sents(int32_t* anc, int64_t anc_ld, const int32_t* parent, int32_t n_slots, int32_t beam, int32_t Tmax,
+                           const int32_t* pos, const int32_t* maxlen, const int32_t* moved, int32_t cap, void* stream);
+int st5_beam_embed_sents(const float* table, int32_t V, const int32_t* tok, int32_t Tmax, const int32_t* spos, int32_t n_slots, int32_t beam,
+                         const float* pos, int32_t pos_rows, int32_t pos_off, float emb_scale, void* y, int64_t y_ld, int32_t cols, int dtype,
+                         void* stream);
+int st5_beam_sents_admit(const int32_t* desc, int32_t n_admit, int32_t n_slots, int32_t beam, int32_t cap, int32_t Tmax, int32_t* tok,
+                         float* score, int32_t* anc, int64_t anc_ld, uint8_t* ignore, int32_t* n_hyp, int32_t* rec_len, int32_t* pos,
+                         int32_t* pos_rows, int32_t* maxlen, int32_t* done, uint8_t* kpm, int32_t S, void* stream);
 /* ---- joint CTC / attention scoring in the device-stepped beam search (csrc/beam_ctc.hip): the rows form of the CTC prefix scorer
  * behind the step counter of st5_beam_step.  rows = S * beam, row r belongs to sentence r / beam; x [S][Tfr][V], lens [S] as for
  * st5_ctc_prefix_score_rows; tok [rows][tok_ld] int32 is st5_beam_step's; nc candidates per row, nc <= 1024.  Buffers: state

@@ -1,0 +1,372 @@
+"""Streaming ASR / ST beam search: SequenceGenerator.generate_stream.  A fixed set of `sentences` slots of `beam` hypothesis rows each
+is stepped by ONE step program (step_program.py), enqueued kernel by kernel ("device") or captured once and replayed until the stream
+ends ("graph"); a slot whose sentence has finished is handed to the next waiting request at a poll.  generate(decode="device" /
+"graph") keeps every sentence of a call in the batch until the last one has finished (beam_graph.py), so a call costs max(steps) per
+sentence; the stream costs mean(steps), as the synthesis stream does for TTS (tts_stream.py).  Attention-only search: ctc_weight = 0,
+no LM (the ST recipe and ASR decoding without CTC).
+
+What makes it possible is that every position-dependent launch of the step reads the position of the SLOT where beam_graph's step
+reads one counter: the pre-net row (st5_beam_embed_sents), the self-attention K|V slot write (st5_gemm_skinny_rows over pos_rows), the
+self-attention (st5_lm_decode_attn_rows), the beam step (st5_beam_step_sents: step = pos[s], max_len = maxlen[s] per workgroup) and
+the ancestry reorder (st5_beam_reorder_sents).  st5_beam_cross_attn has no step dependence and is launched as it is.  There is no
+global counter, no arrival ticket and no finished-sentence count: a slot's position is read and written by its own workgroup only,
+so the hand-off between two launches is the kernel boundary.  A slot that is done (finished or idle) costs what a live one costs in
+every launch but the beam step and the reorder, which return at once for it: the GEMMs stream every weight once whatever the rows.
+
+The captured graph never changes.  An admission rewrites only the DATA the graph reads, between two groups of steps, when nothing of
+the step is in flight: one st5_beam_sents_admit launch (the slot's beam-step state, its record header, its key-padding bytes), the
+K|V projection of the sentence's encoder rows into the slot's slice of every layer's encoder-side buffer, and a zero fill of the
+slice behind the sentence's frames.  The projection runs in the shape it has in a generate() call on that sentence alone (its own
+frames as rows, all layers in one GEMM), so the K|V bits are that call's.
+
+Order of work at a poll, all on the one decode stream:
+  1. the records of finished sentences are copied out (in stream order, in front of anything that overwrites them);
+  2. the finished slots are handed to waiting requests (tts_stream.assign_rows): projections, zero fills, one admit launch;
+  3. the next group of BEAM_POLL_STEPS steps; behind it the encoder work of the next waiting requests.
+
+A result does not depend on the slot, the admission tick or the neighbours: hypothesis rows never read another slot's rows (the
+GEMMs, the LayerNorms and the attentions are per row or per sentence, the beam step per sentence), and it is bit-equal to
+generate(decode="graph", exact_rows=True) on the sentence alone as long as the cross-attention's key split, a function of S alone
+(csrc/beam_decode.hip), is the same: up to 64 encoder positions per slot there is one range whatever S is."""
+import collections
+import time
+
+import torch
+
+from . import functional as Fn
+from . import beam_graph
+from .step_program import GRAPH_WARMUP_STEPS, StepProgram, append_layers, capture, decode_stream
+from .tts_stream import assign_rows
+
+STREAM_MODES = ("device", "graph")
+MAX_ROWS = Fn.SKINNY_MAX_M      # sentences * beam: one launch of the skinny-M GEMM
+
+
+def step_limit(gen, src_len, max_len=None):
+    """The step limit of a request of src_len samples: generate()'s formula on its own length, or the request's max_len."""
+    return int(max_len) if max_len is not None else min(int(gen.max_len_a * src_len + gen.max_len_b), gen.max_len - 1)
+
+
+def check_arguments(gen, sentences, max_src_len, decode):
+    """The refusals that need no request: a ValueError naming the option, before anything is enqueued."""
+    if decode not in STREAM_MODES:
+        raise ValueError(f"decode must be one of {STREAM_MODES} for a stream (the other loops have a host step index), got {decode!r}")
+    if gen.ctc_weight > 0:
+        raise ValueError("generate_stream: ctc_weight > 0 is not supported (the CTC prefix scorer has no per-sentence form); use generate()")
+    if gen.lm_model is not None:
+        raise ValueError("generate_stream: lm_model is not supported (the LM's step has no per-sentence form); use generate()")
+    beam_graph.check_generator(gen)
+    if not isinstance(sentences, int) or isinstance(sentences, bool) or sentences < 1:
+        raise ValueError(f"sentences must be an integer >= 1, got {sentences!r}")
+    if sentences * gen.beam_size > MAX_ROWS:
+        raise ValueError(f"sentences={sentences} x beam_size={gen.beam_size} is more than {MAX_ROWS} hypothesis rows (one skinny-M GEMM launch)")
+    if not isinstance(max_src_len, int) or isinstance(max_src_len, bool) or max_src_len < 1:
+        raise ValueError(f"max_src_len must be an integer >= 1 (samples), got {max_src_len!r}")
+    model = gen.model.models[0]
+    if not hasattr(model, "speech_encoder_prenet"):
+        raise ValueError(f"generate_stream needs a speech encoder pre-net; {type(model).__name__} has none")
+    S = int(model.speech_encoder_prenet._frames(max_src_len))
+    if S < 1:
+        raise ValueError(f"max_src_len={max_src_len} samples give no encoder position")
+    cap = step_limit(gen, max_src_len)
+    if cap < gen.min_len:
+        raise ValueError(f"max_src_len={max_src_len}: the step limit {cap} is below min_len={gen.min_len}")
+    return S, cap
+
+
+class BeamStreamDecode:
+    """Every buffer of a stream and its one step program: n_slots slots x beam rows over at most S encoder positions and step limits
+    up to `cap`.  It outlives the graph that has its buffers baked in."""
+
+    def __init__(self, gen, model, n_slots, S, cap, device):
+        beam, V = gen.beam_size, gen.vocab_size
+        dec, pre, post = model.decoder, model.text_decoder_prenet, model.text_decoder_postnet
+        dev, dtype = device, Fn.compute_dtype()
+        layers = self.layers = list(dec.layers)
+        sa, ca = layers[0].self_attn, layers[0].encoder_attn
+        H, hd, C = sa.num_heads, sa.head_dim, sa.embed_dim
+        rows, Tmax = n_slots * beam, cap + 2
+        self.gen, self.n_slots, self.beam, self.S, self.cap, self.C, self.rows = gen, n_slots, beam, S, cap, C, rows
+        i32 = dict(dtype=torch.int32, device=dev)
+        anc = torch.arange(rows, **i32).unsqueeze(1).expand(rows, Tmax).contiguous()
+        bs = self.bs = Fn.BeamStreamState(n_slots, beam, cap, dev, anc=anc)
+        self.never = beam_graph.never_mask(gen, dev)
+        self.len_div = Fn.beam_len_div(cap, gen.len_penalty, dev) if gen.normalize_scores else None
+        self.host = torch.zeros(bs.image.numel(), dtype=torch.int32, pin_memory=True)
+        self.desc_host = torch.zeros(n_slots, 4, dtype=torch.int32, pin_memory=True)
+        self.desc = torch.zeros(n_slots, 4, **i32)
+        self.event = torch.cuda.Event()
+        # self-attention slot caches and the encoder side once per slot, zero-filled: no excluded key and no idle row ever holds
+        # non-finite bits; all keys valid in idle slots
+        self.kv = [torch.zeros(rows, Tmax, 2 * C, dtype=dtype, device=dev) for _ in layers]
+        self_ws = Fn.lm_decode_attn_ws(rows, Tmax, H, hd, dev)
+        self.kpm = torch.zeros(n_slots, S, dtype=torch.uint8, device=dev)
+        cross = [l.encoder_attn for l in layers]
+        ws_ = [w for a in cross for w in (a.k_proj.weight, a.v_proj.weight)]
+        bs_ = [b for a in cross for b in (a.k_proj.bias, a.v_proj.bias)]
+        # the projections as TransformerDecoder.init_beam_slots groups them: all layers in one GEMM where their shapes allow it
+        if all(b is not None for b in bs_) and all(w.shape == ws_[0].shape for w in ws_):
+            kv_all = torch.zeros(n_slots * S, len(cross) * 2 * C, dtype=dtype, device=dev)
+            self.xkv = [(kv_all, idx * 2 * C) for idx in range(len(cross))]
+            self.proj = [(ws_, bs_, kv_all)]
+        else:
+            self.xkv = [(torch.zeros(n_slots * S, 2 * C, dtype=dtype, device=dev), 0) for _ in cross]
+            self.proj = [([a.k_proj.weight, a.v_proj.weight], [a.k_proj.bias, a.v_proj.bias], kv) for a, (kv, _) in zip(cross, self.xkv)]
+        cross_ws = Fn.beam_cross_attn_ws(rows, S, ca.num_heads, ca.head_dim, dev)
+        sent = torch.arange(n_slots, **i32)
+
+        prog = self.prog = StepProgram(dev, dtype, rows)
+        new, lin, add = prog.new, prog.lin, prog.add
+        # pre-net: embed_scale * E[token] + pos[pos[slot] + padding_idx + 1] (beam_graph.py: the step decides the position)
+        table = pre.embed_tokens.weight.detach()
+        pos = pre.embed_positions.table(cap + 2 + pre.padding_idx + 2, dev)
+        x = new(rows, C)
+        add(lambda x=x: Fn.beam_embed_sents(table, bs, pos, pre.padding_idx + 1, pre.embed_scale, x))
+
+        def self_attn(q, slots, ctx, H, hd):      # positions 0 .. pos[slot] over the one ancestry table, reordered in place
+            Fn.lm_decode_attn_rows(q, slots, bs.anc, bs.pos_rows, 1, Tmax, H, hd, ctx, self_ws)
+
+        def cross_attn(idx, q, ctx):              # no step dependence
+            a, (kv, k_off) = layers[idx].encoder_attn, self.xkv[idx]
+            Fn.beam_cross_attn(q, kv, k_off, sent, n_slots, beam, S, a.num_heads, a.head_dim, kpm=self.kpm, ws=cross_ws, ctx=ctx)
+
+        x = append_layers(prog, x, layers, self.kv, Tmax, bs.pos_rows, self_attn, cross_attn, dec.layer_norm, per_row=True)
+        proj = post.output_projection
+        self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
+        rules = dict(temperature=gen.temperature, pad=gen.pad, unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len)
+        add(lambda: Fn.beam_step_sents(self.logits, V, bs, self.never, self.len_div, **rules))
+        add(lambda: Fn.beam_reorder_sents(bs))
+        prog.finish()
+
+    def buffer_ptrs(self):
+        """Data pointers of what the graph has baked in and must never move: slot K/V, encoder-side K|V, key-padding bytes, the
+        beam-step state, its image and the records."""
+        bs = self.bs
+        return tuple(t.data_ptr() for t in self.kv) + tuple(kv.data_ptr() for kv, _ in self.xkv) + tuple(
+            t.data_ptr() for t in (self.kpm, bs.anc, bs.tok, bs.score, bs.image, bs.pos_rows, bs.rec_tok, bs.rec_pos, self.logits))
+
+    def admit(self, pairs, bos):
+        """pairs: [(slot, request)].  Per request the K|V projection of its encoder rows (the single call's GEMM shape) into the slot's
+        slice of the encoder-side buffers and a zero fill behind its frames; then one launch that resets the slots' state."""
+        S = self.S
+        for i, (s, q) in enumerate(pairs):
+            T = q["T"]
+            for weights, biases, dst in self.proj:
+                dst[s * S:s * S + T].copy_(Fn.linear(q["enc"], weights, biases))
+                if T < S:
+                    dst[s * S + T:(s + 1) * S].zero_()
+            self.desc_host[i, 0], self.desc_host[i, 1], self.desc_host[i, 2], self.desc_host[i, 3] = s, q["max_len"], T, bos
+        self.desc.copy_(self.desc_host, non_blocking=True)
+        Fn.beam_sents_admit(self.desc, len(pairs), self.bs, self.kpm)
+
+    def poll(self):
+        """The state image after the steps enqueued so far (one pinned non-blocking copy and an event): pos, maxlen, done, moved,
+        n_hyp, rec_len, rec_score as host views."""
+        self.host.copy_(self.bs.image, non_blocking=True)
+        self.event.record()
+        self.event.synchronize()
+        return self.bs.unpack_image(self.host)
+
+    def copy_out(self, s):
+        """Device copies of slot s's records, enqueued in front of whatever overwrites them."""
+        b0, b1 = s * self.beam, (s + 1) * self.beam
+        bs = self.bs
+        return bs.rec_tok[b0:b1].clone(), bs.rec_pos[b0:b1].clone(), bs.rec_score[b0:b1].clone()
+
+
+class BeamStream:
+    """The loop.  advance() is one poll: it returns [(key, hyps)] of the sentences found finished there, in slot order."""
+
+    def __init__(self, gen, requests, sentences, max_src_len, S, cap, mode):
+        self.gen, self.model, self.requests = gen, gen.model.models[0], iter(requests)
+        self.n_slots, self.max_src_len, self.S, self.cap, self.mode = sentences, max_src_len, S, cap, mode
+        self.P = int(gen.BEAM_POLL_STEPS)
+        self.st, self.graph = None, None
+        self.ready, self.exhausted, self.refused = collections.deque(), False, []
+        self.occupant = [None] * sentences
+        self.stats = {"polls": 0, "device_steps": 0, "graph_replays": 0, "admitted": 0, "sentence_steps": {}}
+        self.inflight, self.finished = False, False
+        self.first_ptrs = None
+        self.profile = bool(getattr(gen, "beam_profile", False))
+        self.spans = []
+
+    # ---- one request, encoded alone as generate(exact_rows=True) encodes a row ----
+    def _encode(self, req):
+        gen = self.gen
+        if not isinstance(req, (tuple, list)) or len(req) not in (2, 3):
+            return f"request {req!r}: expected (key, source) or (key, source, max_len)"
+        key, src = req[0], req[1]
+        max_len = req[2] if len(req) == 3 else None
+        if not isinstance(src, torch.Tensor) or not src.is_floating_point():
+            return (f"request {key!r}: the source must be an fp32 waveform [n] (text sources have no stream), got "
+                    f"{getattr(src, 'dtype', type(src).__name__)}")
+        if src.dim() != 1 or src.numel() < 1:
+            return f"request {key!r}: the source must be one waveform [n], got shape {tuple(src.shape)}"
+        n = int(src.numel())
+        if n > self.max_src_len:
+            return f"request {key!r} has {n} samples, more than max_src_len={self.max_src_len}"
+        limit = step_limit(gen, n, max_len)
+        if limit > self.cap:
+            return f"request {key!r}: max_len {limit} is above the stream's cap {self.cap} (the step limit at max_src_len)"
+        if limit < gen.min_len:
+            return f"request {key!r}: max_len {limit} is below min_len={gen.min_len}"
+        net_input = {"source": src.unsqueeze(0), "padding_mask": torch.zeros(1, n, dtype=torch.bool, device=src.device)}
+        enc = gen.model.forward_encoder(net_input, exact_rows=True)[0]["encoder_out"][0]          # [T, 1, C]
+        T = int(enc.size(0))
+        if T > self.S or T < 1:
+            return f"request {key!r} has {T} encoder positions, outside 1 .. {self.S} (max_src_len={self.max_src_len})"
+        return {"key": key, "T": T, "max_len": limit, "enc": Fn.as_compute(enc[:, 0].contiguous())}
+
+    def _fill_ready(self):
+        """Encoder work of the next waiting requests, at most `sentences` of them ahead of their admission."""
+        while not self.exhausted and len(self.ready) < self.n_slots:
+            try:
+                req = next(self.requests)
+            except StopIteration:
+                self.exhausted = True
+                break
+            q = self._encode(req)
+            if isinstance(q, str):
+                self.refused.append(q)            # (the stream carries on with the next request; raised when it ends)
+            else:
+                self.ready.append(q)
+
+    def _group(self):
+        st, stats = self.st, self.stats
+        e0 = None
+        n = 0
+        for _ in range(self.P):
+            if self.mode == "graph" and stats["device_steps"] >= GRAPH_WARMUP_STEPS:
+                if self.graph is None:
+                    t0 = time.perf_counter()
+                    self.graph = capture(st.prog.step)
+                    stats["capture_s"] = time.perf_counter() - t0
+                if self.profile and e0 is None:
+                    e0 = torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                self.graph.replay()
+                stats["graph_replays"] += 1
+                n += 1
+            else:
+                if self.profile and self.mode != "graph" and e0 is None:
+                    e0 = torch.cuda.Event(enable_timing=True)
+                    e0.record()
+                st.prog.step()
+                stats["device_steps"] += 1
+                n += self.mode != "graph"         # (the warm-up step in front of the capture is not timed, as in run_steps)
+        if e0 is not None and n:
+            e1 = torch.cuda.Event(enable_timing=True)
+            e1.record()
+            self.spans.append((e0, e1, n))
+
+    def _hyps(self, raw, n_hyp, lengths, scores):
+        """generate()'s hypotheses of one sentence from its copied-out records: best first, by BeamDeviceDecode.finalized's sort."""
+        rec_tok, rec_pos, rec_score = raw
+        hyps = []
+        for k in range(n_hyp):
+            n = int(lengths[k])
+            hyps.append({"tokens": rec_tok[k, :n].to(torch.int64), "score": rec_score[k].clone(), "attention": torch.empty(0),
+                         "alignment": torch.empty(0), "positional_scores": rec_pos[k, :n].clone()})
+        order = torch.sort(scores[:n_hyp], descending=True)[1]
+        return [hyps[i] for i in order]
+
+    def advance(self):
+        st, out = self.st, []
+        if self.inflight:
+            pos, _, done, _, n_hyp, rec_len, rec_score = st.poll()
+            self.stats["polls"] += 1
+            self.inflight = False
+            beam = st.beam
+            for s in range(self.n_slots):                                    # 1. copy-out, in slot order
+                q = self.occupant[s]
+                if q is None or not int(done[s]):
+                    continue
+                b0 = s * beam
+                out.append((q["key"], self._hyps(st.copy_out(s), int(n_hyp[s]), rec_len[b0:b0 + beam].clone(),
+                                                 rec_score[b0:b0 + beam].clone())))
+                self.stats["sentence_steps"][q["key"]] = int(pos[s])
+                self.occupant[s] = None
+        self._fill_ready()
+        if st is None and self.ready:
+            st = self.st = BeamStreamDecode(self.gen, self.model, self.n_slots, self.S, self.cap, self.ready[0]["enc"].device)
+            self.first_ptrs = st.buffer_ptrs()
+        free = [s for s in range(self.n_slots) if self.occupant[s] is None]
+        pairs = [(s, self.ready[k]) for s, k in assign_rows(free, len(self.ready))]
+        if not pairs and all(o is None for o in self.occupant):
+            self.finished = True                                             # no running slot, no waiting request
+            return out
+        if pairs:                                                            # 2.
+            st.admit(pairs, self.gen.eos)
+            for s, q in pairs:
+                self.occupant[s] = self.ready.popleft()
+                assert self.occupant[s] is q
+            self.stats["admitted"] += len(pairs)
+        self._group()                                                        # 3.
+        self.inflight = True
+        self._fill_ready()                                                   # encode ahead, behind the group
+        return out
+
+    def close(self):
+        if self.graph is not None:
+            # released with nothing in flight: a CUDAGraph must never be destroyed inside a later capture
+            torch.cuda.current_stream().synchronize()
+            self.graph.reset()
+            self.graph = None
+        if self.profile and self.spans:
+            torch.cuda.current_stream().synchronize()
+            self.stats["step_ms"] = sum(a.elapsed_time(b) for a, b, _ in self.spans)
+            self.stats["steps_timed"] = sum(n for _, _, n in self.spans)
+        g, stats = self.gen, self.stats
+        g.beam_decode_mode = self.mode
+        g.beam_polls, g.beam_device_steps, g.beam_graph_replays = stats["polls"], stats["device_steps"], stats["graph_replays"]
+        g.beam_stream_stats = stats
+        if self.st is not None:
+            g.beam_buffer_ptrs = (self.first_ptrs, self.st.buffer_ptrs())
+
+
+def run_stream(gen, requests, sentences, max_src_len, decode):
+    """The generator behind SequenceGenerator.generate_stream.  The argument checks run at the call, not at the first next().  The
+    decode stream (step_program.decode_stream for "graph") is entered for each poll and left before anything is yielded, so the
+    consumer runs on its own stream between two polls."""
+    S, cap = check_arguments(gen, sentences, max_src_len, decode)
+    return _run(gen, requests, sentences, max_src_len, S, cap, decode)
+
+
+def _tensors(results):
+    for _, hyps in results:
+        for h in hyps:
+            for t in (h["tokens"], h["score"], h["positional_scores"]):
+                yield t
+
+
+def _run(gen, requests, sentences, max_src_len, S, cap, decode):
+    stream = BeamStream(gen, requests, sentences, max_src_len, S, cap, decode)
+    model = gen.model.models[0]
+    device = next(model.parameters()).device
+    # The two streams are ordered only where something crosses between them (tts_stream._run): the consumer's stream in front of the
+    # decode stream at the start and behind every poll that yielded, the decode stream in front of the consumer's at every poll that
+    # yields.  The request iterator is advanced inside the decode stream's context, so what it creates is created there.
+    order_in, side = True, None
+    try:
+        while not stream.finished:
+            cur = torch.cuda.current_stream(device)
+            side = decode_stream(model, device) if decode == "graph" else cur
+            if side != cur and order_in:
+                side.wait_stream(cur)
+            order_in = False
+            with torch.no_grad(), torch.cuda.stream(side):
+                results = stream.advance()
+            if results and side != cur:
+                for t in _tensors(results):
+                    t.record_stream(cur)
+                cur.wait_stream(side)
+                order_in = True
+            yield from results
+    finally:
+        cur = torch.cuda.current_stream(device)
+        with torch.cuda.stream(side if side is not None else cur):
+            stream.close()
+        if side is not None and side != cur:
+            cur.wait_stream(side)
+    if stream.refused:
+        raise ValueError("requests: refused " + "; ".join(stream.refused))

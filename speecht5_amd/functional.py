@@ -3982,6 +3982,87 @@ def beam_embed_step(table, st, pos, pos_off, emb_scale, y):
 
 
 # -------------------------------------------------------------------------------------------------
+# The beam step PER SENTENCE (st5_beam_*_sents, st5_beam_sents_admit in csrc/beam_step.hip): the step of a beam-search stream
+# (beam_stream.py).  Slot s's bits are those of the scalar forms above at step pos[s] under the limit maxlen[s].
+# -------------------------------------------------------------------------------------------------
+class BeamStreamState:
+    """Device state of st5_beam_step_sents for n_slots sentence slots x beam rows and step limits up to `cap`
+    (include/speecht5_hip.h).  Every slot starts idle (done = 1); st5_beam_sents_admit hands one to a sentence.  `image` is what the
+    host reads at a poll, ONE buffer: pos | maxlen | done | moved | n_hyp (n_slots each), rec_len [rows], rec_score [rows] (fp32
+    bits); rec_tok / rec_pos [rows, cap + 1] are read per finished slot.  `anc` is the slot cache's ancestry table [rows, cap + 2]."""
+
+    def __init__(self, n_slots, beam, cap, device, anc=None):
+        rows, Tmax = n_slots * beam, cap + 2
+        i32 = dict(dtype=torch.int32, device=device)
+        self.n_slots, self.n_sent, self.beam, self.cap, self.max_len, self.Tmax, self.rows = n_slots, n_slots, beam, cap, cap, Tmax, rows
+        self.tok = torch.zeros(rows, Tmax, **i32)
+        self.score = torch.zeros(rows, Tmax, dtype=torch.float32, device=device)
+        self.anc = anc if anc is not None else torch.arange(rows, **i32).unsqueeze(1).expand(rows, Tmax).contiguous()
+        assert self.anc.dtype == torch.int32 and self.anc.shape == (rows, Tmax) and self.anc.stride(1) == 1
+        self.ignore = torch.zeros(rows, dtype=torch.uint8, device=device)
+        self.parent = torch.arange(rows, **i32)
+        self.image = torch.zeros(5 * n_slots + 2 * rows, **i32)
+        n = n_slots
+        self.pos, self.maxlen, self.done, self.moved, self.n_hyp = (self.image[k * n:(k + 1) * n] for k in range(5))
+        self.rec_len = self.image[5 * n:5 * n + rows]
+        self.rec_score = self.image[5 * n + rows:].view(torch.float32)
+        self.done.fill_(1)
+        self.pos_rows = torch.zeros(rows, **i32)
+        self.rec_tok = torch.zeros(rows, cap + 1, **i32)
+        self.rec_pos = torch.zeros(rows, cap + 1, dtype=torch.float32, device=device)
+
+    def unpack_image(self, host):
+        """(pos, maxlen, done, moved, n_hyp, rec_len, rec_score) as views of `host`, a copy of self.image."""
+        n, rows = self.n_slots, self.rows
+        return tuple(host[k * n:(k + 1) * n] for k in range(5)) + (host[5 * n:5 * n + rows], host[5 * n + rows:].view(torch.float32))
+
+
+def beam_step_sents(logits, V, st, never, len_div, *, temperature, pad, unk, eos, unk_penalty, min_len, lprobs=None):
+    """One st5_beam_step_sents on state `st` (BeamStreamState); the arguments are beam_step's, len_div covers 0 .. st.cap."""
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == st.rows and logits.shape[1] >= V
+    assert never.dtype == torch.uint8 and never.is_contiguous() and never.numel() == V
+    assert len_div is None or (len_div.dtype == torch.float32 and len_div.is_contiguous() and len_div.numel() >= st.cap + 1)
+    assert lprobs is None or (lprobs.dtype == torch.float32 and lprobs.stride(1) == 1 and lprobs.shape[0] == st.rows and lprobs.shape[1] >= V)
+    hip.check(hip.lib().st5_beam_step_sents(
+        logits.data_ptr(), logits.stride(0), hip.ptr(lprobs), 0 if lprobs is None else lprobs.stride(0), st.n_slots, st.beam, int(V),
+        float(temperature), st.tok.data_ptr(), st.score.data_ptr(), st.anc.data_ptr(), st.anc.stride(0), st.Tmax, st.ignore.data_ptr(),
+        st.parent.data_ptr(), st.rec_tok.data_ptr(), st.rec_pos.data_ptr(), st.rec_tok.stride(0), st.rec_score.data_ptr(),
+        st.rec_len.data_ptr(), st.n_hyp.data_ptr(), st.pos.data_ptr(), st.maxlen.data_ptr(), st.done.data_ptr(), st.moved.data_ptr(),
+        st.pos_rows.data_ptr(), never.data_ptr(), hip.ptr(len_div), int(pad), int(unk), int(eos), float(unk_penalty), int(min_len),
+        st.cap, hip.stream()), "st5_beam_step_sents")
+
+
+def beam_reorder_sents(st):
+    """The ancestry reorder behind beam_step_sents, in place, for the slots that step moved."""
+    hip.check(hip.lib().st5_beam_reorder_sents(st.anc.data_ptr(), st.anc.stride(0), st.parent.data_ptr(), st.n_slots, st.beam, st.Tmax,
+                                               st.pos.data_ptr(), st.maxlen.data_ptr(), st.moved.data_ptr(), st.cap, hip.stream()),
+              "st5_beam_reorder_sents")
+
+
+def beam_embed_sents(table, st, pos, pos_off, emb_scale, y):
+    """y[r] = emb_scale * table[st.tok[r, p]] + pos[p + pos_off], p = st.pos[r // beam] (fp32 tables, y [rows, C], compute dtype)."""
+    V, C = table.shape
+    assert table.dtype == torch.float32 and table.is_contiguous() and pos.dtype == torch.float32 and pos.is_contiguous()
+    assert pos.shape[1] == C and y.shape == (st.rows, C) and y.stride(1) == 1
+    hip.check(hip.lib().st5_beam_embed_sents(table.data_ptr(), V, st.tok.data_ptr(), st.Tmax, st.pos.data_ptr(), st.n_slots, st.beam,
+                                             pos.data_ptr(), pos.shape[0], int(pos_off), float(emb_scale), y.data_ptr(), y.stride(0), C,
+                                             _dt(y), hip.stream()), "st5_beam_embed_sents")
+    return y
+
+
+def beam_sents_admit(desc, n_admit, st, kpm):
+    """Hands the slots named by desc (int32 [>= n_admit, 4] on the device: slot, max_len, frames, bos) to new sentences: the slot's
+    beam-step state reset, its record header emptied, its key-padding bytes (kpm uint8 [n_slots, S]) written."""
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.shape[1] == 4 and desc.shape[0] >= n_admit
+    assert kpm.dtype == torch.uint8 and kpm.is_contiguous() and kpm.shape[0] == st.n_slots
+    hip.check(hip.lib().st5_beam_sents_admit(desc.data_ptr(), int(n_admit), st.n_slots, st.beam, st.cap, st.Tmax, st.tok.data_ptr(),
+                                             st.score.data_ptr(), st.anc.data_ptr(), st.anc.stride(0), st.ignore.data_ptr(),
+                                             st.n_hyp.data_ptr(), st.rec_len.data_ptr(), st.pos.data_ptr(), st.pos_rows.data_ptr(),
+                                             st.maxlen.data_ptr(), st.done.data_ptr(), kpm.data_ptr(), kpm.shape[1], hip.stream()),
+              "st5_beam_sents_admit")
+
+
+# -------------------------------------------------------------------------------------------------
 # Joint CTC / attention scoring behind the step counter (csrc/beam_ctc.hip): candidates, prefix scores + mix, select.
 # -------------------------------------------------------------------------------------------------
 BEAM_CTC_MAX_CANDIDATES = 1024

@@ -253,6 +253,21 @@ class SequenceGenerator(nn.Module):
         """fairseq generator API: `models` is ignored (the ensemble was fixed at construction, :192-205)."""
         return self._generate(sample, **kwargs)
 
+    def generate_stream(self, requests, *, sentences, max_src_len, decode="graph"):
+        """Streaming beam search (beam_stream.py): a Python generator over `requests`, an iterable of (key, source) or (key, source,
+        max_len) with `source` one fp32 waveform [n]; yields (key, hyps) in completion order (sentences that finish at the same poll
+        in slot order), hyps as generate() returns them for one sentence in the "device" / "graph" modes.  `sentences` slots of
+        beam_size rows each are stepped by one step program ("device": kernel by kernel; "graph": captured once, replayed until the
+        stream ends) and polled every BEAM_POLL_STEPS steps; a finished slot is handed to the next waiting request there.  A request
+        is encoded alone, as generate(exact_rows=True) encodes a row; `max_src_len` (samples) fixes the encoder positions per slot;
+        the step limit of a request is min(int(max_len_a * n + max_len_b), max_len - 1) on its own length n, or its max_len, and at
+        most that formula at max_src_len.  A request that is too long, whose max_len is above that cap, or whose source is not
+        floating point is refused by key when the stream ends (ValueError); the others complete.  Attention-only search: ctc_weight >
+        0, lm_model and everything the device-stepped modes refuse raise a ValueError naming the option, at the call.  The
+        generator's own `decode` does not matter here, and nothing about generate() changes."""
+        from . import beam_stream
+        return beam_stream.run_stream(self, requests, sentences, max_src_len, decode)
+
     # -------------------------------------------------------------------------------------------
     def _never(self, lprobs):
         """Symbols no hypothesis may contain: <ctc_blank>, <mask>, the sentinel masks (:446-450)."""

@@ -299,6 +299,11 @@ class SpeechT5Task(LegacyFairseqTask):
         """Streaming text (or speech) to waveform (T5TransformerModel.synthesize_stream): (key, wav, mel, probs) in completion order."""
         return models[0].synthesize_stream(requests, vocoder=vocoder, **kwargs)
 
+    def inference_stream(self, generator, models, requests, **kwargs):
+        """Streaming beam search (SequenceGenerator.generate_stream): (key, hyps) in completion order; `models` is ignored, as in the
+        generator's generate() (the ensemble was fixed at construction)."""
+        return generator.generate_stream(requests, **kwargs)
+
     @property
     def source_dictionary(self):
         return None
