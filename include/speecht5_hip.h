@@ -364,9 +364,15 @@ int st5_conv0_set_gelu_table(int on);
 int64_t st5_conv0_ws_bytes(int32_t B, int32_t S, int32_t C, int32_t k, int32_t stride);
 
 /* ---- element-wise / reductions (glue ops fused where the reference has separate torch calls) */
-/* dst(dtype) = src(fp32), optionally transposed: src [rows, cols] -> dst [cols, rows] */
+/* Alignment rule of the FLAT entry points (st5_cast_from_f32 without transpose, st5_cast_to_f32, st5_sumsq, st5_sumsq_pair, st5_axpby,
+ * st5_act_fwd, st5_act_bwd, st5_dropout): pointers need only the alignment of their element type.  16-byte vectors when every pointer
+ * argument is 16-byte aligned, scalars otherwise -- the same arithmetic per element, so every element comes out with the same bits
+ * either way (the two sums: see st5_sumsq). */
+/* dst(dtype) = src(fp32), optionally transposed: src [rows, cols] -> dst [cols, rows].  Round to nearest even.  Not transposed: 16-byte
+ * vectors when src and dst are 16-byte aligned, scalars otherwise (same bits). */
 int st5_cast_from_f32(const float* src, void* dst, int64_t rows, int64_t cols, int32_t transpose, int dtype,
                       void* stream);
+/* dst(fp32) = src(dtype).  16-byte vectors when src and dst are 16-byte aligned, scalars otherwise (same bits). */
 int st5_cast_to_f32(const void* src, float* dst, int64_t n, int dtype, void* stream);
 /* out[c] (+)= scale * sum_r x[r, c]   (bias gradients); ws >= st5_colsum_ws_bytes(rows, cols) */
 int st5_colsum_ws(const void* x, float* out, void* ws, int64_t rows, int32_t cols, int64_t ld, float scale,
@@ -389,9 +395,12 @@ int st5_relpos_bwd_supported(int32_t nb);   /* nb a multiple of 64, at most 320 
 /* dpe[c] (dtype) = sum over rows of part[r][c], in the order of st5_colsum_ws (overwrite form, scale 1) followed by st5_cast_from_f32: same
  * bytes, one launch.  gate (may be NULL): *gate == 0 -> part is not read, dpe = exact zeros. */
 int st5_relpos_dpe_final(const float* part, void* dpe, int64_t rows, int32_t cols, const float* gate, int dtype, void* stream);
-/* out[0] (+)= scale * sum(x^2)   (features_pen, speech_encoder_prenet.py:172) */
+/* out[0] (+)= scale * sum(x^2)   (features_pen, speech_encoder_prenet.py:172).  16-byte vectors when x is 16-byte aligned, scalars
+ * otherwise: the squares are then added in ANOTHER ORDER (one element per thread and trip instead of eight), so the sum over an unaligned
+ * buffer may differ in its last bits from the sum of the same values at an aligned address.  st5_sumsq (fp32) and st5_sumsq_pair walk
+ * the same partition on the same alignment (for the pair: x and y both aligned / not both aligned) and agree bit for bit there. */
 int st5_sumsq(const void* x, float* out, int64_t n, float scale, int32_t accumulate, int dtype, void* stream);
-/* y = a*x + b*y */
+/* y = a*x + b*y in place.  16-byte vectors when x and y are 16-byte aligned, scalars otherwise (same bits). */
 int st5_axpby(const void* x, void* y, int64_t n, float a, float b, int dtype, void* stream);
 /* LayerDrop inside a replayed (HIP-graph) step, where the host's per-layer draw cannot steer control flow
  * (modules/encoder.py:251-257 `if not self.training or (dropout_probability > self.encoder_layerdrop)`, modules/decoder.py:64-67
@@ -402,13 +411,15 @@ int st5_select_bwd(const float* keep_dev, const void* g, void* ga, void* gb, int
 /* dx = *keep ? dx : g  in place (raw 16-byte chunks): the input gradient of a gated layer (st5_layernorm_gated_fwd) -- a kept layer's
  * own input gradient stands, a dropped layer's (exact zeros) is replaced by the gradient of its output. */
 int st5_skip_grad(const float* keep_dev, const void* g, void* dx, int64_t nbytes, void* stream);
-/* y = act(x) ; dx = dy * act'(x) */
+/* y = act(x) ; dx = dy * act'(x).  y may be x, dx may be dy.  A NaN in x comes out of every activation's forward as NaN (ReLU
+ * included, as torch.relu gives it).  16-byte vectors when every pointer is 16-byte aligned, scalars otherwise (same bits). */
 int st5_act_fwd(const void* x, void* y, int64_t n, int32_t act, int dtype, void* stream);
 int st5_act_bwd(const void* dy, const void* x, void* dx, int64_t n, int32_t act, int dtype, void* stream);
 /* y[r,c] = act(x[r,c] * a[c] + b[c])   (per-channel affine: spectrogram normalisation, BatchNorm apply) */
 int st5_channel_affine(const void* x, const float* a, const float* b, void* y, int64_t rows, int32_t cols, int32_t act,
                        int dtype, void* stream);
-/* y = dropout(x) with the library's counter RNG (same generator as the GEMM epilogue) */
+/* y = dropout(x) with the library's counter RNG (same generator as the GEMM epilogue), counter = the element's index.  16-byte vectors
+ * when x and y are 16-byte aligned, scalars otherwise (same mask, same bits). */
 int st5_dropout(const void* x, void* y, int64_t n, float p, uint64_t seed, int dtype, void* stream);
 /* x[r,:] = v (fp32 [cols]) where mask[r] != 0  (apply_hubert_mask, speech_encoder_prenet.py:249) */
 int st5_masked_fill_rows(void* x, const uint8_t* mask, const float* v, int64_t rows, int32_t cols, int dtype,
@@ -781,6 +792,8 @@ int st5_se_predict_bwd(const float* d_before, const float* d_after, const float*
 int st5_adam_step_pair(float* p, float* g, float* g2, int32_t zero_grads, float* m, float* v, int64_t n, float lr, float beta1, float beta2,
                        float eps, float weight_decay, int32_t step, const float* gnorm_sq, float max_norm, float grad_scale,
                        void* bf16_mirror, const float* hyper_dev, void* stream);
+/* out[0] (+)= scale * sum((x + y)^2), fp32: bit-identical to st5_sumsq of the buffer x + y at the same alignment.  16-byte vectors when
+ * x and y are 16-byte aligned, scalars otherwise (another summation order: see st5_sumsq). */
 int st5_sumsq_pair(const float* x, const float* y, float* out, int64_t n, float scale, int32_t accumulate, void* stream);
 /* ---- The Adam step behind a finite-gradient guard (ddp.FusedAdam(skip_nonfinite=True), update.PretrainUpdate(nonfinite="skip");
  * csrc/optim.hip) ----

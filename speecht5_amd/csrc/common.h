@@ -268,7 +268,7 @@ template <bool FAST = false>
 __device__ __forceinline__ float act_f(int act, float x) {
   switch (act) {
     case ACT_GELU: return FAST ? gelu_poly(x) : gelu_f(x);
-    case ACT_RELU: return x > 0.f ? x : 0.f;
+    case ACT_RELU: return x <= 0.f ? 0.f : x;   // (not x > 0 ? x : 0: a NaN must come out as NaN, as torch.relu gives it)
     case ACT_TANH: return tanhf(x);
     case ACT_LRELU_01: return x > 0.f ? x : 0.1f * x;
     case ACT_LRELU_001: return x > 0.f ? x : 0.01f * x;

@@ -14,11 +14,22 @@ inline dim3 grid_for(long long nvec) {
   if (b < 1) b = 1;
   return dim3((unsigned)b);
 }
+inline bool aligned16(std::initializer_list<const void*> ps) {
+  for (const void* p : ps) if ((uintptr_t)p & 15u) return false;
+  return true;
+}
+// The flat kernels below walk 8-element vectors (16-byte loads and stores at p + 8 * i) over [0, 8 * nv) and single elements over
+// [8 * nv, n).  The host passes nv = n / 8 when every pointer is 16-byte aligned -- the launch is then the one these entry points always
+// made -- and nv = 0 otherwise: the same per-element arithmetic on scalars, one element per thread and trip.
+struct FlatPlan { long long nv; dim3 grid; };
+inline FlatPlan flat_plan(long long n, std::initializer_list<const void*> ps) {
+  if (aligned16(ps)) return {n / 8, grid_for(n / 8 + 1)};
+  return {0, grid_for(n)};
+}
 
 // ---- casts ----
 template <typename T>
-__global__ void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst, long long n) {
-  const long long nv = n / 8;
+__global__ void cast_from_f32_kernel(const float* __restrict__ src, T* __restrict__ dst, long long n, long long nv) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
     float v[8];
     load8f<float>(src + i * 8, v);
@@ -46,8 +57,7 @@ __global__ void cast_transpose_kernel(const float* __restrict__ src, T* __restri
   }
 }
 template <typename T>
-__global__ void cast_to_f32_kernel(const T* __restrict__ src, float* __restrict__ dst, long long n) {
-  const long long nv = n / 8;
+__global__ void cast_to_f32_kernel(const T* __restrict__ src, float* __restrict__ dst, long long n, long long nv) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
     float v[8];
     load8f<T>(src + i * 8, v);
@@ -60,8 +70,7 @@ __global__ void cast_to_f32_kernel(const T* __restrict__ src, float* __restrict_
 
 // ---- generic unary / binary element-wise with a functor on 8-vectors ----
 template <typename T, typename F>
-__global__ void map1_kernel(const T* __restrict__ x, T* __restrict__ y, long long n, F f) {
-  const long long nv = n / 8;
+__global__ void map1_kernel(const T* __restrict__ x, T* __restrict__ y, long long n, long long nv, F f) {
   const unsigned int st = f.init();       // (loop-invariant state of the functor, computed once per thread: Drop's seed hash)
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
     float v[8];
@@ -75,8 +84,7 @@ __global__ void map1_kernel(const T* __restrict__ x, T* __restrict__ y, long lon
     y[i] = Elem<T>::from_f(f(Elem<T>::to_f(x[i]), i, st));
 }
 template <typename T, typename F>
-__global__ void map2_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, long long n, F f) {
-  const long long nv = n / 8;
+__global__ void map2_kernel(const T* __restrict__ a, const T* __restrict__ b, T* __restrict__ y, long long n, long long nv, F f) {
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
     float u[8], v[8];
     load8f<T>(a + i * 8, u);
@@ -135,10 +143,9 @@ __global__ __launch_bounds__(256) void skip_grad_kernel(const float* __restrict_
 
 // ---- sum of squares ----
 template <typename T>
-__global__ void sumsq_kernel(const T* __restrict__ x, float* __restrict__ part, long long n) {
+__global__ void sumsq_kernel(const T* __restrict__ x, float* __restrict__ part, long long n, long long nv) {
   __shared__ float red[4];
   float s = 0.f;
-  const long long nv = n / 8;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
     float v[8];
     load8f<T>(x + i * 8, v);
@@ -158,10 +165,9 @@ __global__ void sumsq_kernel(const T* __restrict__ x, float* __restrict__ part, 
 // sum of squares of x + y (fp32): the gradient norm over two gradient buffers.  Same partition and summation order as
 // sumsq_kernel<float> (8 elements per thread and trip), so norm(x + y) comes out bit-identical whether the buffers were summed
 // first (several ranks: all-reduce in between) or are summed here.
-__global__ void sumsq_pair_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ part, long long n) {
+__global__ void sumsq_pair_kernel(const float* __restrict__ x, const float* __restrict__ y, float* __restrict__ part, long long n, long long nv) {
   __shared__ float red[4];
   float s = 0.f;
-  const long long nv = n / 8;
   for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < nv; i += (long long)gridDim.x * blockDim.x) {
     const f32x4 a0 = reinterpret_cast<const f32x4*>(x)[2 * i], a1 = reinterpret_cast<const f32x4*>(x)[2 * i + 1];
     const f32x4 b0 = reinterpret_cast<const f32x4*>(y)[2 * i], b1 = reinterpret_cast<const f32x4*>(y)[2 * i + 1];
@@ -683,8 +689,9 @@ extern "C" int st5_cast_from_f32(const float* src, void* dst, int64_t rows, int6
   hipStream_t s = (hipStream_t)stream;
   if (!transpose) {
     const long long n = rows * cols;
-    DISPATCH(dtype, hipLaunchKernelGGL(cast_from_f32_kernel<bf16_t>, grid_for(n / 8 + 1), dim3(256), 0, s, src, (bf16_t*)dst, n),
-             hipLaunchKernelGGL(cast_from_f32_kernel<float>, grid_for(n / 8 + 1), dim3(256), 0, s, src, (float*)dst, n));
+    const FlatPlan pl = flat_plan(n, {src, dst});
+    DISPATCH(dtype, hipLaunchKernelGGL(cast_from_f32_kernel<bf16_t>, pl.grid, dim3(256), 0, s, src, (bf16_t*)dst, n, pl.nv),
+             hipLaunchKernelGGL(cast_from_f32_kernel<float>, pl.grid, dim3(256), 0, s, src, (float*)dst, n, pl.nv));
   } else {
     dim3 grid((unsigned)((cols + 31) / 32), (unsigned)((rows + 31) / 32));
     DISPATCH(dtype, hipLaunchKernelGGL(cast_transpose_kernel<bf16_t>, grid, dim3(256), 0, s, src, (bf16_t*)dst, (long long)rows, (long long)cols),
@@ -697,8 +704,9 @@ extern "C" int st5_cast_to_f32(const void* src, float* dst, int64_t n, int dtype
   if (!src || !dst || n < 0) return ST5_ERR_ARG;
   if (n == 0) return ST5_OK;
   hipStream_t s = (hipStream_t)stream;
-  DISPATCH(dtype, hipLaunchKernelGGL(cast_to_f32_kernel<bf16_t>, grid_for(n / 8 + 1), dim3(256), 0, s, (const bf16_t*)src, dst, (long long)n),
-           hipLaunchKernelGGL(cast_to_f32_kernel<float>, grid_for(n / 8 + 1), dim3(256), 0, s, (const float*)src, dst, (long long)n));
+  const FlatPlan pl = flat_plan(n, {src, dst});
+  DISPATCH(dtype, hipLaunchKernelGGL(cast_to_f32_kernel<bf16_t>, pl.grid, dim3(256), 0, s, (const bf16_t*)src, dst, (long long)n, pl.nv),
+           hipLaunchKernelGGL(cast_to_f32_kernel<float>, pl.grid, dim3(256), 0, s, (const float*)src, dst, (long long)n, pl.nv));
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
@@ -707,9 +715,10 @@ extern "C" int st5_sumsq(const void* x, float* out, int64_t n, float scale, int3
   hipStream_t s = (hipStream_t)stream;
   float* part = sumsq_parts(s);
   if (!part) return ST5_ERR_LAUNCH;
-  dim3 grid = grid_for(n / 8 + 1);
-  DISPATCH(dtype, hipLaunchKernelGGL(sumsq_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, part, (long long)n),
-           hipLaunchKernelGGL(sumsq_kernel<float>, grid, dim3(256), 0, s, (const float*)x, part, (long long)n));
+  const FlatPlan pl = flat_plan(n, {x});
+  const dim3 grid = pl.grid;
+  DISPATCH(dtype, hipLaunchKernelGGL(sumsq_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)x, part, (long long)n, pl.nv),
+           hipLaunchKernelGGL(sumsq_kernel<float>, grid, dim3(256), 0, s, (const float*)x, part, (long long)n, pl.nv));
   hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, s, part, out, (int)grid.x, scale, accumulate);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
@@ -719,8 +728,9 @@ extern "C" int st5_sumsq_pair(const float* x, const float* y, float* out, int64_
   hipStream_t s = (hipStream_t)stream;
   float* part = sumsq_parts(s);
   if (!part) return ST5_ERR_LAUNCH;
-  dim3 grid = grid_for(n / 8 + 1);
-  hipLaunchKernelGGL(sumsq_pair_kernel, grid, dim3(256), 0, s, x, y, part, (long long)n);
+  const FlatPlan pl = flat_plan(n, {x, y});
+  const dim3 grid = pl.grid;
+  hipLaunchKernelGGL(sumsq_pair_kernel, grid, dim3(256), 0, s, x, y, part, (long long)n, pl.nv);
   hipLaunchKernelGGL(sum_final_kernel, dim3(1), dim3(256), 0, s, part, out, (int)grid.x, scale, accumulate);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
@@ -730,8 +740,9 @@ extern "C" int st5_axpby(const void* x, void* y, int64_t n, float a, float b, in
   if (n == 0) return ST5_OK;
   hipStream_t s = (hipStream_t)stream;
   Axpby f{a, b};
-  DISPATCH(dtype, hipLaunchKernelGGL((map2_kernel<bf16_t, Axpby>), grid_for(n / 8 + 1), dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)y, (bf16_t*)y, (long long)n, f),
-           hipLaunchKernelGGL((map2_kernel<float, Axpby>), grid_for(n / 8 + 1), dim3(256), 0, s, (const float*)x, (const float*)y, (float*)y, (long long)n, f));
+  const FlatPlan pl = flat_plan(n, {x, y});
+  DISPATCH(dtype, hipLaunchKernelGGL((map2_kernel<bf16_t, Axpby>), pl.grid, dim3(256), 0, s, (const bf16_t*)x, (const bf16_t*)y, (bf16_t*)y, (long long)n, pl.nv, f),
+           hipLaunchKernelGGL((map2_kernel<float, Axpby>), pl.grid, dim3(256), 0, s, (const float*)x, (const float*)y, (float*)y, (long long)n, pl.nv, f));
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
@@ -767,8 +778,9 @@ extern "C" int st5_act_fwd(const void* x, void* y, int64_t n, int32_t act, int d
   if (n == 0) return ST5_OK;
   hipStream_t s = (hipStream_t)stream;
   ActF f{act};
-  DISPATCH(dtype, hipLaunchKernelGGL((map1_kernel<bf16_t, ActF>), grid_for(n / 8 + 1), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (long long)n, f),
-           hipLaunchKernelGGL((map1_kernel<float, ActF>), grid_for(n / 8 + 1), dim3(256), 0, s, (const float*)x, (float*)y, (long long)n, f));
+  const FlatPlan pl = flat_plan(n, {x, y});
+  DISPATCH(dtype, hipLaunchKernelGGL((map1_kernel<bf16_t, ActF>), pl.grid, dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (long long)n, pl.nv, f),
+           hipLaunchKernelGGL((map1_kernel<float, ActF>), pl.grid, dim3(256), 0, s, (const float*)x, (float*)y, (long long)n, pl.nv, f));
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
@@ -777,8 +789,9 @@ extern "C" int st5_act_bwd(const void* dy, const void* x, void* dx, int64_t n, i
   if (n == 0) return ST5_OK;
   hipStream_t s = (hipStream_t)stream;
   ActB f{act};
-  DISPATCH(dtype, hipLaunchKernelGGL((map2_kernel<bf16_t, ActB>), grid_for(n / 8 + 1), dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, (long long)n, f),
-           hipLaunchKernelGGL((map2_kernel<float, ActB>), grid_for(n / 8 + 1), dim3(256), 0, s, (const float*)dy, (const float*)x, (float*)dx, (long long)n, f));
+  const FlatPlan pl = flat_plan(n, {dy, x, dx});
+  DISPATCH(dtype, hipLaunchKernelGGL((map2_kernel<bf16_t, ActB>), pl.grid, dim3(256), 0, s, (const bf16_t*)dy, (const bf16_t*)x, (bf16_t*)dx, (long long)n, pl.nv, f),
+           hipLaunchKernelGGL((map2_kernel<float, ActB>), pl.grid, dim3(256), 0, s, (const float*)dy, (const float*)x, (float*)dx, (long long)n, pl.nv, f));
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
@@ -797,8 +810,9 @@ extern "C" int st5_dropout(const void* x, void* y, int64_t n, float p, uint64_t 
   if (n == 0) return ST5_OK;
   hipStream_t s = (hipStream_t)stream;
   Drop f{(unsigned long long)seed, (unsigned int)(p * 65536.0f), 1.f / (1.f - p)};
-  DISPATCH(dtype, hipLaunchKernelGGL((map1_kernel<bf16_t, Drop>), grid_for(n / 8 + 1), dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (long long)n, f),
-           hipLaunchKernelGGL((map1_kernel<float, Drop>), grid_for(n / 8 + 1), dim3(256), 0, s, (const float*)x, (float*)y, (long long)n, f));
+  const FlatPlan pl = flat_plan(n, {x, y});
+  DISPATCH(dtype, hipLaunchKernelGGL((map1_kernel<bf16_t, Drop>), pl.grid, dim3(256), 0, s, (const bf16_t*)x, (bf16_t*)y, (long long)n, pl.nv, f),
+           hipLaunchKernelGGL((map1_kernel<float, Drop>), pl.grid, dim3(256), 0, s, (const float*)x, (float*)y, (long long)n, pl.nv, f));
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
@@ -1144,11 +1158,6 @@ __global__ __launch_bounds__(256) void se_predict_bwd_kernel(const float* __rest
     gb[i] = se_bwd(mode, db[i], xb[i], s);
   }
 }
-inline bool aligned16(std::initializer_list<const void*> ps) {
-  for (const void* p : ps) if ((uintptr_t)p & 15u) return false;
-  return true;
-}
-
 // ---- ragged log-mel framing: st5_stft_frames over B waveforms of different lengths, frames packed item after item ----
 // Thread = 4 consecutive samples of one frame (one 16-byte store); the item of a packed frame row is found by bisection in
 // frame_off [B + 1]; reflection happens at the item's own ends.
