@@ -950,6 +950,47 @@ int st5_ctc_select_dev(const int32_t* lens, int32_t S, int32_t Tfr, int32_t beam
 int st5_beam_embed_step(const float* table, int32_t V, const int32_t* tok, int32_t Tmax, const int32_t* counter, const float* pos,
                         int32_t pos_rows, int32_t pos_off, float emb_scale, void* y, int64_t y_ld, int32_t rows, int32_t cols, int dtype,
                         void* stream);
+/* ---- joint CTC / attention scoring PER SENTENCE SLOT (csrc/beam_ctc.hip, csrc/beam_step.hip; index arithmetic in
+ * csrc/beam_stream_index.h): the CTC part of the step of a beam-search stream (generate_stream(joint_ctc=True),
+ * speecht5_amd/beam_stream.py).  The same kernel bodies as the three kernels above under a template flag: slot s = r / beam reads
+ * pos[s], maxlen[s] (clamped into [0, cap]), done[s], moved[s] of the st5_beam_step_sents state and frames[s] where the scalar forms
+ * read *counter, max_len and lens.  rows = n_slots * beam; x [n_slots][S][V] fp32, the slot's posterior over frames[s] <= S frames;
+ * frames int32 [n_slots]; state [rows][S][2], r_new [rows][S][nc][2], log_psi [rows][nc], prev [rows], cs int32 [rows][nc],
+ * lp [rows][lp_ld], unknown int32 [n_slots].  Per (row, candidate) pair the bits are the scalar forms' at step pos[s].  None of these
+ * writes done, pos or anything of another slot, and none reads another slot's CTC state.  Launch order inside a step: candidates_sents,
+ * prefix_score_rows_sents, st5_beam_step_sents_logprobs on lp, select_sents, st5_beam_reorder_sents.
+ * st5_beam_ctc_candidates_sents: st5_beam_ctc_candidates for step = pos[s].  A slot with done[s] != 0, or pos[s] outside
+ *   0 .. maxlen[s], returns before its first load: its lp and cs rows are not written.
+ * st5_ctc_prefix_score_rows_sents: st5_ctc_prefix_score_rows_dev under the same gate with T = clamp(frames[s], 0, S), out_len = pos[s],
+ *   last[r] = tok[r][pos[s]].  The gate is uniform per workgroup.
+ * st5_beam_step_sents_logprobs: st5_beam_step_sents on log-probabilities, as st5_beam_step_logprobs is st5_beam_step on them.
+ * st5_ctc_select_sents, behind the beam step: acts only where moved[s] != 0 and 1 <= t = pos[s] <= maxlen[s]; st5_ctc_select_dev for the
+ *   slot's rows with sent_done = done[s] as that step left it.  unknown[s] = 1 (sticky until the slot's next admission) when a row of
+ *   slot s that still counts (ignore clear, done[s] clear) was continued by a token outside its parent's candidates, or has a parent
+ *   outside its own slot (then: logzero state, prev NaN).
+ * st5_ctc_sents_admit, behind st5_beam_sents_admit over the same descriptors (slot, max_len, frames, bos): frames[slot] =
+ *   clamp(frames, 0, S); state of the slot's `beam` rows = st5_ctc_initial_state_rows' state of the slot's slice of x over those frames
+ *   (the same arithmetic; logzero behind them); prev = 0 for the slot's rows; unknown[slot] = 0.  The slice of x is written by the
+ *   caller in front of the launch.  A slot outside [0, n_slots) admits nothing; no other slot's bytes change. */
+int st5_beam_ctc_candidates_sents(const float* logits, int64_t ld, int32_t n_slots, int32_t beam, int32_t V, float temperature,
+                                  const uint8_t* never, const int32_t* pos, const int32_t* maxlen, const int32_t* done, int32_t cap,
+                                  float* lp, int64_t lp_ld, int32_t* cs, int32_t nc, void* stream);
+int st5_ctc_prefix_score_rows_sents(const float* x, const int32_t* frames, int32_t n_slots, int32_t S, int32_t V, int32_t blank, int32_t eos,
+                                    int32_t beam, const float* r_prev, const int32_t* tok, int32_t tok_ld, const int32_t* pos,
+                                    const int32_t* maxlen, const int32_t* done, int32_t cap, const int32_t* cs, int32_t nc, float* log_psi,
+                                    float* r_new, const float* prev, float* lp, int64_t lp_ld, double ctc_weight, void* stream);
+int st5_beam_step_sents_logprobs(const float* lp, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_slots, int32_t beam, int32_t V,
+                                 int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax, uint8_t* ignore,
+                                 int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score, int32_t* rec_len,
+                                 int32_t* n_hyp, int32_t* pos, const int32_t* maxlen, int32_t* done, int32_t* moved, int32_t* pos_rows,
+                                 const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos, float unk_penalty,
+                                 int32_t min_len, int32_t cap, void* stream);
+int st5_ctc_select_sents(const int32_t* frames, int32_t n_slots, int32_t S, int32_t beam, const int32_t* cs, int32_t nc,
+                         const float* log_psi, const float* r_new, const int32_t* parent, const int32_t* tok, int32_t tok_ld,
+                         const uint8_t* ignore, const int32_t* pos, const int32_t* maxlen, const int32_t* done, const int32_t* moved,
+                         int32_t cap, float* state, float* prev, int32_t* unknown, void* stream);
+int st5_ctc_sents_admit(const int32_t* desc, int32_t n_admit, int32_t n_slots, int32_t beam, const float* x, int32_t S, int32_t V,
+                        int32_t blank, int32_t* frames, float* state, float* prev, int32_t* unknown, void* stream);
 /* ---- shallow fusion of a language model in the device-stepped beam search (csrc/beam_lm.hip), step = *counter in [0, max_len], nothing
  * is written outside it.  lm_logits [rows][lm_ld] in `lm_dtype` (ST5_F32 / ST5_BF16), V_lm <= V; lp [rows][lp_ld] fp32.
  * st5_beam_lm_logprobs, logits != NULL: lp[r][c] = (logits[r][c] / temperature - max) - log(sum), st5_beam_ctc_candidates' lp (the

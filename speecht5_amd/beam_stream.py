@@ -2,8 +2,8 @@
 is stepped by ONE step program (step_program.py), enqueued kernel by kernel ("device") or captured once and replayed until the stream
 ends ("graph"); a slot whose sentence has finished is handed to the next waiting request at a poll.  generate(decode="device" /
 "graph") keeps every sentence of a call in the batch until the last one has finished (beam_graph.py), so a call costs max(steps) per
-sentence; the stream costs mean(steps), as the synthesis stream does for TTS (tts_stream.py).  Attention-only search: ctc_weight = 0,
-no LM (the ST recipe and ASR decoding without CTC).
+sentence; the stream costs mean(steps), as the synthesis stream does for TTS (tts_stream.py).  No LM.  Attention-only search (the ST
+recipe and ASR decoding without CTC) by default; joint CTC / attention scoring with generate_stream(joint_ctc=True), see below.
 
 What makes it possible is that every position-dependent launch of the step reads the position of the SLOT where beam_graph's step
 reads one counter: the pre-net row (st5_beam_embed_sents), the self-attention K|V slot write (st5_gemm_skinny_rows over pos_rows), the
@@ -27,7 +27,25 @@ Order of work at a poll, all on the one decode stream:
 A result does not depend on the slot, the admission tick or the neighbours: hypothesis rows never read another slot's rows (the
 GEMMs, the LayerNorms and the attentions are per row or per sentence, the beam step per sentence), and it is bit-equal to
 generate(decode="graph", exact_rows=True) on the sentence alone as long as the cross-attention's key split, a function of S alone
-(csrc/beam_decode.hip), is the same: up to 64 encoder positions per slot there is one range whatever S is."""
+(csrc/beam_decode.hip), is the same: up to 64 encoder positions per slot there is one range whatever S is.
+
+Joint CTC / attention scoring (joint_ctc=True; ctc_weight > 0 with ctc_rows=True): the step program becomes beam_graph.py's CTC step
+with every launch in its per-slot form: pre-net row, layers, projection, st5_beam_ctc_candidates_sents, st5_ctc_prefix_score_rows_sents,
+st5_beam_step_sents_logprobs on the mixed log-probabilities, st5_ctc_select_sents, st5_beam_reorder_sents (csrc/beam_ctc.hip; buffers:
+functional.BeamCtcStreamState).  Slot s has its own slice of the posterior x [n_slots, S, V], its own frame count frames[s] and its own
+rows of every CTC buffer; no kernel reads another slot's.  A request's posterior is the log-softmax of the CTC projection of ITS OWN
+encoder call (_encode: forward_encoder(exact_rows=True) on the sentence alone, T rows through the projection's GEMM), which is the call
+shape of generate(exact_rows=True) on that sentence alone, padded or not: forward_encoder_rows strips a row's padding before the
+encoder, so the single call's projection has the same T rows and BeamDeviceDecode._ctc_state sees the same bits.  An admission copies
+the posterior into the slot's slice and launches st5_ctc_sents_admit behind st5_beam_sents_admit (frames, the initial prefix states,
+prev = 0, unknown = 0).  Without joint_ctc the launch list is what it is without this paragraph.
+
+Joint scoring brings a per-sentence failure: a hypothesis continued by a token outside its CTC candidates has no prefix state
+(_generate raises KeyError for the call).  Here the flag is per slot (`unknown` [n_slots]), read at every poll beside the state image.
+A flagged slot yields nothing, finished or not: its key goes to stream.failed and beam_stream_stats["failed"], its occupant is cleared
+and the slot is handed on like a finished one (the admission clears the flag; if nobody waits the slot runs on to its limit and is
+never read).  When the stream ends the failed keys are raised in one KeyError (with the refusals' text when there are any); every other
+sentence has completed by then."""
 import collections
 import time
 
@@ -47,12 +65,22 @@ def step_limit(gen, src_len, max_len=None):
     return int(max_len) if max_len is not None else min(int(gen.max_len_a * src_len + gen.max_len_b), gen.max_len - 1)
 
 
-def check_arguments(gen, sentences, max_src_len, decode):
+def check_arguments(gen, sentences, max_src_len, decode, joint_ctc=False):
     """The refusals that need no request: a ValueError naming the option, before anything is enqueued."""
     if decode not in STREAM_MODES:
         raise ValueError(f"decode must be one of {STREAM_MODES} for a stream (the other loops have a host step index), got {decode!r}")
-    if gen.ctc_weight > 0:
-        raise ValueError("generate_stream: ctc_weight > 0 is not supported (the CTC prefix scorer has no per-sentence form); use generate()")
+    if joint_ctc:
+        if not gen.ctc_weight > 0:
+            raise ValueError(f"generate_stream: joint_ctc=True needs a generator with ctc_weight > 0, got ctc_weight={gen.ctc_weight}")
+        if not gen.ctc_rows:
+            raise ValueError("generate_stream: joint_ctc=True needs ctc_rows=True (every slot is scored against its own sentence's CTC "
+                             "posterior; the first-sentence scoring of ctc_rows=False is decode='slots' only)")
+        enc = getattr(gen.model.models[0], "encoder", None)
+        if getattr(enc, "proj", None) is None:
+            raise ValueError("generate_stream: joint_ctc=True needs a model whose encoder has a CTC projection")
+    elif gen.ctc_weight > 0:
+        raise ValueError("generate_stream: ctc_weight > 0 needs joint_ctc=True (joint CTC / attention scoring per sentence slot; a "
+                         "sentence whose hypothesis leaves its CTC candidates then fails by key, see generate_stream) or generate()")
     if gen.lm_model is not None:
         raise ValueError("generate_stream: lm_model is not supported (the LM's step has no per-sentence form); use generate()")
     beam_graph.check_generator(gen)
@@ -78,7 +106,7 @@ class BeamStreamDecode:
     """Every buffer of a stream and its one step program: n_slots slots x beam rows over at most S encoder positions and step limits
     up to `cap`.  It outlives the graph that has its buffers baked in."""
 
-    def __init__(self, gen, model, n_slots, S, cap, device):
+    def __init__(self, gen, model, n_slots, S, cap, device, joint_ctc=False):
         beam, V = gen.beam_size, gen.vocab_size
         dec, pre, post = model.decoder, model.text_decoder_prenet, model.text_decoder_postnet
         dev, dtype = device, Fn.compute_dtype()
@@ -96,6 +124,13 @@ class BeamStreamDecode:
         self.desc_host = torch.zeros(n_slots, 4, dtype=torch.int32, pin_memory=True)
         self.desc = torch.zeros(n_slots, 4, **i32)
         self.event = torch.cuda.Event()
+        self.ctc = self.unknown_host = None
+        if joint_ctc:                               # (nc as BeamDeviceDecode._ctc_state computes it)
+            from .sequence_generator import CTC_SCORING_RATIO
+            V_ctc = model.encoder.proj.weight.shape[0]
+            nc = self.ctc_beam = min(V_ctc - gen.mask_idxs.numel(), int(beam * CTC_SCORING_RATIO))
+            self.ctc = Fn.BeamCtcStreamState(bs, S, V_ctc, nc, gen.ctc_weight, gen.blank, gen.eos, dev)
+            self.unknown_host = torch.zeros(n_slots, dtype=torch.int32, pin_memory=True)
         # self-attention slot caches and the encoder side once per slot, zero-filled: no excluded key and no idle row ever holds
         # non-finite bits; all keys valid in idle slots
         self.kv = [torch.zeros(rows, Tmax, 2 * C, dtype=dtype, device=dev) for _ in layers]
@@ -134,20 +169,31 @@ class BeamStreamDecode:
         proj = post.output_projection
         self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
         rules = dict(temperature=gen.temperature, pad=gen.pad, unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len)
-        add(lambda: Fn.beam_step_sents(self.logits, V, bs, self.never, self.len_div, **rules))
+        if self.ctc is None:
+            add(lambda: Fn.beam_step_sents(self.logits, V, bs, self.never, self.len_div, **rules))
+        else:
+            # beam_graph.py's CTC step per slot: log-probabilities and candidates, prefix scores mixed into them, the beam step on
+            # them, the continued rows' prefix states
+            ctc = self.ctc
+            add(lambda: Fn.beam_ctc_candidates_sents(self.logits, V, bs, ctc, self.never, gen.temperature))
+            add(lambda: Fn.ctc_prefix_score_rows_sents(bs, ctc))
+            add(lambda: Fn.beam_step_sents_logprobs(ctc.lp, V, bs, self.never, self.len_div, **rules))
+            add(lambda: Fn.ctc_select_sents(bs, ctc))
         add(lambda: Fn.beam_reorder_sents(bs))
         prog.finish()
 
     def buffer_ptrs(self):
         """Data pointers of what the graph has baked in and must never move: slot K/V, encoder-side K|V, key-padding bytes, the
-        beam-step state, its image and the records."""
+        beam-step state, its image and the records; with joint_ctc the CTC buffers."""
         bs = self.bs
+        ctc = () if self.ctc is None else tuple(t.data_ptr() for t in self.ctc.buffers())
         return tuple(t.data_ptr() for t in self.kv) + tuple(kv.data_ptr() for kv, _ in self.xkv) + tuple(
-            t.data_ptr() for t in (self.kpm, bs.anc, bs.tok, bs.score, bs.image, bs.pos_rows, bs.rec_tok, bs.rec_pos, self.logits))
+            t.data_ptr() for t in (self.kpm, bs.anc, bs.tok, bs.score, bs.image, bs.pos_rows, bs.rec_tok, bs.rec_pos, self.logits)) + ctc
 
     def admit(self, pairs, bos):
         """pairs: [(slot, request)].  Per request the K|V projection of its encoder rows (the single call's GEMM shape) into the slot's
-        slice of the encoder-side buffers and a zero fill behind its frames; then one launch that resets the slots' state."""
+        slice of the encoder-side buffers and a zero fill behind its frames; then one launch that resets the slots' state.  With
+        joint_ctc the request's CTC posterior goes into the slot's slice of ctc.x and a second launch resets the slots' CTC state."""
         S = self.S
         for i, (s, q) in enumerate(pairs):
             T = q["T"]
@@ -155,17 +201,24 @@ class BeamStreamDecode:
                 dst[s * S:s * S + T].copy_(Fn.linear(q["enc"], weights, biases))
                 if T < S:
                     dst[s * S + T:(s + 1) * S].zero_()
+            if self.ctc is not None:
+                self.ctc.x[s, :T].copy_(q["post"])
             self.desc_host[i, 0], self.desc_host[i, 1], self.desc_host[i, 2], self.desc_host[i, 3] = s, q["max_len"], T, bos
         self.desc.copy_(self.desc_host, non_blocking=True)
         Fn.beam_sents_admit(self.desc, len(pairs), self.bs, self.kpm)
+        if self.ctc is not None:
+            Fn.ctc_sents_admit(self.desc, len(pairs), self.bs, self.ctc)
 
     def poll(self):
         """The state image after the steps enqueued so far (one pinned non-blocking copy and an event): pos, maxlen, done, moved,
-        n_hyp, rec_len, rec_score as host views."""
+        n_hyp, rec_len, rec_score as host views, and the CTC scorer's per-slot `unknown` flags (None without joint_ctc), read where the
+        image is read."""
         self.host.copy_(self.bs.image, non_blocking=True)
+        if self.ctc is not None:
+            self.unknown_host.copy_(self.ctc.unknown, non_blocking=True)
         self.event.record()
         self.event.synchronize()
-        return self.bs.unpack_image(self.host)
+        return self.bs.unpack_image(self.host) + (self.unknown_host,)
 
     def copy_out(self, s):
         """Device copies of slot s's records, enqueued in front of whatever overwrites them."""
@@ -177,14 +230,17 @@ class BeamStreamDecode:
 class BeamStream:
     """The loop.  advance() is one poll: it returns [(key, hyps)] of the sentences found finished there, in slot order."""
 
-    def __init__(self, gen, requests, sentences, max_src_len, S, cap, mode):
+    def __init__(self, gen, requests, sentences, max_src_len, S, cap, mode, joint_ctc=False):
         self.gen, self.model, self.requests = gen, gen.model.models[0], iter(requests)
         self.n_slots, self.max_src_len, self.S, self.cap, self.mode = sentences, max_src_len, S, cap, mode
+        self.joint_ctc, self.failed = bool(joint_ctc), []
         self.P = int(gen.BEAM_POLL_STEPS)
         self.st, self.graph = None, None
         self.ready, self.exhausted, self.refused = collections.deque(), False, []
         self.occupant = [None] * sentences
         self.stats = {"polls": 0, "device_steps": 0, "graph_replays": 0, "admitted": 0, "sentence_steps": {}}
+        if self.joint_ctc:
+            self.stats["failed"] = []
         self.inflight, self.finished = False, False
         self.first_ptrs = None
         self.profile = bool(getattr(gen, "beam_profile", False))
@@ -211,11 +267,17 @@ class BeamStream:
         if limit < gen.min_len:
             return f"request {key!r}: max_len {limit} is below min_len={gen.min_len}"
         net_input = {"source": src.unsqueeze(0), "padding_mask": torch.zeros(1, n, dtype=torch.bool, device=src.device)}
-        enc = gen.model.forward_encoder(net_input, exact_rows=True)[0]["encoder_out"][0]          # [T, 1, C]
+        out = gen.model.forward_encoder(net_input, exact_rows=True)[0]
+        enc = out["encoder_out"][0]                                                               # [T, 1, C]
         T = int(enc.size(0))
         if T > self.S or T < 1:
             return f"request {key!r} has {T} encoder positions, outside 1 .. {self.S} (max_src_len={self.max_src_len})"
-        return {"key": key, "T": T, "max_len": limit, "enc": Fn.as_compute(enc[:, 0].contiguous())}
+        q = {"key": key, "T": T, "max_len": limit, "enc": Fn.as_compute(enc[:, 0].contiguous())}
+        if self.joint_ctc:
+            # the posterior [T, V] as BeamDeviceDecode._ctc_state builds it in a call on this sentence alone (module docstring)
+            post = self.model.get_normalized_probs_for_ctc(out, log_probs=True).transpose(0, 1)   # 1 x T x V
+            q["post"] = post.detach().float().contiguous()[0]
+        return q
 
     def _fill_ready(self):
         """Encoder work of the next waiting requests, at most `sentences` of them ahead of their admission."""
@@ -273,13 +335,21 @@ class BeamStream:
     def advance(self):
         st, out = self.st, []
         if self.inflight:
-            pos, _, done, _, n_hyp, rec_len, rec_score = st.poll()
+            pos, _, done, _, n_hyp, rec_len, rec_score, unknown = st.poll()
             self.stats["polls"] += 1
             self.inflight = False
             beam = st.beam
             for s in range(self.n_slots):                                    # 1. copy-out, in slot order
                 q = self.occupant[s]
-                if q is None or not int(done[s]):
+                if q is None:
+                    continue
+                if unknown is not None and int(unknown[s]):
+                    # a hypothesis left its CTC candidates: the sentence fails, finished or not, and its slot is handed on
+                    self.failed.append(q["key"])
+                    self.stats["failed"].append(q["key"])
+                    self.occupant[s] = None
+                    continue
+                if not int(done[s]):
                     continue
                 b0 = s * beam
                 out.append((q["key"], self._hyps(st.copy_out(s), int(n_hyp[s]), rec_len[b0:b0 + beam].clone(),
@@ -288,7 +358,8 @@ class BeamStream:
                 self.occupant[s] = None
         self._fill_ready()
         if st is None and self.ready:
-            st = self.st = BeamStreamDecode(self.gen, self.model, self.n_slots, self.S, self.cap, self.ready[0]["enc"].device)
+            st = self.st = BeamStreamDecode(self.gen, self.model, self.n_slots, self.S, self.cap, self.ready[0]["enc"].device,
+                                            joint_ctc=self.joint_ctc)
             self.first_ptrs = st.buffer_ptrs()
         free = [s for s in range(self.n_slots) if self.occupant[s] is None]
         pairs = [(s, self.ready[k]) for s, k in assign_rows(free, len(self.ready))]
@@ -324,12 +395,12 @@ class BeamStream:
             g.beam_buffer_ptrs = (self.first_ptrs, self.st.buffer_ptrs())
 
 
-def run_stream(gen, requests, sentences, max_src_len, decode):
+def run_stream(gen, requests, sentences, max_src_len, decode, joint_ctc=False):
     """The generator behind SequenceGenerator.generate_stream.  The argument checks run at the call, not at the first next().  The
     decode stream (step_program.decode_stream for "graph") is entered for each poll and left before anything is yielded, so the
     consumer runs on its own stream between two polls."""
-    S, cap = check_arguments(gen, sentences, max_src_len, decode)
-    return _run(gen, requests, sentences, max_src_len, S, cap, decode)
+    S, cap = check_arguments(gen, sentences, max_src_len, decode, joint_ctc)
+    return _run(gen, requests, sentences, max_src_len, S, cap, decode, joint_ctc)
 
 
 def _tensors(results):
@@ -339,8 +410,8 @@ def _tensors(results):
                 yield t
 
 
-def _run(gen, requests, sentences, max_src_len, S, cap, decode):
-    stream = BeamStream(gen, requests, sentences, max_src_len, S, cap, decode)
+def _run(gen, requests, sentences, max_src_len, S, cap, decode, joint_ctc=False):
+    stream = BeamStream(gen, requests, sentences, max_src_len, S, cap, decode, joint_ctc)
     model = gen.model.models[0]
     device = next(model.parameters()).device
     # The two streams are ordered only where something crosses between them (tts_stream._run): the consumer's stream in front of the
@@ -368,5 +439,10 @@ def _run(gen, requests, sentences, max_src_len, S, cap, decode):
             stream.close()
         if side is not None and side != cur:
             cur.wait_stream(side)
-    if stream.refused:
-        raise ValueError("requests: refused " + "; ".join(stream.refused))
+    refused = "requests: refused " + "; ".join(stream.refused) if stream.refused else ""
+    if stream.failed:
+        # _generate's KeyError, by key: the other sentences have completed
+        raise KeyError(f"sentences {stream.failed!r}: a hypothesis was extended by a token outside its CTC candidate list "
+                       f"(ctc_beam={stream.st.ctc_beam}); its prefix state does not exist" + ("; " + refused if refused else ""))
+    if refused:
+        raise ValueError(refused)

@@ -31,6 +31,8 @@
 // st5_beam_step_sents: the same kernel body with step = pos[s] and max_len = maxlen[s] per workgroup (a template parameter); a slot
 //   whose done flag is set writes moved[s] = 0 and returns before its first load of logits; otherwise stages 1 - 6, then one thread
 //   writes pos[s] + 1, the slot's pos_rows and moved[s] = 1.  No counter, no ticket: no workgroup reads another slot's position.
+// st5_beam_step_sents_logprobs: st5_beam_step_sents on log-probabilities (the CTC-mixed ones of a stream with joint_ctc), as
+//   st5_beam_step_logprobs is st5_beam_step on them.
 // st5_beam_reorder_sents / st5_beam_embed_sents: the two launches above at the slot's own position (the reorder only where moved).
 // st5_beam_sents_admit: hands finished slots to new sentences (state reset, record header emptied, key-padding bytes).
 // Plain vector loads and stores only; the hand-off between the launches of a step is the kernel boundary.
@@ -386,12 +388,12 @@ static int beam_step_launch(int logprobs, const float* logits, int64_t ld, float
   return hipGetLastError() == hipSuccess ? ST5_OK : ST5_ERR_LAUNCH;
 }
 
-extern "C" int st5_beam_step_sents(const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_slots, int32_t beam, int32_t V,
-                                   float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax,
-                                   uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score,
-                                   int32_t* rec_len, int32_t* n_hyp, int32_t* pos, const int32_t* maxlen, int32_t* done, int32_t* moved,
-                                   int32_t* pos_rows, const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos,
-                                   float unk_penalty, int32_t min_len, int32_t cap, void* stream) {
+static int beam_step_sents_launch(int logprobs, const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_slots,
+                                  int32_t beam, int32_t V, float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld,
+                                  int32_t Tmax, uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld,
+                                  float* rec_score, int32_t* rec_len, int32_t* n_hyp, int32_t* pos, const int32_t* maxlen, int32_t* done,
+                                  int32_t* moved, int32_t* pos_rows, const uint8_t* never, const float* len_div, int32_t pad, int32_t unk,
+                                  int32_t eos, float unk_penalty, int32_t min_len, int32_t cap, void* stream) {
   if (!logits || !tok || !score || !anc || !ignore || !parent || !rec_tok || !rec_pos || !rec_score || !rec_len || !n_hyp || !pos ||
       !maxlen || !done || !moved || !pos_rows || !never)
     return ST5_ERR_ARG;
@@ -402,7 +404,7 @@ extern "C" int st5_beam_step_sents(const float* logits, int64_t ld, float* lprob
   if (eos < 0 || eos >= V) return ST5_ERR_ARG;
   BeamStepSentsArgs a;
   a.logits = logits; a.ld = ld; a.lprobs = lprobs_out; a.lp_ld = lp_ld;
-  a.n_sent = n_slots; a.beam = beam; a.V = V; a.Tmax = Tmax; a.temperature = temperature; a.logprobs = 0;
+  a.n_sent = n_slots; a.beam = beam; a.V = V; a.Tmax = Tmax; a.temperature = temperature; a.logprobs = logprobs;
   a.tok = tok; a.score = score; a.anc = anc; a.anc_ld = anc_ld; a.ignore = ignore; a.parent = parent;
   a.rec_tok = rec_tok; a.rec_pos = rec_pos; a.rec_ld = rec_ld; a.rec_score = rec_score; a.rec_len = rec_len;
   a.n_hyp = n_hyp; a.sent_done = done; a.n_finished = nullptr; a.ticket = nullptr; a.counter = nullptr;
@@ -412,6 +414,29 @@ extern "C" int st5_beam_step_sents(const float* logits, int64_t ld, float* lprob
   hipLaunchKernelGGL((beam_step_kernel<true, BeamStepSentsArgs>), dim3(n_slots), dim3(BS_THREADS), 0, reinterpret_cast<hipStream_t>(stream),
                      a);
   return hipGetLastError() == hipSuccess ? ST5_OK : ST5_ERR_LAUNCH;
+}
+
+extern "C" int st5_beam_step_sents(const float* logits, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_slots, int32_t beam, int32_t V,
+                                   float temperature, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax,
+                                   uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld, float* rec_score,
+                                   int32_t* rec_len, int32_t* n_hyp, int32_t* pos, const int32_t* maxlen, int32_t* done, int32_t* moved,
+                                   int32_t* pos_rows, const uint8_t* never, const float* len_div, int32_t pad, int32_t unk, int32_t eos,
+                                   float unk_penalty, int32_t min_len, int32_t cap, void* stream) {
+  return beam_step_sents_launch(0, logits, ld, lprobs_out, lp_ld, n_slots, beam, V, temperature, tok, score, anc, anc_ld, Tmax, ignore, parent,
+                                rec_tok, rec_pos, rec_ld, rec_score, rec_len, n_hyp, pos, maxlen, done, moved, pos_rows, never, len_div, pad,
+                                unk, eos, unk_penalty, min_len, cap, stream);
+}
+
+extern "C" int st5_beam_step_sents_logprobs(const float* lp, int64_t ld, float* lprobs_out, int64_t lp_ld, int32_t n_slots, int32_t beam,
+                                            int32_t V, int32_t* tok, float* score, const int32_t* anc, int64_t anc_ld, int32_t Tmax,
+                                            uint8_t* ignore, int32_t* parent, int32_t* rec_tok, float* rec_pos, int64_t rec_ld,
+                                            float* rec_score, int32_t* rec_len, int32_t* n_hyp, int32_t* pos, const int32_t* maxlen,
+                                            int32_t* done, int32_t* moved, int32_t* pos_rows, const uint8_t* never, const float* len_div,
+                                            int32_t pad, int32_t unk, int32_t eos, float unk_penalty, int32_t min_len, int32_t cap,
+                                            void* stream) {
+  return beam_step_sents_launch(1, lp, ld, lprobs_out, lp_ld, n_slots, beam, V, 1.f, tok, score, anc, anc_ld, Tmax, ignore, parent, rec_tok,
+                                rec_pos, rec_ld, rec_score, rec_len, n_hyp, pos, maxlen, done, moved, pos_rows, never, len_div, pad, unk, eos,
+                                unk_penalty, min_len, cap, stream);
 }
 
 extern "C" int st5_beam_reorder_sents(int32_t* anc, int64_t anc_ld, const int32_t* parent, int32_t n_slots, int32_t beam, int32_t Tmax,

@@ -45,3 +45,27 @@ BST_HD uint8_t bst_kpm_byte(long long j, long long frames) { return j >= frames 
 // element offsets of the admission's writes
 BST_HD long long bst_kpm_off(long long slot, long long S, long long j) { return slot * S + j; }
 BST_HD long long bst_cell_off(long long row, long long ld, long long col) { return row * ld + col; }
+
+// ---- joint CTC / attention scoring per slot (csrc/beam_ctc.hip: st5_beam_ctc_candidates_sents, st5_ctc_prefix_score_rows_sents,
+// st5_ctc_select_sents, st5_ctc_sents_admit; tests/test_beam_stream_ctc_cpu.py sweeps these).  The posterior is x [n_slots][S][V], the
+// prefix states state [rows][S][2], the extensions' states r_new [rows][S][nc][2], log_psi / cs [rows][nc]; frames[s] of a slot's S
+// frames are its sentence's.  Offsets of state and r_new count float2 cells.
+// the slot of a hypothesis row
+BST_HD long long bst_slot_of(long long row, long long beam) { return row / beam; }
+// does a slot take the CTC part of a step?  Not when it is done (finished or idle), and only at the steps the beam step runs
+BST_HD bool bst_ctc_live(long long done, long long pos, long long maxlen) { return done == 0 && bst_step_live(pos, maxlen); }
+// does the select behind a step act on a slot?  Only where that step moved it and wrote continuing rows: the step at the limit
+// writes none, and it leaves pos = maxlen + 1
+BST_HD bool bst_select_live(long long moved, long long pos, long long maxlen) { return moved != 0 && pos >= 1 && pos <= maxlen; }
+// a parent row read from device memory: it must lie inside the row's own slot, so no slot reads another's extensions
+BST_HD bool bst_parent_ok(long long parent, long long slot, long long beam) {
+  return parent >= bst_row0(slot, beam) && parent < bst_row0(slot, beam) + beam;
+}
+// a candidate token read from device memory
+BST_HD bool bst_token_ok(long long token, long long V) { return token >= 0 && token < V; }
+// element offsets: the slot's posterior, a row's prefix state, a row's extension by candidate c at frame 0 (frame f: + f * nc), a
+// row's candidate cell
+BST_HD long long bst_x_off(long long slot, long long S, long long V) { return slot * S * V; }
+BST_HD long long bst_state_off(long long row, long long S) { return row * S; }
+BST_HD long long bst_rnew_off(long long row, long long S, long long nc, long long c) { return row * S * nc + c; }
+BST_HD long long bst_cand_off(long long row, long long nc, long long j) { return row * nc + j; }

@@ -86,17 +86,7 @@ __global__ void ctc_prefix_score_kernel(const float* __restrict__ x, int T, int 
 __global__ void ctc_initial_state_rows_kernel(const float* __restrict__ x, const int* __restrict__ lens, int Tmax, int V, int blank,
                                               float* __restrict__ r) {
   const int s = blockIdx.x;
-  int T = lens[s];
-  T = T < 0 ? 0 : (T > Tmax ? Tmax : T);
-  const float* xs = x + (long long)s * Tmax * V;
-  float2* rs = reinterpret_cast<float2*>(r) + (long long)s * Tmax;
-  for (int t = T + threadIdx.x; t < Tmax; t += blockDim.x) rs[t] = make_float2(LOGZERO, LOGZERO);
-  if (threadIdx.x != 0) return;
-  float acc = 0.f;
-  for (int t = 0; t < T; ++t) {
-    acc = t == 0 ? xs[blank] : acc + xs[(long long)t * V + blank];
-    rs[t] = make_float2(LOGZERO, acc);
-  }
+  ctc_rows::initial_state(x + (long long)s * Tmax * V, lens[s], Tmax, V, blank, reinterpret_cast<float2*>(r) + (long long)s * Tmax);
 }
 
 __global__ void __launch_bounds__(1024)

@@ -19,6 +19,20 @@ __device__ __forceinline__ float logaddexp_sel(float a, float b) {
   return a == b ? a + 0.693147180559945309417232121458176568f : g;
 }
 
+// The initial prefix state of one sentence, by the threads of one block: rs[t] = (LOGZERO, sum_{u<=t} xs[u][blank]) for t < T, summed
+// in frame order by thread 0; (LOGZERO, LOGZERO) for T <= t < Tmax.  T is brought into [0, Tmax] here.  Shared by
+// ctc_initial_state_rows_kernel (ctc_prefix.hip) and the stream's admission (beam_ctc.hip: ctc_sents_admit_kernel).
+__device__ __forceinline__ void initial_state(const float* __restrict__ xs, int T, int Tmax, int V, int blank, float2* __restrict__ rs) {
+  T = T < 0 ? 0 : (T > Tmax ? Tmax : T);
+  for (int t = T + threadIdx.x; t < Tmax; t += blockDim.x) rs[t] = make_float2(LOGZERO, LOGZERO);
+  if (threadIdx.x != 0) return;
+  float acc = 0.f;
+  for (int t = 0; t < T; ++t) {
+    acc = t == 0 ? xs[blank] : acc + xs[(long long)t * V + blank];
+    rs[t] = make_float2(LOGZERO, acc);
+  }
+}
+
 constexpr int ROWS_SEG = 2048;            // frames per LDS segment
 constexpr int ROWS_U = 16;                // frames per prefetched chunk
 constexpr int ROWS_REP = ROWS_SEG + 4;    // offset of the repeat form in phi_s (+4: the two forms never share a bank slot)

@@ -4134,6 +4134,99 @@ def ctc_select_dev(bs, ctc):
 
 
 # -------------------------------------------------------------------------------------------------
+# Joint CTC / attention scoring PER SENTENCE SLOT (st5_*_sents in csrc/beam_ctc.hip, st5_beam_step_sents_logprobs): the CTC part of
+# the step of a beam-search stream (beam_stream.py, joint_ctc).  Slot s's bits are those of the scalar forms above at step pos[s].
+# -------------------------------------------------------------------------------------------------
+class BeamCtcStreamState:
+    """Device state of the CTC part of a stream's step, beside BeamStreamState `bs`: x fp32 [n_slots, S, V] (slot s's posterior over
+    its frames[s] <= S frames, zero-filled here and written at admission), frames int32 [n_slots], state [rows, S, 2], r_new [rows, S,
+    nc, 2], log_psi [rows, nc], prev [rows], cs int32 [rows, nc], lp [rows, V], unknown int32 [n_slots] (per slot).  ValueError when
+    r_new would exceed BEAM_CTC_MAX_STATE_BYTES: a stream holds S frames of state per slot whatever its sentences' lengths."""
+
+    def __init__(self, bs, S, V, nc, ctc_weight, blank, eos, device):
+        rows, n_slots = bs.rows, bs.n_slots
+        if not 0 < nc <= min(BEAM_CTC_MAX_CANDIDATES, V):
+            raise ValueError(f"{nc} CTC candidates per row: the device scorer takes 1 .. min({BEAM_CTC_MAX_CANDIDATES}, V = {V})")
+        nbytes = rows * S * nc * 8
+        if nbytes > BEAM_CTC_MAX_STATE_BYTES:
+            raise ValueError(f"the CTC extension states of sentences={n_slots} x beam_size={bs.beam} rows x {S} encoder positions "
+                             f"(max_src_len) x {nc} candidates take {nbytes} bytes, more than the {BEAM_CTC_MAX_STATE_BYTES} a stream "
+                             f"allows; lower sentences or max_src_len")
+        f32, i32 = dict(dtype=torch.float32, device=device), dict(dtype=torch.int32, device=device)
+        self.n_slots, self.beam, self.rows, self.S, self.V, self.nc = n_slots, bs.beam, rows, int(S), int(V), int(nc)
+        self.ctc_weight, self.blank, self.eos = float(ctc_weight), int(blank), int(eos)
+        self.x = torch.zeros(n_slots, S, V, **f32)
+        self.frames = torch.zeros(n_slots, **i32)
+        self.state = torch.full((rows, S, 2), -10000000000.0, **f32)      # (LOGZERO: an idle slot has no frames)
+        self.r_new = torch.empty(rows, S, nc, 2, **f32)                   # (written by a step before its select reads it)
+        self.log_psi = torch.zeros(rows, nc, **f32)
+        self.prev = torch.zeros(rows, **f32)
+        self.cs = torch.zeros(rows, nc, **i32)
+        self.lp = torch.zeros(rows, V, **f32)
+        self.unknown = torch.zeros(n_slots, **i32)
+
+    def buffers(self):
+        return (self.x, self.frames, self.state, self.r_new, self.log_psi, self.prev, self.cs, self.lp, self.unknown)
+
+
+def beam_ctc_candidates_sents(logits, V, bs, ctc, never, temperature):
+    """beam_ctc_candidates per slot: ctc.lp / ctc.cs of the rows of every slot that is not done, at its own step bs.pos[s]."""
+    assert logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == bs.rows == ctc.rows and logits.shape[1] >= V
+    assert never.dtype == torch.uint8 and never.is_contiguous() and never.numel() == V == ctc.V
+    hip.check(hip.lib().st5_beam_ctc_candidates_sents(logits.data_ptr(), logits.stride(0), bs.n_slots, bs.beam, int(V), float(temperature),
+                                                      never.data_ptr(), bs.pos.data_ptr(), bs.maxlen.data_ptr(), bs.done.data_ptr(),
+                                                      bs.cap, ctc.lp.data_ptr(), ctc.lp.stride(0), ctc.cs.data_ptr(), ctc.nc,
+                                                      hip.stream()), "st5_beam_ctc_candidates_sents")
+
+
+def ctc_prefix_score_rows_sents(bs, ctc):
+    """ctc_prefix_score_rows_dev per slot: out_len = bs.pos[s], last = bs.tok[r, pos[s]], T = ctc.frames[s], and the mix into ctc.lp."""
+    assert bs.rows == ctc.rows and bs.tok.dtype == torch.int32 and bs.tok.is_contiguous()
+    hip.check(hip.lib().st5_ctc_prefix_score_rows_sents(ctc.x.data_ptr(), ctc.frames.data_ptr(), bs.n_slots, ctc.S, ctc.V, ctc.blank, ctc.eos,
+                                                        bs.beam, ctc.state.data_ptr(), bs.tok.data_ptr(), bs.Tmax, bs.pos.data_ptr(),
+                                                        bs.maxlen.data_ptr(), bs.done.data_ptr(), bs.cap, ctc.cs.data_ptr(), ctc.nc,
+                                                        ctc.log_psi.data_ptr(), ctc.r_new.data_ptr(), ctc.prev.data_ptr(), ctc.lp.data_ptr(),
+                                                        ctc.lp.stride(0), ctc.ctc_weight, hip.stream()), "st5_ctc_prefix_score_rows_sents")
+
+
+def beam_step_sents_logprobs(lp, V, st, never, len_div, *, pad, unk, eos, unk_penalty, min_len, lprobs=None, temperature=None):
+    """beam_step_sents on log-probabilities (st5_beam_step_sents_logprobs): no log-softmax; `temperature` has been applied by whoever
+    made them and is not used."""
+    assert lp.dtype == torch.float32 and lp.stride(1) == 1 and lp.shape[0] == st.rows and lp.shape[1] >= V
+    assert never.dtype == torch.uint8 and never.is_contiguous() and never.numel() == V
+    assert len_div is None or (len_div.dtype == torch.float32 and len_div.is_contiguous() and len_div.numel() >= st.cap + 1)
+    assert lprobs is None or (lprobs.dtype == torch.float32 and lprobs.stride(1) == 1 and lprobs.shape[0] == st.rows and lprobs.shape[1] >= V)
+    hip.check(hip.lib().st5_beam_step_sents_logprobs(
+        lp.data_ptr(), lp.stride(0), hip.ptr(lprobs), 0 if lprobs is None else lprobs.stride(0), st.n_slots, st.beam, int(V),
+        st.tok.data_ptr(), st.score.data_ptr(), st.anc.data_ptr(), st.anc.stride(0), st.Tmax, st.ignore.data_ptr(),
+        st.parent.data_ptr(), st.rec_tok.data_ptr(), st.rec_pos.data_ptr(), st.rec_tok.stride(0), st.rec_score.data_ptr(),
+        st.rec_len.data_ptr(), st.n_hyp.data_ptr(), st.pos.data_ptr(), st.maxlen.data_ptr(), st.done.data_ptr(), st.moved.data_ptr(),
+        st.pos_rows.data_ptr(), never.data_ptr(), hip.ptr(len_div), int(pad), int(unk), int(eos), float(unk_penalty), int(min_len),
+        st.cap, hip.stream()), "st5_beam_step_sents_logprobs")
+
+
+def ctc_select_sents(bs, ctc):
+    """Behind beam_step_sents_logprobs: ctc.state / ctc.prev of the continued rows of the slots that step moved; ctc.unknown[s] is set
+    when a row of slot s that still counts was continued by a token outside its parent's candidates."""
+    assert bs.rows == ctc.rows
+    hip.check(hip.lib().st5_ctc_select_sents(ctc.frames.data_ptr(), bs.n_slots, ctc.S, bs.beam, ctc.cs.data_ptr(), ctc.nc,
+                                             ctc.log_psi.data_ptr(), ctc.r_new.data_ptr(), bs.parent.data_ptr(), bs.tok.data_ptr(), bs.Tmax,
+                                             bs.ignore.data_ptr(), bs.pos.data_ptr(), bs.maxlen.data_ptr(), bs.done.data_ptr(),
+                                             bs.moved.data_ptr(), bs.cap, ctc.state.data_ptr(), ctc.prev.data_ptr(),
+                                             ctc.unknown.data_ptr(), hip.stream()), "st5_ctc_select_sents")
+
+
+def ctc_sents_admit(desc, n_admit, bs, ctc):
+    """Behind beam_sents_admit, over the same descriptors: ctc.frames[slot], the slot's prefix states (the initial state of its slice of
+    ctc.x, which the caller has written), prev = 0 and unknown[slot] = 0."""
+    assert desc.dtype == torch.int32 and desc.is_contiguous() and desc.shape[1] == 4 and desc.shape[0] >= n_admit
+    assert bs.rows == ctc.rows and bs.n_slots == ctc.n_slots
+    hip.check(hip.lib().st5_ctc_sents_admit(desc.data_ptr(), int(n_admit), bs.n_slots, bs.beam, ctc.x.data_ptr(), ctc.S, ctc.V, ctc.blank,
+                                            ctc.frames.data_ptr(), ctc.state.data_ptr(), ctc.prev.data_ptr(), ctc.unknown.data_ptr(),
+                                            hip.stream()), "st5_ctc_sents_admit")
+
+
+# -------------------------------------------------------------------------------------------------
 # Shallow fusion of a language model behind the step counter (csrc/beam_lm.hip).
 # -------------------------------------------------------------------------------------------------
 def beam_lm_logprobs(lp, V, bs, lm_logits, lm_weight, logits=None, temperature=1.0):

@@ -290,6 +290,19 @@ _SIGS = {
                                               c_int64, c_double, c_void_p]),
     "st5_ctc_select_dev": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
                                    c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "st5_beam_ctc_candidates_sents": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_int32, c_void_p, c_int64, c_void_p, c_int32, c_void_p]),
+    "st5_ctc_prefix_score_rows_sents": (c_int, [c_void_p, c_void_p, c_int32, c_int32, c_int32, c_int32, c_int32, c_int32, c_void_p,
+                                                c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int32, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_int64, c_double, c_void_p]),
+    "st5_beam_step_sents_logprobs": (c_int, [c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                             c_int64, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_int32,
+                                             c_int32, c_float, c_int32, c_int32, c_void_p]),
+    "st5_ctc_select_sents": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p, c_int32,
+                                     c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "st5_ctc_sents_admit": (c_int, [c_void_p, c_int32, c_int32, c_int32, c_void_p, c_int32, c_int32, c_int32, c_void_p, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
     "st5_beam_embed_step": (c_int, [c_void_p, c_int32, c_void_p, c_int32, c_void_p, c_void_p, c_int32, c_int32, c_float, c_void_p, c_int64,
                                     c_int32, c_int32, c_int, c_void_p]),
     "st5_beam_lm_logprobs": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_int64, c_int32, c_float, c_int, c_void_p,

@@ -253,7 +253,7 @@ class SequenceGenerator(nn.Module):
         """fairseq generator API: `models` is ignored (the ensemble was fixed at construction, :192-205)."""
         return self._generate(sample, **kwargs)
 
-    def generate_stream(self, requests, *, sentences, max_src_len, decode="graph"):
+    def generate_stream(self, requests, *, sentences, max_src_len, decode="graph", joint_ctc=False):
         """Streaming beam search (beam_stream.py): a Python generator over `requests`, an iterable of (key, source) or (key, source,
         max_len) with `source` one fp32 waveform [n]; yields (key, hyps) in completion order (sentences that finish at the same poll
         in slot order), hyps as generate() returns them for one sentence in the "device" / "graph" modes.  `sentences` slots of
@@ -262,11 +262,17 @@ class SequenceGenerator(nn.Module):
         is encoded alone, as generate(exact_rows=True) encodes a row; `max_src_len` (samples) fixes the encoder positions per slot;
         the step limit of a request is min(int(max_len_a * n + max_len_b), max_len - 1) on its own length n, or its max_len, and at
         most that formula at max_src_len.  A request that is too long, whose max_len is above that cap, or whose source is not
-        floating point is refused by key when the stream ends (ValueError); the others complete.  Attention-only search: ctc_weight >
-        0, lm_model and everything the device-stepped modes refuse raise a ValueError naming the option, at the call.  The
-        generator's own `decode` does not matter here, and nothing about generate() changes."""
+        floating point is refused by key when the stream ends (ValueError); the others complete.  Attention-only search by
+        default: ctc_weight > 0 without `joint_ctc`, lm_model and everything the device-stepped modes refuse raise a ValueError naming
+        the option, at the call.  `joint_ctc=True` (needs ctc_weight > 0, ctc_rows=True and an encoder CTC projection): joint CTC /
+        attention scoring per sentence slot, bit-equal to generate(decode="graph", exact_rows=True, ctc_rows=True) on the sentence
+        alone.  It brings a per-sentence failure the attention-only stream does not have: a sentence one of whose hypotheses was
+        continued by a token outside its CTC candidate list yields nothing; its key is collected (beam_stream_stats["failed"]), its
+        slot is handed on, and when the stream ends a KeyError names the failed keys and ctc_beam (and carries the refusals' text, if
+        any); all other sentences have completed by then.  The generator's own `decode` does not matter here, and nothing about
+        generate() changes."""
         from . import beam_stream
-        return beam_stream.run_stream(self, requests, sentences, max_src_len, decode)
+        return beam_stream.run_stream(self, requests, sentences, max_src_len, decode, joint_ctc)
 
     # -------------------------------------------------------------------------------------------
     def _never(self, lprobs):

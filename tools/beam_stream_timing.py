@@ -18,7 +18,16 @@ Reported per arm: sentences per second and total steps (device steps + graph rep
 Per-step cost: `slots` clips of 10 s through the stream's per-sentence program and through the scalar program of beam_graph.py (the
 parent commit's step, unchanged) at the same rows and limits, HIP events around every group of steps between two polls.
 
-    python tools/beam_stream_timing.py [--reps 5] [--json profiles/beam_stream_timing.json]"""
+--joint-ctc: the same workload and arms with joint CTC / attention scoring (ctc_weight 0.5, ctc_rows=True): the stream is
+generate_stream(joint_ctc=True), the batch arms are generate(decode="graph", ctc_rows=True), the per-step comparison is the per-slot
+CTC step against the scalar CTC step of beam_graph.py at the same rows.  A random model's next-token distribution is nearly flat, and
+under a flat distribution a hypothesis soon leaves its 7 x beam CTC candidates (tools/beam_ctc_timing.py); --temperature (the same
+for every arm) sharpens it, the values are tried in order and the first under which no arm raises the generator's KeyError is
+measured and recorded with the ones that raised; a configuration under which every temperature raises is reported and the tool exits
+non-zero.
+
+    python tools/beam_stream_timing.py [--reps 5] [--json profiles/beam_stream_timing.json]
+    python tools/beam_stream_timing.py --joint-ctc [--temperature 0.25 0.05] [--json profiles/beam_stream_ctc_timing.json]"""
 import argparse
 import json
 import os
@@ -58,13 +67,19 @@ def clips(dev, seed=64):
     return [(i, wav[i, :m].clone()) for i, m in enumerate(n)], n
 
 
-def generator(model, d, beam, decode="concat"):
+CTC_WEIGHT = 0.5
+
+
+def generator(model, d, beam, decode="concat", joint_ctc=False, temperature=1.0):
     from speecht5_amd.sequence_generator import SequenceGenerator
-    return SequenceGenerator([model], d, beam_size=beam, max_len_a=STEPS_PER_SECOND / RATE, max_len_b=0, exact_rows=True, decode=decode)
+    ctc = dict(ctc_weight=CTC_WEIGHT, ctc_rows=True, temperature=temperature) if joint_ctc else {}
+    return SequenceGenerator([model], d, beam_size=beam, max_len_a=STEPS_PER_SECOND / RATE, max_len_b=0, exact_rows=True, decode=decode,
+                             **ctc)
 
 
 def stream_arm(gen, reqs, slots):
-    n = sum(1 for _ in gen.generate_stream(reqs, sentences=slots, max_src_len=MAX_S * RATE, decode="graph"))
+    kw = dict(joint_ctc=True) if gen.ctc_weight > 0 else {}
+    n = sum(1 for _ in gen.generate_stream(reqs, sentences=slots, max_src_len=MAX_S * RATE, decode="graph", **kw))
     assert n == len(reqs)
     st = gen.beam_stream_stats
     return gen.beam_device_steps + gen.beam_graph_replays, gen.beam_polls, st.get("step_ms", 0.0), st.get("steps_timed", 0), dict(st["sentence_steps"])
@@ -105,6 +120,8 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--json", default=None)
+    ap.add_argument("--joint-ctc", action="store_true")
+    ap.add_argument("--temperature", type=float, nargs="+", default=[0.25, 0.05])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model, d = build_model(dev, torch.bfloat16)
@@ -113,70 +130,96 @@ def main():
     reqs, n = clips(dev)
     by_len = sorted(reqs, key=lambda q: q[1].numel())
     limits = [int(STEPS_PER_SECOND / RATE * m) for m in n]
-    results = []
+    results, failed = [], []
     with torch.no_grad():
         for beam, slots in CONFIGS:
-            gs, gb = generator(model, d, beam), generator(model, d, beam, "graph")
-            P = gs.BEAM_POLL_STEPS
-            arms = {"stream": lambda: stream_arm(gs, reqs, slots), "batch": lambda: batch_arm(gb, reqs, slots),
-                    "batch_sorted": lambda: batch_arm(gb, by_len, slots)}
-            steps, polls, times = {}, {}, {k: [] for k in arms}
-            for name, fn in arms.items():                  # warm-up; every sentence of the stream runs to its own limit
-                _, (steps[name], polls[name], _, _, per_sentence) = timed(fn)
-                if per_sentence is not None:
-                    assert per_sentence == {i: m + 1 for i, m in enumerate(limits)}, "a sentence ended before its limit"
-            assert steps["stream"] == stream_schedule([m + 1 for m in limits], slots, P)[0]
-            for rep in range(a.reps):
-                for name, fn in arms.items():
-                    dt, out = timed(fn)
-                    assert out[0] == steps[name]
-                    times[name].append(dt)
-                print(f"# beam {beam} x {slots}, repeat {rep + 1}: " + ", ".join(f"{k} {v[-1]:.4f} s" for k, v in times.items()), flush=True)
-            gs.beam_profile = True                         # one more stream call with HIP events around every group of steps
-            try:
-                dt, (_, _, step_ms, timed_n, _) = timed(arms["stream"])
-            finally:
-                gs.beam_profile = False
-            for name in arms:
-                med = statistics.median(times[name])
-                r = dict(kind="throughput", arm=name, dtype="bf16", beam=beam, slots=slots, clips=N_CLIPS, seconds=[min(n) // RATE, max(n) // RATE],
-                         sum_steps=sum(m + 1 for m in limits), poll_steps=P, steps=steps[name], polls=polls[name],
-                         sentences_per_s=round(N_CLIPS / med, 3), call_s=[round(t, 4) for t in times[name]], call_s_median=round(med, 4),
-                         ms_per_step=round(med / steps[name] * 1e3, 4))
-                if name == "stream":
-                    r.update(profiled_call_s=round(dt, 4), steps_only_s=round(step_ms * 1e-3, 4),
-                             steps_only_ms_per_step=round(step_ms / max(timed_n, 1), 4),
-                             overhead_ms_per_poll=round((dt - step_ms * 1e-3) / max(polls[name], 1) * 1e3, 4))
-                results.append(r)
-                print(json.dumps(r), flush=True)
-
-            # ---- per-step cost: the per-sentence program against the scalar program, `slots` clips of 10 s, the same rows ----
-            wav, pad = batch([10 * RATE] * slots, dev, seed=7)
-            same = [(b, wav[b]) for b in range(slots)]
-            sample = {"net_input": {"source": wav, "padding_mask": pad}}
-            per = {"per_sentence": [], "scalar": []}
-            timed_n = {}
-            gs.beam_profile = True
-            try:
-                for rep in range(a.reps + 1):              # (the first round is the warm-up)
-                    list(gs.generate_stream(same, sentences=slots, max_src_len=10 * RATE, decode="graph"))
-                    st = gs.beam_stream_stats
-                    ms, k = scalar_steps(gb, model, sample, slots)
-                    if rep:
-                        per["per_sentence"].append(st["step_ms"] / st["steps_timed"])
-                        per["scalar"].append(ms / k)
-                        timed_n = {"per_sentence": st["steps_timed"], "scalar": k}
-            finally:
-                gs.beam_profile = False
-            for name, v in per.items():
-                results.append(dict(kind="step", program=name, dtype="bf16", beam=beam, slots=slots, rows=beam * slots, S=499,
-                                    steps_timed=timed_n[name], steps_only_ms_per_step=[round(x, 4) for x in v],
-                                    median=round(statistics.median(v), 4)))
-                print(json.dumps(results[-1]), flush=True)
+            raised = []
+            for temperature in (a.temperature if a.joint_ctc else [1.0]):
+                try:
+                    part = measure_config(a, dev, model, d, reqs, by_len, n, limits, beam, slots, temperature)
+                except KeyError as e:
+                    torch.cuda.synchronize()
+                    raised.append(temperature)
+                    print(f"# beam {beam} x {slots}, temperature {temperature}: {str(e)[:200]}", flush=True)
+                    continue
+                for r in part:
+                    if a.joint_ctc:
+                        r.update(ctc_weight=CTC_WEIGHT, ctc_rows=True, temperature=temperature, key_error_at_temperature=raised)
+                    print(json.dumps(r), flush=True)
+                results.extend(part)
+                break
+            else:
+                failed.append((beam, slots))
+                results.append(dict(kind="not_measured", beam=beam, slots=slots, ctc_weight=CTC_WEIGHT, key_error_at_temperature=raised))
             if a.json:
                 with open(a.json, "w") as f:
                     json.dump(results, f, indent=1)
     Fn.set_compute_dtype(torch.float32)
+    if failed:
+        sys.exit(f"beam_stream_timing: no timing for (beam, slots) {failed}: every temperature raised the CTC KeyError")
+
+
+def measure_config(a, dev, model, d, reqs, by_len, n, limits, beam, slots, temperature):
+    """The result rows of one (beam, slots) configuration.  KeyError (joint CTC only): a hypothesis left its CTC candidates."""
+    results = []
+    gs = generator(model, d, beam, joint_ctc=a.joint_ctc, temperature=temperature)
+    gb = generator(model, d, beam, "graph", joint_ctc=a.joint_ctc, temperature=temperature)
+    P = gs.BEAM_POLL_STEPS
+    arms = {"stream": lambda: stream_arm(gs, reqs, slots), "batch": lambda: batch_arm(gb, reqs, slots),
+            "batch_sorted": lambda: batch_arm(gb, by_len, slots)}
+    steps, polls, times = {}, {}, {k: [] for k in arms}
+    for name, fn in arms.items():                  # warm-up; every sentence of the stream runs to its own limit
+        _, (steps[name], polls[name], _, _, per_sentence) = timed(fn)
+        if per_sentence is not None:
+            assert per_sentence == {i: m + 1 for i, m in enumerate(limits)}, "a sentence ended before its limit"
+    assert steps["stream"] == stream_schedule([m + 1 for m in limits], slots, P)[0]
+    for rep in range(a.reps):
+        for name, fn in arms.items():
+            dt, out = timed(fn)
+            assert out[0] == steps[name]
+            times[name].append(dt)
+        print(f"# beam {beam} x {slots}, repeat {rep + 1}: " + ", ".join(f"{k} {v[-1]:.4f} s" for k, v in times.items()), flush=True)
+    gs.beam_profile = True                         # one more stream call with HIP events around every group of steps
+    try:
+        dt, (_, _, step_ms, timed_n, _) = timed(arms["stream"])
+    finally:
+        gs.beam_profile = False
+    for name in arms:
+        med = statistics.median(times[name])
+        r = dict(kind="throughput", arm=name, dtype="bf16", beam=beam, slots=slots, clips=N_CLIPS, seconds=[min(n) // RATE, max(n) // RATE],
+                 sum_steps=sum(m + 1 for m in limits), poll_steps=P, steps=steps[name], polls=polls[name],
+                 sentences_per_s=round(N_CLIPS / med, 3), call_s=[round(t, 4) for t in times[name]], call_s_median=round(med, 4),
+                 ms_per_step=round(med / steps[name] * 1e3, 4))
+        if name == "stream":
+            r.update(profiled_call_s=round(dt, 4), steps_only_s=round(step_ms * 1e-3, 4),
+                     steps_only_ms_per_step=round(step_ms / max(timed_n, 1), 4),
+                     overhead_ms_per_poll=round((dt - step_ms * 1e-3) / max(polls[name], 1) * 1e3, 4))
+        results.append(r)
+
+    # ---- per-step cost: the per-sentence program against the scalar program, `slots` clips of 10 s, the same rows ----
+    wav, pad = batch([10 * RATE] * slots, dev, seed=7)
+    same = [(b, wav[b]) for b in range(slots)]
+    sample = {"net_input": {"source": wav, "padding_mask": pad}}
+    per = {"per_sentence": [], "scalar": []}
+    timed_n = {}
+    gs.beam_profile = True
+    try:
+        for rep in range(a.reps + 1):              # (the first round is the warm-up)
+            list(gs.generate_stream(same, sentences=slots, max_src_len=10 * RATE, decode="graph",
+                                    **(dict(joint_ctc=True) if a.joint_ctc else {})))
+            st = gs.beam_stream_stats
+            ms, k = scalar_steps(gb, model, sample, slots)
+            if rep:
+                per["per_sentence"].append(st["step_ms"] / st["steps_timed"])
+                per["scalar"].append(ms / k)
+                timed_n = {"per_sentence": st["steps_timed"], "scalar": k}
+    finally:
+        gs.beam_profile = False
+    for name, v in per.items():
+        results.append(dict(kind="step", program=name, dtype="bf16", beam=beam, slots=slots, rows=beam * slots, S=499,
+                            steps_timed=timed_n[name], steps_only_ms_per_step=[round(x, 4) for x in v],
+                            median=round(statistics.median(v), 4)))
+    return results
 
 
 if __name__ == "__main__":
