@@ -493,11 +493,23 @@ int st5_ragged_gather_rows(const void* src, const int32_t* idx, void* dst, int64
  * with x[b, t, tau, c] = x[b * x_bs + t * x_ts + tau * tap_stride + c] (all strides in ELEMENTS; the caller's buffer holds the halo rows:
  * a dilated convolution is tap_stride = dilation * Cin over the zero-padded input, one phase of a stride-s transposed convolution is
  * taps = 2, tap_stride = Cin), y / residual addressed as base + b * bs + t * ts + co (padded or phase-interleaved layouts without
- * copies).  Cin in {32, 64, 128}, Cout in {32, 64}; x, w 16-byte aligned, strides multiples of 8 (x) / 4 (y, residual) elements,
- * else ST5_ERR_ARG / ST5_ERR_ALIGN.  act in {ST5_ACT_NONE, ST5_ACT_LRELU_01, ST5_ACT_LRELU_001}.  bias fp32 or NULL; residual NULL for none. */
+ * copies).  Cin in {32, 64, 128}, Cout in {32, 64}; x, w 16-byte aligned, y and residual 8-byte aligned, strides multiples of
+ * 8 (x) / 4 (y, residual) elements, else ST5_ERR_ARG / ST5_ERR_ALIGN.  The weight image lives in LDS:
+ * Cout * (taps * Cin + 8) * 2 bytes <= 160 KB, else ST5_ERR_ARG (nothing is launched).  act in {ST5_ACT_NONE, ST5_ACT_LRELU_01,
+ * ST5_ACT_LRELU_001}, else ST5_ERR_ARG.  bias fp32 or NULL; residual NULL for none. */
 int st5_conv1d_narrow(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int64_t y_bs, int32_t y_ts,
                       const void* residual, int64_t r_bs, int32_t r_ts, int32_t B, int32_t L, int32_t Cin, int32_t Cout, int32_t taps,
                       int32_t tap_stride, float alpha, float beta, int32_t act, void* stream);
+/* What st5_conv1d_narrow would run for these arguments, host only (nothing is launched or dereferenced): the error code the launch would
+ * return, and on ST5_OK plan[0..5] = { staged (1: the LDS-staged 32-channel form conv1d_narrow32_kernel<NJ>, 0: the direct form
+ * conv1d_narrow_kernel<CB, NJ>), CB = Cout / 32, NJ = Cin / 16, tiles per block, time steps per block tile (1024; 512 for Cout = 64),
+ * dynamic LDS bytes }.  The staged form needs Cout = 32, Cin in {32, 64}, x_ts == Cin, tap_stride % Cin == 0, y / residual 16-byte
+ * aligned with strides multiples of 8, and its LDS image (weights + 8 waves x (128 + (taps - 1) tap_stride / Cin) rows of 2 Cin + 16
+ * bytes) within 160 KB; ST5_NARROW_V1=1 in the environment selects the direct form throughout.  st5_conv1d_narrow takes its dispatch
+ * from the same function. */
+int st5_conv1d_narrow_plan(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int64_t y_bs, int32_t y_ts,
+                           const void* residual, int64_t r_bs, int32_t r_ts, int32_t B, int32_t L, int32_t Cin, int32_t Cout, int32_t taps,
+                           int32_t tap_stride, float alpha, float beta, int32_t act, int32_t* plan);
 /* The generator's last convolution (HF modeling_speecht5.py:3058-3062: 32 -> 1 channels, k = 7, tanh), bf16:
  *   y[b * L + t] = act(alpha * sum_{tau, c} w[tau * Cin + c] * x[b * x_bs + t * x_ts + tau * tap_stride + c] + bias[0]). */
 int st5_conv1d_cout1(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int32_t B, int32_t L, int32_t Cin,

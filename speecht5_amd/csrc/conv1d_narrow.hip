@@ -335,51 +335,51 @@ __global__ __launch_bounds__(256) void conv1d_cout1_kernel(const bf16_t* __restr
   }
 }
 
+// What a call of st5_conv1d_narrow runs: the ONE place the dispatch is decided (st5_conv1d_narrow_plan reports it, st5_conv1d_narrow
+// launches it).
+struct NarrowPlan {
+  NarrowArgs a;
+  int staged, CB, NJ, tile_t;      // staged: the second (LDS-staged) 32-channel form; tile_t: time steps per block tile
+  int tap_rows, rows_w, rows_in;   // staged form only
+  size_t lds;
+};
+
 template <int CB, int NJ>
-int launch_narrow(const NarrowArgs& a, hipStream_t s) {
-  const size_t lds = (size_t)CB * 32 * (a.K + 8) * sizeof(bf16_t);
+int launch_narrow(const NarrowPlan& p, hipStream_t s) {
   static bool attr_done = false;     // (per instantiation; idempotent)
   if (!attr_done) {
     if (hipFuncSetAttribute((const void*)conv1d_narrow_kernel<CB, NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
       return ST5_ERR_LAUNCH;
     attr_done = true;
   }
-  hipLaunchKernelGGL((conv1d_narrow_kernel<CB, NJ>), dim3((unsigned)(a.B * a.blocks_per_batch)), dim3(NTHR), lds, s, a);
+  hipLaunchKernelGGL((conv1d_narrow_kernel<CB, NJ>), dim3((unsigned)(p.a.B * p.a.blocks_per_batch)), dim3(NTHR), p.lds, s, p.a);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
 
 template <int NJ>
-int launch_narrow32(const NarrowArgs& a, int tap_rows, hipStream_t s, bool* fits) {
-  constexpr int ROWB = NJ * 32 + 16;
-  const int rows_w = TB * 32 + (a.taps - 1) * tap_rows, rows_in = a.L + (a.taps - 1) * tap_rows;
-  const size_t wbytes = ((size_t)32 * (a.K + 8) * 2 + 15) & ~(size_t)15;
-  const size_t per_wave = ((size_t)rows_w * ROWB + 15) & ~(size_t)15;      // (>= 129 rows: also holds the 32 x 36 float accumulator staging)
-  const size_t lds = wbytes + NW * per_wave;
-  *fits = lds <= 160 * 1024;
-  if (!*fits) return ST5_OK;
+int launch_narrow32(const NarrowPlan& p, hipStream_t s) {
   static bool attr_done = false;
   if (!attr_done) {
     if (hipFuncSetAttribute((const void*)conv1d_narrow32_kernel<NJ>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) != hipSuccess)
       return ST5_ERR_LAUNCH;
     attr_done = true;
   }
-  hipLaunchKernelGGL((conv1d_narrow32_kernel<NJ>), dim3((unsigned)(a.B * a.blocks_per_batch)), dim3(NTHR), lds, s, a, tap_rows, rows_w, rows_in);
+  hipLaunchKernelGGL((conv1d_narrow32_kernel<NJ>), dim3((unsigned)(p.a.B * p.a.blocks_per_batch)), dim3(NTHR), p.lds, s, p.a, p.tap_rows, p.rows_w,
+                     p.rows_in);
   HIP_CHECK_LAUNCH();
   return ST5_OK;
 }
 
-}  // namespace
-
-extern "C" int st5_conv1d_narrow(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int64_t y_bs,
-                                 int32_t y_ts, const void* residual, int64_t r_bs, int32_t r_ts, int32_t B, int32_t L, int32_t Cin,
-                                 int32_t Cout, int32_t taps, int32_t tap_stride, float alpha, float beta, int32_t act, void* stream) {
+int narrow_plan(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int64_t y_bs, int32_t y_ts,
+                const void* residual, int64_t r_bs, int32_t r_ts, int32_t B, int32_t L, int32_t Cin, int32_t Cout, int32_t taps,
+                int32_t tap_stride, float alpha, float beta, int32_t act, NarrowPlan* p) {
   if (!x || !w || !y || B <= 0 || L <= 0 || taps <= 0) return ST5_ERR_ARG;
   if ((Cout != 32 && Cout != 64) || (Cin != 32 && Cin != 64 && Cin != 128)) return ST5_ERR_ARG;
   // 16-byte fragment loads / 8-byte stores: every stride and base a multiple of 8 elements (4 for the outputs)
   if (x_ts % 8 || x_bs % 8 || tap_stride % 8 || y_ts % 4 || y_bs % 4 || (residual && (r_ts % 4 || r_bs % 4))) return ST5_ERR_ALIGN;
   if (((uintptr_t)x | (uintptr_t)w) % 16 || (uintptr_t)y % 8 || (residual && (uintptr_t)residual % 8)) return ST5_ERR_ALIGN;
-  NarrowArgs a;
+  NarrowArgs& a = p->a;
   a.x = (const bf16_t*)x; a.x_bs = x_bs; a.x_ts = x_ts; a.w = (const bf16_t*)w; a.bias = bias;
   a.y = (bf16_t*)y; a.y_bs = y_bs; a.y_ts = y_ts; a.R = (const bf16_t*)residual; a.r_bs = r_bs; a.r_ts = r_ts;
   a.B = B; a.L = L; a.Cin = Cin; a.taps = taps; a.tap_stride = tap_stride; a.K = taps * Cin;
@@ -394,23 +394,49 @@ extern "C" int st5_conv1d_narrow(const void* x, int64_t x_bs, int32_t x_ts, cons
   if (act != ACT_NONE && act != ACT_LRELU_01 && act != ACT_LRELU_001) return ST5_ERR_ARG;
   a.alpha = alpha; a.beta = beta; a.slope = act == ACT_LRELU_01 ? 0.1f : act == ACT_LRELU_001 ? 0.01f : 1.0f;
   if ((size_t)(Cout) * (a.K + 8) * sizeof(bf16_t) > 160 * 1024) return ST5_ERR_ARG;
-  hipStream_t s = (hipStream_t)stream;
+  p->staged = 0; p->CB = Cout / 32; p->NJ = Cin / 16; p->tile_t = tile_t;
+  p->tap_rows = p->rows_w = p->rows_in = 0;
+  p->lds = (size_t)p->CB * 32 * (a.K + 8) * sizeof(bf16_t);
   static const bool first_form_only = getenv("ST5_NARROW_V1") && getenv("ST5_NARROW_V1")[0] == '1';   // (A/B switch)
   const bool vec16 = (uintptr_t)y % 16 == 0 && y_ts % 8 == 0 && y_bs % 8 == 0 &&
                      (!residual || ((uintptr_t)residual % 16 == 0 && r_ts % 8 == 0 && r_bs % 8 == 0));
   if (Cout == 32 && !first_form_only && vec16 && x_ts == Cin && tap_stride % Cin == 0 && (Cin == 32 || Cin == 64)) {
-    bool fits = false;
-    const int rc = Cin == 32 ? launch_narrow32<2>(a, tap_stride / Cin, s, &fits) : launch_narrow32<4>(a, tap_stride / Cin, s, &fits);
-    if (rc != ST5_OK || fits) return rc;
+    const int rowb = p->NJ * 32 + 16;                                      // conv1d_narrow32_kernel's ROWB
+    const int tap_rows = tap_stride / Cin;
+    const int rows_w = TB * 32 + (taps - 1) * tap_rows, rows_in = L + (taps - 1) * tap_rows;
+    const size_t wbytes = ((size_t)32 * (a.K + 8) * 2 + 15) & ~(size_t)15;
+    const size_t per_wave = ((size_t)rows_w * rowb + 15) & ~(size_t)15;    // (>= 129 rows: also holds the 32 x 36 float accumulator staging)
+    const size_t lds = wbytes + NW * per_wave;
+    if (lds <= 160 * 1024) {                                               // (else: the first form)
+      p->staged = 1; p->tap_rows = tap_rows; p->rows_w = rows_w; p->rows_in = rows_in; p->lds = lds;
+    }
   }
-  if (Cout == 32) {
-    if (Cin == 32) return launch_narrow<1, 2>(a, s);
-    if (Cin == 64) return launch_narrow<1, 4>(a, s);
-    return launch_narrow<1, 8>(a, s);
-  }
-  if (Cin == 32) return launch_narrow<2, 2>(a, s);
-  if (Cin == 64) return launch_narrow<2, 4>(a, s);
-  return launch_narrow<2, 8>(a, s);
+  return ST5_OK;
+}
+
+}  // namespace
+
+extern "C" int st5_conv1d_narrow_plan(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int64_t y_bs,
+                                      int32_t y_ts, const void* residual, int64_t r_bs, int32_t r_ts, int32_t B, int32_t L, int32_t Cin,
+                                      int32_t Cout, int32_t taps, int32_t tap_stride, float alpha, float beta, int32_t act, int32_t* plan) {
+  if (!plan) return ST5_ERR_ARG;
+  NarrowPlan p;
+  const int rc = narrow_plan(x, x_bs, x_ts, w, bias, y, y_bs, y_ts, residual, r_bs, r_ts, B, L, Cin, Cout, taps, tap_stride, alpha, beta, act, &p);
+  if (rc != ST5_OK) return rc;
+  plan[0] = p.staged; plan[1] = p.CB; plan[2] = p.NJ; plan[3] = p.a.tiles_per_block; plan[4] = p.tile_t; plan[5] = (int32_t)p.lds;
+  return ST5_OK;
+}
+
+extern "C" int st5_conv1d_narrow(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int64_t y_bs,
+                                 int32_t y_ts, const void* residual, int64_t r_bs, int32_t r_ts, int32_t B, int32_t L, int32_t Cin,
+                                 int32_t Cout, int32_t taps, int32_t tap_stride, float alpha, float beta, int32_t act, void* stream) {
+  NarrowPlan p;
+  const int rc = narrow_plan(x, x_bs, x_ts, w, bias, y, y_bs, y_ts, residual, r_bs, r_ts, B, L, Cin, Cout, taps, tap_stride, alpha, beta, act, &p);
+  if (rc != ST5_OK) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (p.staged) return p.NJ == 2 ? launch_narrow32<2>(p, s) : launch_narrow32<4>(p, s);
+  if (p.CB == 1) return p.NJ == 2 ? launch_narrow<1, 2>(p, s) : p.NJ == 4 ? launch_narrow<1, 4>(p, s) : launch_narrow<1, 8>(p, s);
+  return p.NJ == 2 ? launch_narrow<2, 2>(p, s) : p.NJ == 4 ? launch_narrow<2, 4>(p, s) : launch_narrow<2, 8>(p, s);
 }
 
 extern "C" int st5_conv1d_cout1(const void* x, int64_t x_bs, int32_t x_ts, const void* w, const float* bias, void* y, int32_t B, int32_t L,

@@ -107,6 +107,7 @@ def conv_transpose1d(xp, L, convt, *, alpha=1.0):
     _, Cout, k = convt.weight.shape
     s = convt.stride[0]
     assert k == 2 * s and convt.padding[0] == s // 2 and Lp == L + 2
+    assert s % 2 == 0, "odd stride: the transposed convolution is L * s - 1 rows long, not the L * s rows written here"
     y = torch.empty(B, L * s, Cout, dtype=xp.dtype, device=xp.device)
 
     def build():
