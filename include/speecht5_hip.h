@@ -1013,6 +1013,15 @@ int st5_ctc_sents_admit(const int32_t* desc, int32_t n_admit, int32_t n_slots, i
 int st5_beam_lm_logprobs(const float* logits, int64_t ld, int32_t rows, int32_t V, float temperature, const void* lm_logits, int64_t lm_ld,
                          int32_t V_lm, float lm_weight, int lm_dtype, const int32_t* counter, int32_t max_len, float* lp, int64_t lp_ld,
                          void* stream);
+/* st5_beam_lm_logprobs_sents: st5_beam_lm_logprobs PER SENTENCE SLOT (the step of a beam-search stream with an LM,
+ * speecht5_amd/beam_stream.py), the same kernel body under a template flag.  rows = n_slots * beam; row r belongs to slot s = r / beam
+ * and is scored at step = pos[s] under maxlen[s] (clamped into [0, cap]) of the st5_beam_step_sents state.  A slot with done[s] != 0,
+ * or pos[s] outside 0 .. maxlen[s], returns before its first load: its rows of lp are not written.  Both forms (logits != NULL and
+ * in place); per live row the bits are st5_beam_lm_logprobs' at that step.  n_slots <= 65535, beam <= 32.  Launched behind the LM's
+ * per-row step, in front of st5_beam_step_sents_logprobs; with CTC behind st5_ctc_prefix_score_rows_sents. */
+int st5_beam_lm_logprobs_sents(const float* logits, int64_t ld, int32_t n_slots, int32_t beam, int32_t V, float temperature,
+                               const void* lm_logits, int64_t lm_ld, int32_t V_lm, float lm_weight, int lm_dtype, const int32_t* pos,
+                               const int32_t* maxlen, const int32_t* done, int32_t cap, float* lp, int64_t lp_ld, void* stream);
 
 /* Skinny-M GEMM of the decode loops (csrc/decode_gemm.hip): out[m, n] = epilogue(sum_k x[m, k] * w[n, k] + bias[n]) for 1 <= M <= 32,
  * w in nn.Linear layout [N, K] (stacked weights are one [sum N_i, K] matrix), x / w / res in `dtype`, fp32 accumulation.  Weight-streaming:

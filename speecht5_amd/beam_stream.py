@@ -2,8 +2,9 @@
 is stepped by ONE step program (step_program.py), enqueued kernel by kernel ("device") or captured once and replayed until the stream
 ends ("graph"); a slot whose sentence has finished is handed to the next waiting request at a poll.  generate(decode="device" /
 "graph") keeps every sentence of a call in the batch until the last one has finished (beam_graph.py), so a call costs max(steps) per
-sentence; the stream costs mean(steps), as the synthesis stream does for TTS (tts_stream.py).  No LM.  Attention-only search (the ST
-recipe and ASR decoding without CTC) by default; joint CTC / attention scoring with generate_stream(joint_ctc=True), see below.
+sentence; the stream costs mean(steps), as the synthesis stream does for TTS (tts_stream.py).  Attention-only search (the ST recipe
+and ASR decoding without CTC) by default; joint CTC / attention scoring with generate_stream(joint_ctc=True) and Transformer-LM
+shallow fusion for a generator built with an lm_model, alone or together (the ASR recipe), see below.
 
 What makes it possible is that every position-dependent launch of the step reads the position of the SLOT where beam_graph's step
 reads one counter: the pre-net row (st5_beam_embed_sents), the self-attention K|V slot write (st5_gemm_skinny_rows over pos_rows), the
@@ -45,7 +46,19 @@ Joint scoring brings a per-sentence failure: a hypothesis continued by a token o
 A flagged slot yields nothing, finished or not: its key goes to stream.failed and beam_stream_stats["failed"], its occupant is cleared
 and the slot is handed on like a finished one (the admission clears the flag; if nobody waits the slot runs on to its limit and is
 never read).  When the stream ends the failed keys are raised in one KeyError (with the refusals' text when there are any); every other
-sentence has completed by then."""
+sentence has completed by then.
+
+Shallow fusion (a generator built with lm_model; no keyword: such a generator was refused before): the LM's step in its per-slot form
+(TransformerLanguageModel.device_step_sents: st5_beam_embed_sents with the LM's tables, the layers with K|V into slot pos_rows[r],
+st5_lm_decode_attn_rows, the final LayerNorm, the output projection with fp32 output) follows the decoder's projection, then
+st5_beam_lm_logprobs_sents (csrc/beam_lm.hip) puts the LM term into the step's log-probabilities, in beam_graph.py's order.  Without
+CTC: st5_beam_lm_logprobs_sents on the decoder's logits into lp [rows, V], st5_beam_step_sents_logprobs on lp, the reorder.  With
+joint_ctc: candidates, prefix scores and mix, st5_beam_lm_logprobs_sents in place on ctc.lp, st5_beam_step_sents_logprobs, select, the
+reorder.  The LM's slot caches are read through the stream's ONE ancestry table (init_decode(anc=bs.anc)), which the admission resets
+and the reorder reorders; an admission does nothing for the LM, and a handed-over slot's stale K|V are never read (device_step_sents
+says why).  Refused, each with a ValueError naming lm_model before anything is enqueued: an LM that is not a TransformerLanguageModel,
+V_lm > vocab_size, and cap + 2 positions more than lm.max_positions() (cap: the step limit at max_src_len, which every request's limit
+is held to).  Without an LM the launch list is what it is without this paragraph."""
 import collections
 import time
 
@@ -82,7 +95,14 @@ def check_arguments(gen, sentences, max_src_len, decode, joint_ctc=False):
         raise ValueError("generate_stream: ctc_weight > 0 needs joint_ctc=True (joint CTC / attention scoring per sentence slot; a "
                          "sentence whose hypothesis leaves its CTC candidates then fails by key, see generate_stream) or generate()")
     if gen.lm_model is not None:
-        raise ValueError("generate_stream: lm_model is not supported (the LM's step has no per-sentence form); use generate()")
+        # in front of check_generator, which refuses the same LMs in the words of generate()'s `decode` modes
+        from .transformer_lm import TransformerLanguageModel
+        if not isinstance(gen.lm_model, TransformerLanguageModel):
+            raise ValueError(f"generate_stream: an LM (lm_model) of type {type(gen.lm_model).__name__} is not supported (only "
+                             f"speecht5_amd.transformer_lm.TransformerLanguageModel has a per-sentence step); use generate()")
+        V_lm = gen.lm_model.decoder.output_projection.weight.shape[0]      # the columns of the LM's logits, what the kernel is given
+        if V_lm > gen.vocab_size:
+            raise ValueError(f"generate_stream: lm_model has a dictionary of {V_lm} symbols, more than the model's {gen.vocab_size}")
     beam_graph.check_generator(gen)
     if not isinstance(sentences, int) or isinstance(sentences, bool) or sentences < 1:
         raise ValueError(f"sentences must be an integer >= 1, got {sentences!r}")
@@ -99,6 +119,10 @@ def check_arguments(gen, sentences, max_src_len, decode, joint_ctc=False):
     cap = step_limit(gen, max_src_len)
     if cap < gen.min_len:
         raise ValueError(f"max_src_len={max_src_len}: the step limit {cap} is below min_len={gen.min_len}")
+    if gen.lm_model is not None and cap + 2 > gen.lm_model.max_positions():
+        # every request's limit is held to cap (BeamStream._encode), so this covers them all
+        raise ValueError(f"generate_stream: lm_model takes {gen.lm_model.max_positions()} positions, the step limit at max_src_len="
+                         f"{max_src_len} needs cap + 2 = {cap + 2}; lower max_src_len, max_len_a or max_len_b")
     return S, cap
 
 
@@ -169,14 +193,30 @@ class BeamStreamDecode:
         proj = post.output_projection
         self.logits = lin(x, [proj.weight], [proj.bias], new(rows, V, dt=torch.float32), out_f32=True)
         rules = dict(temperature=gen.temperature, pad=gen.pad, unk=gen.unk, eos=gen.eos, unk_penalty=gen.unk_penalty, min_len=gen.min_len)
-        if self.ctc is None:
+        # shallow fusion: the LM's per-row step over the same rows and the stream's one ancestry table, behind the decoder's projection
+        # (beam_graph.py's order).  Its caches and lp need no fill: a row's attention reads positions 0 .. pos_rows[r] of its own slot,
+        # all written by the occupant's steps (an idle slot stands at position 0 and rewrites it in every step), and a slot that is
+        # done or idle never has its LM logits or its rows of lp read (st5_beam_lm_logprobs_sents and the beam step return for it).
+        lm, w_lm = gen.lm_model, float(gen.lm_weight)
+        self.lm_state = self.lm_logits = self.lp = None
+        if lm is not None:
+            self.lm_state = lm.init_decode(rows, Tmax, anc=bs.anc)
+            self.lm_logits = lm.device_step_sents(self.lm_state, bs, prog)
+        if self.ctc is None and lm is None:
             add(lambda: Fn.beam_step_sents(self.logits, V, bs, self.never, self.len_div, **rules))
+        elif self.ctc is None:
+            # log-probabilities with the LM term, the beam step on them
+            self.lp = new(rows, V, dt=torch.float32)
+            add(lambda: Fn.beam_lm_logprobs_sents(self.lp, V, bs, self.lm_logits, w_lm, logits=self.logits, temperature=gen.temperature))
+            add(lambda: Fn.beam_step_sents_logprobs(self.lp, V, bs, self.never, self.len_div, **rules))
         else:
-            # beam_graph.py's CTC step per slot: log-probabilities and candidates, prefix scores mixed into them, the beam step on
-            # them, the continued rows' prefix states
+            # beam_graph.py's CTC step per slot: log-probabilities and candidates, prefix scores mixed into them, [the LM term,] the
+            # beam step on them, the continued rows' prefix states
             ctc = self.ctc
             add(lambda: Fn.beam_ctc_candidates_sents(self.logits, V, bs, ctc, self.never, gen.temperature))
             add(lambda: Fn.ctc_prefix_score_rows_sents(bs, ctc))
+            if lm is not None:
+                add(lambda: Fn.beam_lm_logprobs_sents(ctc.lp, V, bs, self.lm_logits, w_lm))
             add(lambda: Fn.beam_step_sents_logprobs(ctc.lp, V, bs, self.never, self.len_div, **rules))
             add(lambda: Fn.ctc_select_sents(bs, ctc))
         add(lambda: Fn.beam_reorder_sents(bs))
@@ -184,11 +224,14 @@ class BeamStreamDecode:
 
     def buffer_ptrs(self):
         """Data pointers of what the graph has baked in and must never move: slot K/V, encoder-side K|V, key-padding bytes, the
-        beam-step state, its image and the records; with joint_ctc the CTC buffers."""
+        beam-step state, its image and the records; with joint_ctc the CTC buffers; with an LM its slot caches, its logits and
+        (without CTC) the fused log-probabilities."""
         bs = self.bs
         ctc = () if self.ctc is None else tuple(t.data_ptr() for t in self.ctc.buffers())
+        lm = () if self.lm_state is None else tuple(t.data_ptr() for t in self.lm_state.kv) + tuple(
+            t.data_ptr() for t in (self.lm_logits, self.lp) if t is not None)
         return tuple(t.data_ptr() for t in self.kv) + tuple(kv.data_ptr() for kv, _ in self.xkv) + tuple(
-            t.data_ptr() for t in (self.kpm, bs.anc, bs.tok, bs.score, bs.image, bs.pos_rows, bs.rec_tok, bs.rec_pos, self.logits)) + ctc
+            t.data_ptr() for t in (self.kpm, bs.anc, bs.tok, bs.score, bs.image, bs.pos_rows, bs.rec_tok, bs.rec_pos, self.logits)) + ctc + lm
 
     def admit(self, pairs, bos):
         """pairs: [(slot, request)].  Per request the K|V projection of its encoder rows (the single call's GEMM shape) into the slot's

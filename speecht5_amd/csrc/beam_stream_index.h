@@ -52,8 +52,11 @@ BST_HD long long bst_cell_off(long long row, long long ld, long long col) { retu
 // frames are its sentence's.  Offsets of state and r_new count float2 cells.
 // the slot of a hypothesis row
 BST_HD long long bst_slot_of(long long row, long long beam) { return row / beam; }
-// does a slot take the CTC part of a step?  Not when it is done (finished or idle), and only at the steps the beam step runs
-BST_HD bool bst_ctc_live(long long done, long long pos, long long maxlen) { return done == 0 && bst_step_live(pos, maxlen); }
+// does a slot take the scoring part of a step (the CTC kernels in front of the beam step; the LM term, csrc/beam_lm.hip
+// st5_beam_lm_logprobs_sents; tests/test_beam_stream_lm_cpu.py sweeps it)?  Not when it is done (finished or idle), and only at the
+// steps the beam step runs.  bst_ctc_live is the name the CTC kernels know it by.
+BST_HD bool bst_slot_live(long long done, long long pos, long long maxlen) { return done == 0 && bst_step_live(pos, maxlen); }
+BST_HD bool bst_ctc_live(long long done, long long pos, long long maxlen) { return bst_slot_live(done, pos, maxlen); }
 // does the select behind a step act on a slot?  Only where that step moved it and wrote continuing rows: the step at the limit
 // writes none, and it leaves pos = maxlen + 1
 BST_HD bool bst_select_live(long long moved, long long pos, long long maxlen) { return moved != 0 && pos >= 1 && pos <= maxlen; }

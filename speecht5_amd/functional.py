@@ -4248,6 +4248,21 @@ def beam_lm_logprobs(lp, V, bs, lm_logits, lm_weight, logits=None, temperature=1
     return lp
 
 
+def beam_lm_logprobs_sents(lp, V, bs, lm_logits, lm_weight, logits=None, temperature=1.0):
+    """beam_lm_logprobs per slot (bs: BeamStreamState): the rows of every slot that is not done, at its own step bs.pos[s] under
+    bs.maxlen[s]; a done or idle slot's rows of lp are not written.  Both forms, the same arguments."""
+    V_lm = lm_logits.shape[1]
+    assert lp.dtype == torch.float32 and lp.stride(1) == 1 and lp.shape[0] == bs.rows and lp.shape[1] >= V
+    assert lm_logits.stride(1) == 1 and lm_logits.shape[0] == bs.rows and V_lm <= V
+    assert logits is None or (logits.dtype == torch.float32 and logits.stride(1) == 1 and logits.shape[0] == bs.rows and
+                              logits.shape[1] >= V and logits.data_ptr() != lp.data_ptr())
+    hip.check(hip.lib().st5_beam_lm_logprobs_sents(hip.ptr(logits), 0 if logits is None else logits.stride(0), bs.n_slots, bs.beam, int(V),
+                                                   float(temperature), lm_logits.data_ptr(), lm_logits.stride(0), V_lm, float(lm_weight),
+                                                   _dt(lm_logits), bs.pos.data_ptr(), bs.maxlen.data_ptr(), bs.done.data_ptr(), bs.cap,
+                                                   lp.data_ptr(), lp.stride(0), hip.stream()), "st5_beam_lm_logprobs_sents")
+    return lp
+
+
 # -------------------------------------------------------------------------------------------------
 # Speaker-identification head (s2c, speaker_decoder_postnet.py): BatchNorm1d over [B, C] rows (st5_batchnorm_act_*), cosine logits
 # F.linear(F.normalize(x), F.normalize(W)) (st5_norm_rows + st5_gemm) with the AM / AAM margin (csrc/speaker_head.hip), and the time

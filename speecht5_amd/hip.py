@@ -309,6 +309,8 @@ _SIGS = {
                                     c_int32, c_int32, c_int, c_void_p]),
     "st5_beam_lm_logprobs": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_float, c_void_p, c_int64, c_int32, c_float, c_int, c_void_p,
                                      c_int32, c_void_p, c_int64, c_void_p]),
+    "st5_beam_lm_logprobs_sents": (c_int, [c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_void_p, c_int64, c_int32, c_float,
+                                           c_int, c_void_p, c_void_p, c_void_p, c_int32, c_void_p, c_int64, c_void_p]),
     "st5_angular_margin_fwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float, c_float, c_void_p]),
     "st5_angular_margin_bwd": (c_int, [c_void_p, c_int64, c_void_p, c_void_p, c_int64, c_void_p, c_int64, c_int32, c_int32, c_int32, c_float,
                                        c_float, c_void_p]),

@@ -301,7 +301,8 @@ class SpeechT5Task(LegacyFairseqTask):
 
     def inference_stream(self, generator, models, requests, **kwargs):
         """Streaming beam search (SequenceGenerator.generate_stream): (key, hyps) in completion order; `models` is ignored, as in the
-        generator's generate() (the ensemble was fixed at construction)."""
+        generator's generate() (the ensemble was fixed at construction).  A generator from build_generator with an lm_model (a
+        fairseq transformer_lm is converted there) decodes with shallow fusion; joint_ctc=True adds the CTC scores: the ASR recipe."""
         return generator.generate_stream(requests, **kwargs)
 
     @property

@@ -22,6 +22,7 @@ Two ways to run it:
   value.  Attention of the newest position: st5_lm_decode_attn (csrc/lm_decode.hip).
   device_step: the same step as a list of launches behind a device step counter (step_program.py), for the device-stepped beam
   search (beam_graph.py): the slot caches are read through the text decoder's ancestry table, there is no reorder of the LM's own.
+  device_step_sents: that step with one position per sentence slot, for the beam-search stream (beam_stream.py).
 
 Layouts it does not implement raise NotImplementedError naming the option: adaptive softmax / adaptive input, learned positions,
 layernorm_embedding, post-LN layers, no_decoder_final_norm, character embeddings, decoder_input_dim != decoder_embed_dim."""
@@ -282,6 +283,39 @@ class TransformerLanguageModel(nn.Module):
             Fn.lm_decode_attn_dev(q, slots, state.anc, bs.counter, 1, Tmax, H, hd, ctx, state.ws)
 
         y = append_layers(prog, x, list(dec.layers), state.kv, Tmax, bs.counter, self_attn, final_norm=dec.layer_norm)
+        proj = dec.output_projection
+        return prog.lin(y, [proj.weight], [None], prog.new(rows, proj.weight.shape[0], dt=torch.float32), out_f32=True)
+
+    @torch.no_grad()
+    def device_step_sents(self, state, bs, prog):
+        """device_step PER SENTENCE SLOT, the LM's share of one step of a beam-search stream (beam_stream.BeamStreamDecode): `bs` is a
+        functional.BeamStreamState, every slot of `beam` rows has its own position bs.pos[slot].  The embedding is st5_beam_embed_sents
+        with the LM's tables at position pos[slot] + padding_idx + 1, the layers are append_layers(per_row=True) over bs.pos_rows (row
+        r's K|V go to slot pos_rows[r] of its cache), the self-attention is st5_lm_decode_attn_rows over state.anc and bs.pos_rows;
+        then the final LayerNorm and the output projection with fp32 output.  Returns the buffer of the logits [rows, V_lm].
+        `state`: init_decode(rows, cap + 2, anc=bs.anc).  The LM reads the stream's ONE ancestry table, which st5_beam_sents_admit
+        resets and st5_beam_reorder_sents reorders: it has no table and no reorder of its own, and an admission does nothing for it.
+        A slot handed to a new sentence keeps the K|V of its earlier occupant in the LM's caches.  That is harmless: the admission
+        resets the slot's rows of the ancestry table to themselves and its position to 0; the step at position p writes slot p of
+        every row of the sentence before the attention of that step reads positions 0 .. p, and a reorder only ever points a row at
+        rows of its own sentence slot.  So every (row, position) an attention reads has been written by this sentence, at a step
+        <= the current one, and positions behind p are never read."""
+        dec = self.decoder
+        rows, Tmax = state.rows, state.Tmax
+        if bs.rows != rows or bs.Tmax != Tmax:
+            raise ValueError(f"device_step_sents: a decode state of {rows} rows x {Tmax} positions beside a stream state of {bs.rows} x "
+                             f"{bs.Tmax}")
+        if state.anc.data_ptr() != bs.anc.data_ptr():
+            raise ValueError("device_step_sents: the decode state must read the stream's ancestry table (init_decode(anc=bs.anc))")
+        table = dec.embed_tokens.weight.detach()
+        pos = dec.embed_positions.table(Tmax + dec.padding_idx + 2, table.device)
+        x = prog.new(rows, self.num_heads * self.head_dim)
+        prog.add(lambda: Fn.beam_embed_sents(table, bs, pos, dec.padding_idx + 1, dec.embed_scale, x))
+
+        def self_attn(q, slots, ctx, H, hd):
+            Fn.lm_decode_attn_rows(q, slots, state.anc, bs.pos_rows, 1, Tmax, H, hd, ctx, state.ws)
+
+        y = append_layers(prog, x, list(dec.layers), state.kv, Tmax, bs.pos_rows, self_attn, final_norm=dec.layer_norm, per_row=True)
         proj = dec.output_projection
         return prog.lin(y, [proj.weight], [None], prog.new(rows, proj.weight.shape[0], dt=torch.float32), out_f32=True)
 

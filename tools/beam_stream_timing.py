@@ -26,8 +26,18 @@ for every arm) sharpens it, the values are tried in order and the first under wh
 measured and recorded with the ones that raised; a configuration under which every temperature raises is reported and the tool exits
 non-zero.
 
+--lm (combinable with --joint-ctc): the same workload and arms with Transformer-LM shallow fusion: a seeded random LM of the
+transformer_lm_t5 preset as tools/beam_lm_timing.py builds it (20 layers x 1280, FFN 6144, 16 heads, 83 symbols), lm_weight 0.3.  The
+stream is generate_stream of a generator built with that lm_model, the batch arms are generate(decode="graph", exact_rows=True,
+lm_model=...), the per-step comparison is the per-slot LM step (TransformerLanguageModel.device_step_sents,
+st5_beam_lm_logprobs_sents) against the scalar LM step of beam_graph.py (the parent commit's step, unchanged) at the same rows and
+limits.  The LM's term (0.3 x a nearly flat log-softmax) is far below the ~150 that keep eos away, so every sentence still runs to its
+limit.
+
     python tools/beam_stream_timing.py [--reps 5] [--json profiles/beam_stream_timing.json]
-    python tools/beam_stream_timing.py --joint-ctc [--temperature 0.25 0.05] [--json profiles/beam_stream_ctc_timing.json]"""
+    python tools/beam_stream_timing.py --joint-ctc [--temperature 0.25 0.05] [--json profiles/beam_stream_ctc_timing.json]
+    python tools/beam_stream_timing.py --lm [--json profiles/beam_stream_lm_timing.json]
+    python tools/beam_stream_timing.py --lm --joint-ctc [--json profiles/beam_stream_ctc_lm_timing.json]"""
 import argparse
 import json
 import os
@@ -42,6 +52,7 @@ from speecht5_amd import beam_graph  # noqa: E402
 from speecht5_amd import functional as Fn  # noqa: E402
 from speecht5_amd.step_program import on_decode_stream, run_steps  # noqa: E402
 from speecht5_amd.tts_stream import stream_schedule  # noqa: E402
+from beam_lm_timing import LM_WEIGHT, build_lm  # noqa: E402
 from beam_slots_timing import build_model, timed  # noqa: E402
 from speech_rows_timing import RATE, batch  # noqa: E402
 
@@ -70,11 +81,12 @@ def clips(dev, seed=64):
 CTC_WEIGHT = 0.5
 
 
-def generator(model, d, beam, decode="concat", joint_ctc=False, temperature=1.0):
+def generator(model, d, beam, decode="concat", joint_ctc=False, temperature=1.0, lm=None):
     from speecht5_amd.sequence_generator import SequenceGenerator
     ctc = dict(ctc_weight=CTC_WEIGHT, ctc_rows=True, temperature=temperature) if joint_ctc else {}
+    fuse = dict(lm_model=lm, lm_weight=LM_WEIGHT) if lm is not None else {}
     return SequenceGenerator([model], d, beam_size=beam, max_len_a=STEPS_PER_SECOND / RATE, max_len_b=0, exact_rows=True, decode=decode,
-                             **ctc)
+                             **ctc, **fuse)
 
 
 def stream_arm(gen, reqs, slots):
@@ -121,12 +133,14 @@ def main():
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--json", default=None)
     ap.add_argument("--joint-ctc", action="store_true")
+    ap.add_argument("--lm", action="store_true", help="Transformer-LM shallow fusion (transformer_lm_t5 preset, lm_weight 0.3)")
     ap.add_argument("--temperature", type=float, nargs="+", default=[0.25, 0.05])
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     model, d = build_model(dev, torch.bfloat16)
     assert len(d) == 83
     suppress_eos(model, d)
+    lm = build_lm(dev, len(d)) if a.lm else None
     reqs, n = clips(dev)
     by_len = sorted(reqs, key=lambda q: q[1].numel())
     limits = [int(STEPS_PER_SECOND / RATE * m) for m in n]
@@ -136,7 +150,7 @@ def main():
             raised = []
             for temperature in (a.temperature if a.joint_ctc else [1.0]):
                 try:
-                    part = measure_config(a, dev, model, d, reqs, by_len, n, limits, beam, slots, temperature)
+                    part = measure_config(a, dev, model, d, reqs, by_len, n, limits, beam, slots, temperature, lm)
                 except KeyError as e:
                     torch.cuda.synchronize()
                     raised.append(temperature)
@@ -145,6 +159,8 @@ def main():
                 for r in part:
                     if a.joint_ctc:
                         r.update(ctc_weight=CTC_WEIGHT, ctc_rows=True, temperature=temperature, key_error_at_temperature=raised)
+                    if a.lm:
+                        r.update(lm="transformer_lm_t5", lm_weight=LM_WEIGHT)
                     print(json.dumps(r), flush=True)
                 results.extend(part)
                 break
@@ -159,11 +175,11 @@ def main():
         sys.exit(f"beam_stream_timing: no timing for (beam, slots) {failed}: every temperature raised the CTC KeyError")
 
 
-def measure_config(a, dev, model, d, reqs, by_len, n, limits, beam, slots, temperature):
+def measure_config(a, dev, model, d, reqs, by_len, n, limits, beam, slots, temperature, lm=None):
     """The result rows of one (beam, slots) configuration.  KeyError (joint CTC only): a hypothesis left its CTC candidates."""
     results = []
-    gs = generator(model, d, beam, joint_ctc=a.joint_ctc, temperature=temperature)
-    gb = generator(model, d, beam, "graph", joint_ctc=a.joint_ctc, temperature=temperature)
+    gs = generator(model, d, beam, joint_ctc=a.joint_ctc, temperature=temperature, lm=lm)
+    gb = generator(model, d, beam, "graph", joint_ctc=a.joint_ctc, temperature=temperature, lm=lm)
     P = gs.BEAM_POLL_STEPS
     arms = {"stream": lambda: stream_arm(gs, reqs, slots), "batch": lambda: batch_arm(gb, reqs, slots),
             "batch_sorted": lambda: batch_arm(gb, by_len, slots)}
